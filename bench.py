@@ -33,8 +33,14 @@ ahead of the frame that the reference does not know either.
   torch.distributed.run the ranks are the launcher's, without a launcher environment bench.py starts the N ranks
   itself as fresh child processes (before this process has touched a GPU).
 
+  python bench.py --dump-outputs DIR                       after the timed steps: what the timed path handed its caller in its
+                                                           last step (pose, frame record, result arrays) as DIR/<name>.npy
+  python bench.py --full                                   everything below besides the headline: roofline, CPU baseline and
+                                                           parity, secondary legs. A plain run (no --full) sets up, warms up,
+                                                           times the steps, writes its outputs and prints the result line.
+
 Prints ONE JSON line on rank 0. `value` is measured with the images resident in HBM before the timed region;
-secondary measurements of the same run (N = 1 only) are reported next to it:
+with --full, secondary measurements of the same run (N = 1 only) are reported next to it:
   host_images            the same frames with BOTH images arriving from pinned host memory every frame (H2D inside the
                          timed region, overlapped with the frame in flight)
   sequential_step10      step [10] as three host-driven operator calls after the frame's result (updateWeightBin,
@@ -318,6 +324,63 @@ def replay_split(stamps, replayed):
     return out
 
 
+# ---- --dump-outputs ------------------------------------------------------------------------------------------------
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_TRAJECTORY_FRAMES = 65536  # poses of the last timed frames at most (64 B each)
+
+
+def struct_values(s):
+    """Every scalar of a ctypes frame record (nested records and arrays included), in declaration order."""
+    import ctypes as C
+    vals = []
+    for name, _ in s._fields_:
+        v = getattr(s, name)
+        if isinstance(v, C.Structure):
+            vals += struct_values(v)
+        elif isinstance(v, C.Array):
+            vals += list(v)
+        else:
+            vals.append(v)
+    return vals
+
+
+def result_arrays(r, prefix=""):
+    """The arrays of a frame operator's result dict (nested dicts and ctypes records flattened under prefixed names)."""
+    import ctypes as C
+    out = {}
+    for k, v in r.items():
+        if isinstance(v, dict):
+            out.update(result_arrays(v, f"{prefix}{k}_"))
+        elif isinstance(v, C.Structure):
+            out[prefix + k] = np.array(struct_values(v), np.float64)
+        elif isinstance(v, np.ndarray):
+            out[prefix + k] = v
+    return out
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 where that holds the values exactly (f32, u8, i16, bool), float64
+    otherwise (f64, i32, i64)."""
+    os.makedirs(path, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        exact32 = (a.dtype.kind == "f" and a.dtype.itemsize <= 4) or (a.dtype.kind in "biu" and a.dtype.itemsize <= 2)
+        conv[name] = np.ascontiguousarray(a, np.float32 if exact32 else np.float64)
+    total = sum(a.nbytes for a in conv.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes, more than {DUMP_LIMIT_BYTES}")
+    for name, a in conv.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def loop_outputs(info, traj, K):
+    """A closed loop's last timed step as its caller receives it (the frame record of result() / runSequence()), and the
+    poses of the timed frames."""
+    return {"T_wc": np.array(info.T_wc, np.float32).reshape(4, 4), "frame_info": np.array(struct_values(info), np.float64),
+            "trajectory_T_wc": np.stack(traj[len(traj) - min(K, DUMP_TRAJECTORY_FRAMES):]).astype(np.float32)}
+
+
 def cpu_model():
     try:
         for ln in open("/proc/cpuinfo"):
@@ -589,6 +652,17 @@ def _render_one(job):
     return k, L, R
 
 
+_RENDER = {}  # the stream render_stream renders and its poses: built once, inherited by the forked workers
+
+
+def _render_frame(k):
+    """Frame k of _RENDER's stream: what _render_one((cfg, seed, k, n)) renders, without building the stream and its n poses
+    again for every frame."""
+    st, poses = _RENDER["stream"]
+    L, R, _ = st.render_pair(poses[k])
+    return k, L, R
+
+
 def scene_length(cfg, n_frames):
     """The synthetic corridor ends in a wall at 600 m (the scene every round rendered): a forward-driving stream longer
     than ~700 frames at 0.8 m per frame would drive into it — the tracks die, the loop ends like the reference's would
@@ -612,13 +686,16 @@ def render_stream(cfg, seed, n, workers):
         except Exception:
             pass
     import multiprocessing as mp
+    from visual_odometry_ros_amd import synthetic as S
     workers = max(1, min(workers or host_cores(), n, 32))
-    jobs = [(cfg, seed, k, n) for k in range(n)]
+    st = S.StereoStream(width=cfg["W"], height=cfg["H"], K=cfg["K"], n_u=cfg["n_u"], n_v=cfg["n_v"], seed=seed, speed=cfg["speed"],
+                        z_end=scene_length(cfg, n), tex_scale=cfg.get("tex_scale", 1.0))
+    _RENDER["stream"] = (st, st.poses(n))  # (once, not per frame: the poses of a long stream cost more than a tenth of a frame)
     if workers == 1:
-        out = [_render_one(j) for j in jobs]
+        out = [_render_frame(k) for k in range(n)]
     else:
         with mp.get_context("fork").Pool(workers) as pool:
-            out = pool.map(_render_one, jobs, chunksize=1)
+            out = pool.map(_render_frame, range(n), chunksize=1)
     out.sort(key=lambda t: t[0])
     try:
         np.savez(cache, L=np.stack([o[1] for o in out]), R=np.stack([o[2] for o in out]))
@@ -641,6 +718,50 @@ LOOP_PRIME_GROWING = 3
 
 def loop_frames_needed(args):
     return LOOP_PRIME + args.warmup + args.steps + 2  # (+2: the frame in flight at the end of the timed region, and the pair prefetched under it)
+
+
+def loop_roofline(args, ctx, infos, n_kp_bins, win, eff_levels, eff_levels_bwd):
+    """--full: the closed loop's roofline from the event-bracketed launches of the timed frames and the algorithmic bytes of
+    every frame (n_kp_bins: the keypoint pass over every left image before the loop)."""
+    klt_n, klt_ms = ctx.profile_get(1)
+    launches = max(klt_n, 1)
+    strict = bool(args.strict_border)
+    b_req = b_spec = b_des = 0
+    for (k, n_in, n_l0l1, n_refine, n_rep, n_cand_emit, n_new, n_final, kf, lba, it, nba) in infos:
+        per = klt_bytes_per_point_level(win)
+        feat = per * (n_in + (n_refine - n_rep)) * eff_levels + IC_BYTES_8D * n_l0l1
+        cand_all = per * n_kp_bins[k] * (eff_levels + eff_levels_bwd)   # every bin's candidate is tracked (speculation)
+        cand_req = per * n_cand_emit * (eff_levels + eff_levels_bwd)     # the candidates the reference would track
+        b_req += feat + cand_req
+        b_spec += cand_all - cand_req
+        b_des += (IC_RECORD_BYTES * n_in if strict else 0) + POINT_IO_BYTES * (n_in + n_kp_bins[k])
+    achieved = ((b_req + b_spec) / launches) / (klt_ms / launches * 1e-3) / 1e9 if klt_n else 0.0
+    achieved_req = (b_req / launches) / (klt_ms / launches * 1e-3) / 1e9 if klt_n else 0.0
+    counters = stamped_counters(args.config)
+    issue = issue_roofline(counters, klt_ms, launches) if klt_n else None
+    out = {
+        "roofline": {
+            "bound": "hbm",
+            "kernel": f"frame_track_kernel<{win}>",
+            "achieved": round(achieved, 2),
+            "peak": HBM_PEAK_GBS,
+            "unit": "GB/s",
+            "frac": round(achieved / HBM_PEAK_GBS, 5),
+            "traffic": counters["traffic"],
+            "achieved_required_only": round(achieved_req, 2),
+            "frac_required_only": round(achieved_req / HBM_PEAK_GBS, 5),
+            "alg_bytes_per_launch": {"survey_8d_required": round(b_req / launches), "survey_8d_speculative": round(b_spec / launches),
+                                     "design_records": round(b_des / launches)},
+            "avg_launch_us": round(1e3 * klt_ms / launches, 2),
+            "note": "achieved = SURVEY 8(d) bytes (features + every bucket's candidate) / launch duration (HIP events, live); "
+                    "required_only leaves out the candidates the reference would not have tracked; the path is issue/latency-"
+                    "bound, the fraction is reported because the metric asks for it (DESIGN.md §6)",
+        },
+        "roofline_issue": issue,
+    }
+    if counters["counters_note"]:
+        out["roofline"]["counters_note"] = counters["counters_note"]
+    return out
 
 
 def run_loop(cfg, args, rank, local_rank, world, torch, V, barrier, dev, imgs, secondary):
@@ -666,13 +787,14 @@ def run_loop(cfg, args, rank, local_rank, world, torch, V, barrier, dev, imgs, s
     eff_levels = ctx.pyramid_levels(W, H, win, lvl) + 1
     eff_levels_bwd = ctx.pyramid_levels(W, H, win, lvl - 1) + 1
     # bins that hold a keypoint, per left image: the candidates the frame kernel tracks speculatively (bytes accounting)
-    fe = V.FeatureExtractor(ctx)
-    fe.initParams(W, H, cfg["n_u"], cfg["n_v"], THRES_FAST=cfg["thres_fast"])
     n_kp_bins = []
-    for k in range(F):
-        ctx.set_image_device(4, d_L[k].data_ptr(), W, H, W)
-        n_kp_bins.append(bins_with_keypoints(fe, 4))
-    ctx.synchronize()
+    if args.full:
+        fe = V.FeatureExtractor(ctx)
+        fe.initParams(W, H, cfg["n_u"], cfg["n_v"], THRES_FAST=cfg["thres_fast"])
+        for k in range(F):
+            ctx.set_image_device(4, d_L[k].data_ptr(), W, H, W)
+            n_kp_bins.append(bins_with_keypoints(fe, 4))
+        ctx.synchronize()
     ptr = [((d_L[k].data_ptr(), W), (d_R[k].data_ptr(), W)) for k in range(F)]
     prefetch = not args.no_prefetch
     state = {"k": 0}
@@ -696,6 +818,7 @@ def run_loop(cfg, args, rank, local_rank, world, torch, V, barrier, dev, imgs, s
         if not keep:
             kf_before[0] += int(bool(i.is_keyframe))
         if keep:
+            last["info"] = i
             c = i.counts
             infos.append((k, i.n_tracks_in, c.n_l0l1, c.n_refine, c.n_replayed, i.n_new_candidates, i.n_new, i.n_final,
                           i.is_keyframe, i.lba_ran, c.gn_iterations, c.n_ba))
@@ -709,12 +832,14 @@ def run_loop(cfg, args, rank, local_rank, world, torch, V, barrier, dev, imgs, s
     K = args.steps
 
     kf_before = [0]
+    last = {}  # the frame record of the last timed step (--dump-outputs)
 
     def collect(out, keep, k0):
         for j, i in enumerate(out):
             if not keep:
                 kf_before[0] += int(bool(i.is_keyframe))
             if keep:
+                last["info"] = i
                 c = i.counts
                 infos.append((k0 + j, i.n_tracks_in, c.n_l0l1, c.n_refine, c.n_replayed, i.n_new_candidates, i.n_new, i.n_final,
                               i.is_keyframe, i.lba_ran, c.gn_iterations, c.n_ba))
@@ -731,9 +856,10 @@ def run_loop(cfg, args, rank, local_rank, world, torch, V, barrier, dev, imgs, s
         issue(0)
         for _ in range(LOOP_PRIME + args.warmup):
             step(False)
-    ctx.profile_enable(K * 4 + 64)
-    ctx.profile_set_classes(1 << 1)
-    ctx.profile_reset()
+    if args.full:  # (event brackets around the dominant kernel: the roofline's launch durations)
+        ctx.profile_enable(K * 4 + 64)
+        ctx.profile_set_classes(1 << 1)
+        ctx.profile_reset()
 
     def timed_run():
         if lib_loop:
@@ -753,23 +879,9 @@ def run_loop(cfg, args, rank, local_rank, world, torch, V, barrier, dev, imgs, s
     tot_frames, max_dt = sum(p[0] for p in per_rank), max(p[1] for p in per_rank)
     if rank != 0:
         return None, ctx
-    klt_n, klt_ms = ctx.profile_get(1)
-    launches = max(klt_n, 1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, loop_outputs(last["info"], traj, K))
     I = np.array(infos, np.int64)
-    strict = bool(args.strict_border)
-    b_req = b_spec = b_des = 0
-    for (k, n_in, n_l0l1, n_refine, n_rep, n_cand_emit, n_new, n_final, kf, lba, it, nba) in infos:
-        per = klt_bytes_per_point_level(win)
-        feat = per * (n_in + (n_refine - n_rep)) * eff_levels + IC_BYTES_8D * n_l0l1
-        cand_all = per * n_kp_bins[k] * (eff_levels + eff_levels_bwd)   # every bin's candidate is tracked (speculation)
-        cand_req = per * n_cand_emit * (eff_levels + eff_levels_bwd)     # the candidates the reference would track
-        b_req += feat + cand_req
-        b_spec += cand_all - cand_req
-        b_des += (IC_RECORD_BYTES * n_in if strict else 0) + POINT_IO_BYTES * (n_in + n_kp_bins[k])
-    achieved = ((b_req + b_spec) / launches) / (klt_ms / launches * 1e-3) / 1e9 if klt_n else 0.0
-    achieved_req = (b_req / launches) / (klt_ms / launches * 1e-3) / 1e9 if klt_n else 0.0
-    counters = stamped_counters(args.config)
-    issue = issue_roofline(counters, klt_ms, launches) if klt_n else None
     # trajectory against the renderer's ground truth (frame 0 = identity)
     T0i = np.linalg.inv(poses_gt[0])
     gt = np.stack([(T0i @ p)[:3, 3] for p in poses_gt[:len(traj)]])
@@ -829,28 +941,10 @@ def run_loop(cfg, args, rank, local_rank, world, torch, V, barrier, dev, imgs, s
             "keyframes_before_timed_region": kf_before[0], "kf_window": int(svo.prm.kf_window),
             "untimed_frames": LOOP_PRIME + args.warmup,
         },
-        "roofline": {
-            "bound": "hbm",
-            "kernel": f"frame_track_kernel<{win}>",
-            "achieved": round(achieved, 2),
-            "peak": HBM_PEAK_GBS,
-            "unit": "GB/s",
-            "frac": round(achieved / HBM_PEAK_GBS, 5),
-            "traffic": counters["traffic"],
-            "achieved_required_only": round(achieved_req, 2),
-            "frac_required_only": round(achieved_req / HBM_PEAK_GBS, 5),
-            "alg_bytes_per_launch": {"survey_8d_required": round(b_req / launches), "survey_8d_speculative": round(b_spec / launches),
-                                     "design_records": round(b_des / launches)},
-            "avg_launch_us": round(1e3 * klt_ms / launches, 2),
-            "note": "achieved = SURVEY 8(d) bytes (features + every bucket's candidate) / launch duration (HIP events, live); "
-                    "required_only leaves out the candidates the reference would not have tracked; the path is issue/latency-"
-                    "bound, the fraction is reported because the metric asks for it (DESIGN.md §6)",
-        },
-        "roofline_issue": issue,
         "per_rank_fps": [round(p[0] / p[1], 2) for p in per_rank],
     }
-    if counters["counters_note"]:
-        out["roofline"]["counters_note"] = counters["counters_note"]
+    if args.full:
+        out.update(loop_roofline(args, ctx, infos, n_kp_bins, win, eff_levels, eff_levels_bwd))
     if ctx.debug_switches:  # (VO_TEST_SWITCHES=1 only: a measurement run with a test switch on says so)
         out["config"]["debug_switches"] = dict(ctx.debug_switches)
     svo.close()
@@ -1186,7 +1280,14 @@ def main():
                          "through it anyway — the code path N > 1 takes, executed on a 1-GPU box (tests/test_bench_gpu.py)")
     ap.add_argument("--rendezvous-check", action="store_true",
                     help="run only the multi-rank control flow (gloo, no GPU work) and print its JSON line")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: roofline (a keypoint pass over every frame, "
+                         "event brackets in the timed loop), the CPU baseline with its parity check and the secondary legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the outputs, the result line
+        args.no_secondary = args.no_cpu_baseline = True
     if args.mode is None:
         args.mode = "loop"  # (config 2, mono: the MonoVO loop; --mode closed / open: the frame operator on ground-truth track sets)
     if args.steps is None:
@@ -1289,7 +1390,7 @@ def run_stereo(cfg, args, rank, local_rank, world, torch, V, barrier, dev, secon
     ctx, K = B.ctx, args.steps
     mode, host = args.mode, bool(args.host_images)
     # bins that hold a keypoint, per distinct left image: the candidates the closed frame kernel tracks (bytes accounting)
-    if mode == "closed":
+    if mode == "closed" and args.full:
         for fid in range(B.F):
             ctx.set_image_device(3, B.d_L[fid].data_ptr(), B.W, B.H, B.W)
             B.fe.resetWeightBin()
@@ -1298,16 +1399,22 @@ def run_stereo(cfg, args, rank, local_rank, world, torch, V, barrier, dev, secon
     if args.warmup:
         B.run(first, args.warmup, mode, host)
     first += args.warmup
-    ctx.profile_enable(K * 4 + 64)
-    all_classes = bool(os.environ.get("VO_BENCH_ALL_KERNELS"))  # (more event brackets: a few us per frame slower)
-    ctx.profile_set_classes(0 if all_classes else 1 << 1)  # default: event-bracket only the dominant kernel
-    ctx.profile_reset()
+    all_classes = args.full and bool(os.environ.get("VO_BENCH_ALL_KERNELS"))  # (more event brackets: a few us per frame slower)
+    if args.full:
+        ctx.profile_enable(K * 4 + 64)
+        ctx.profile_set_classes(0 if all_classes else 1 << 1)  # default: event-bracket only the dominant kernel
+        ctx.profile_reset()
     acc = {"b8d": 0, "bdes": 0}
     results, stamps = [], []
     replayed = []  # per frame: features the strict-border replay handled
+    last = {}  # the result of the last timed step (--dump-outputs)
 
     def account(step, r):
+        last["r"] = r
         cts = r["counts"]  # features finished by the replay kernel do their step [5] there
+        replayed.append(cts.n_replayed)
+        if not args.full:
+            return
         if mode == "closed":
             n_cand = B.n_bins_with_kp[B.frame_id(step + 1)]
         else:
@@ -1316,7 +1423,6 @@ def run_stereo(cfg, args, rank, local_rank, world, torch, V, barrier, dev, secon
                                   B.eff_levels_bwd, bool(args.strict_border))
         acc["b8d"] += a
         acc["bdes"] += b
-        replayed.append(cts.n_replayed)
 
     dt = timed(lambda: B.run(first, K, mode, host, results, stamps, account), barrier, ctx)
     if os.environ.get("VO_BENCH_DUMP"):  # per-frame wall time and replayed-feature count, for A/B analysis
@@ -1325,13 +1431,12 @@ def run_stereo(cfg, args, rank, local_rank, world, torch, V, barrier, dev, secon
     tot_frames, max_dt = sum(p[0] for p in per_rank), max(p[1] for p in per_rank)
     if rank != 0:
         return None, ctx
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, result_arrays(last["r"]))
 
-    klt_n, klt_ms = ctx.profile_get(1)
+    klt_n, klt_ms = ctx.profile_get(1) if args.full else (0, 0.0)
     launches = max(klt_n, 1)
     achieved = (acc["b8d"] / launches) / (klt_ms / launches * 1e-3) / 1e9 if klt_n else 0.0
-    # (counter passes of THIS workload on the present kernel sources, or nothing: profiles/r03[_cfgN]_closed_*.json)
-    counters = stamped_counters(args.config, "closed") if mode == "closed" else stamped_counters(0, "none")
-    traffic = counters["traffic"]
     step10 = {"closed": "closed on the device: per-bucket best keypoints detected from the image alone on the side stream, "
                         "every bucket's candidate tracked inside the frame kernel, updateWeightBin + emission behind the BA",
               "sequential": "three host-driven operator calls after the frame's result",
@@ -1365,24 +1470,27 @@ def run_stereo(cfg, args, rank, local_rank, world, torch, V, barrier, dev, secon
             "untriangulated_fraction": UNTRIANGULATED,
             "distinct_frames": B.F,
         },
-        "roofline": {
+        "per_rank_fps": [round(p[0] / p[1], 2) for p in per_rank],
+    }
+    if args.full:
+        # (counter passes of THIS workload on the present kernel sources, or nothing: profiles/r03[_cfgN]_closed_*.json)
+        counters = stamped_counters(args.config, "closed") if mode == "closed" else stamped_counters(0, "none")
+        out["roofline"] = {
             "bound": "hbm",
             "kernel": f"frame_track_kernel<{B.win}>",
             "achieved": round(achieved, 2),
             "peak": HBM_PEAK_GBS,
             "unit": "GB/s",
             "frac": round(achieved / HBM_PEAK_GBS, 5),
-            "traffic": traffic,
+            "traffic": counters["traffic"],
             "alg_bytes_per_launch": {"survey_8d": round(acc["b8d"] / launches), "design_records": round(acc["bdes"] / launches)},
             "avg_launch_us": round(1e3 * klt_ms / launches, 2),
             "note": "achieved = survey_8d bytes / launch duration (HIP events, live); the path is issue/latency-bound, "
                     "the fraction is reported because the metric asks for it (DESIGN.md §6)",
-        },
-        "roofline_issue": issue_roofline(counters, klt_ms, launches) if klt_n else None,
-        "per_rank_fps": [round(p[0] / p[1], 2) for p in per_rank],
-    }
-    if counters.get("counters_note"):
-        out["roofline"]["counters_note"] = counters["counters_note"]
+        }
+        out["roofline_issue"] = issue_roofline(counters, klt_ms, launches) if klt_n else None
+        if counters.get("counters_note"):
+            out["roofline"]["counters_note"] = counters["counters_note"]
     if all_classes:
         names = {0: "pyramid", 1: "frame_track", 2: "ic_replay", 3: "gn_pose", 4: "hamming", 5: "aux"}
         out["kernels"] = {}
@@ -1526,17 +1634,19 @@ def run_mono_loop(cfg, args, rank, local_rank, world, torch, V, barrier, dev, im
     mvo = V.MonoVO(ctx, W, H, cfg["K"], cfg["n_u"], cfg["n_v"], hook, **kw)
     eff_levels = ctx.pyramid_levels(W, H, win, lvl) + 1
     eff_levels_bwd = ctx.pyramid_levels(W, H, win, lvl - 1) + 1
-    fe = V.FeatureExtractor(ctx)
-    fe.initParams(W, H, cfg["n_u"], cfg["n_v"], THRES_FAST=cfg["thres_fast"])
     n_kp_bins = []
-    for k in range(F):
-        ctx.set_image_device(2, d_I[k].data_ptr(), W, H, W)
-        n_kp_bins.append(bins_with_keypoints(fe, 2))
-    ctx.synchronize()
+    if args.full:  # (bytes accounting of the roofline)
+        fe = V.FeatureExtractor(ctx)
+        fe.initParams(W, H, cfg["n_u"], cfg["n_v"], THRES_FAST=cfg["thres_fast"])
+        for k in range(F):
+            ctx.set_image_device(2, d_I[k].data_ptr(), W, H, W)
+            n_kp_bins.append(bins_with_keypoints(fe, 2))
+        ctx.synchronize()
     ptr = [np.ascontiguousarray(I) for I in mono] if args.host_images else [(d_I[k].data_ptr(), W) for k in range(F)]
     prefetch = not args.no_prefetch
     state = {"k": 0}
     traj, infos, stamps = [], [], []
+    last = {}  # the frame record of the last timed step (--dump-outputs)
 
     def issue(k):
         hook.k = k
@@ -1556,6 +1666,7 @@ def run_mono_loop(cfg, args, rank, local_rank, world, torch, V, barrier, dev, im
         if not keep:
             kf_before[0] += int(bool(i.is_keyframe))
         if keep:
+            last["info"] = i
             c = i.counts
             infos.append((k, i.n_tracks_in, c.n_klt, c.n_refine, c.n_replayed, i.n_new, i.n_final, i.is_keyframe, i.lba_ran,
                           c.gn_iterations, c.n_ba, i.used_five_point))
@@ -1578,6 +1689,7 @@ def run_mono_loop(cfg, args, rank, local_rank, world, torch, V, barrier, dev, im
             if not keep:
                 kf_before[0] += int(bool(i.is_keyframe))
             if keep:
+                last["info"] = i
                 c = i.counts
                 infos.append((k0 + j, i.n_tracks_in, c.n_klt, c.n_refine, c.n_replayed, i.n_new, i.n_final, i.is_keyframe, i.lba_ran,
                               c.gn_iterations, c.n_ba, i.used_five_point))
@@ -1591,9 +1703,10 @@ def run_mono_loop(cfg, args, rank, local_rank, world, torch, V, barrier, dev, im
     else:
         for _ in range(args.warmup):
             step(False)
-    ctx.profile_enable(K * 4 + 64)
-    ctx.profile_set_classes(1 << 1)
-    ctx.profile_reset()
+    if args.full:
+        ctx.profile_enable(K * 4 + 64)
+        ctx.profile_set_classes(1 << 1)
+        ctx.profile_reset()
     dt = timed((lambda: lib_frames(K, True)) if lib_loop else (lambda: [step(True) for _ in range(K)]), barrier, ctx)
     if state["k"] < F:
         hook.k = state["k"]
@@ -1602,17 +1715,9 @@ def run_mono_loop(cfg, args, rank, local_rank, world, torch, V, barrier, dev, im
     tot_frames, max_dt = sum(p[0] for p in per_rank), max(p[1] for p in per_rank)
     if rank != 0:
         return None, ctx
-    klt_n, klt_ms = ctx.profile_get(1)
-    launches = max(klt_n, 1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, loop_outputs(last["info"], traj, K))
     I = np.array(infos, np.int64)
-    b8d = bdes = 0
-    for row in I:
-        k, n_in, n_klt = int(row[0]), int(row[1]), int(row[2])
-        n_cand = n_kp_bins[k]
-        b8d += klt_bytes_per_point_level(win) * (2 * n_in * eff_levels + n_cand * (eff_levels + eff_levels_bwd)) + IC_BYTES_8D * n_klt
-        bdes += (IC_RECORD_BYTES * n_in if args.strict_border else 0) + POINT_IO_BYTES * (n_in + n_cand)
-    achieved = (b8d / launches) / (klt_ms / launches * 1e-3) / 1e9 if klt_n else 0.0
-    counters = stamped_counters(args.config, "loop", "mono_track")
     # trajectory against the renderer's ground truth, up to the scale the initialisation fixes (|t| of the first motion = 1)
     T0i = np.linalg.inv(poses_gt[0])
     gt = np.stack([(T0i @ p)[:3, 3] for p in poses_gt[:len(traj)]])
@@ -1643,17 +1748,28 @@ def run_mono_loop(cfg, args, rank, local_rank, world, torch, V, barrier, dev, im
                  "five_point_calls": int(hook.calls), "keyframes_before_timed_region": kf_before[0],
                  "untimed_frames": LOOP_PRIME + args.warmup,
                  "end_point_error_scaled": round(float(np.linalg.norm(est[-1] * sc - gt[-1])), 4), "path_m": round(float(np.linalg.norm(gt[-1])), 1)},
-        "roofline": {"bound": "hbm", "kernel": f"mono_track_kernel<{win}>", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": counters["traffic"],
-                     "alg_bytes_per_launch": {"survey_8d": round(b8d / launches), "design_records": round(bdes / launches)},
-                     "avg_launch_us": round(1e3 * klt_ms / launches, 2),
-                     "note": "algorithmic bytes per SURVEY 8(d): forward + backward PyrLK of every feature, every bin's candidate forward + "
-                             "backward (speculative), IC tiles; the path is issue/latency-bound at these sizes"},
-        "roofline_issue": issue_roofline(counters, klt_ms, launches),
         "per_rank_fps": [round(p[0] / p[1], 2) for p in per_rank],
     }
-    if counters["counters_note"]:
-        out["roofline"]["counters_note"] = counters["counters_note"]
+    if args.full:
+        klt_n, klt_ms = ctx.profile_get(1)
+        launches = max(klt_n, 1)
+        b8d = bdes = 0
+        for row in I:
+            k, n_in, n_klt = int(row[0]), int(row[1]), int(row[2])
+            n_cand = n_kp_bins[k]
+            b8d += klt_bytes_per_point_level(win) * (2 * n_in * eff_levels + n_cand * (eff_levels + eff_levels_bwd)) + IC_BYTES_8D * n_klt
+            bdes += (IC_RECORD_BYTES * n_in if args.strict_border else 0) + POINT_IO_BYTES * (n_in + n_cand)
+        achieved = (b8d / launches) / (klt_ms / launches * 1e-3) / 1e9 if klt_n else 0.0
+        counters = stamped_counters(args.config, "loop", "mono_track")
+        out["roofline"] = {"bound": "hbm", "kernel": f"mono_track_kernel<{win}>", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                           "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": counters["traffic"],
+                           "alg_bytes_per_launch": {"survey_8d": round(b8d / launches), "design_records": round(bdes / launches)},
+                           "avg_launch_us": round(1e3 * klt_ms / launches, 2),
+                           "note": "algorithmic bytes per SURVEY 8(d): forward + backward PyrLK of every feature, every bin's candidate forward + "
+                                   "backward (speculative), IC tiles; the path is issue/latency-bound at these sizes"}
+        out["roofline_issue"] = issue_roofline(counters, klt_ms, launches)
+        if counters["counters_note"]:
+            out["roofline"]["counters_note"] = counters["counters_note"]
     if ctx.debug_switches:
         out["config"]["debug_switches"] = dict(ctx.debug_switches)
     mvo.close()
@@ -1732,7 +1848,7 @@ def run_mono(cfg, args, rank, local_rank, world, torch, V, barrier, dev):
     fe.initParams(W_, H_, cfg["n_u"], cfg["n_v"], THRES_FAST=cfg["thres_fast"])
     bins = fe.binParams()
     n_bins_with_kp = {}
-    if closed:
+    if closed and args.full:  # (bytes accounting of the roofline)
         for f_ in range(F):
             ctx.set_image_device(2, d_I[f_].data_ptr(), W_, H_, W_)
             fe.resetWeightBin()
@@ -1775,13 +1891,18 @@ def run_mono(cfg, args, rank, local_rank, world, torch, V, barrier, dev):
     run(0, 4)
     run(4, args.warmup)
     K = args.steps
-    ctx.profile_enable(K * 4 + 64)
-    ctx.profile_set_classes(1 << 1)
-    ctx.profile_reset()
+    if args.full:
+        ctx.profile_enable(K * 4 + 64)
+        ctx.profile_set_classes(1 << 1)
+        ctx.profile_reset()
     kept, stamps = [], []
     acc = {"b8d": 0, "bdes": 0}
+    last = {}  # the result of the last timed step (--dump-outputs)
 
     def account(s, r):
+        last["r"] = r
+        if not args.full:
+            return
         c = r["counts"]  # forward + backward PyrLK at full depth for every feature, IC for the tracked ones
         n_cand = n_bins_with_kp[fid(s + 1)] if closed else 0  # + forward / backward (maxLevel - 1) for every bin's candidate
         acc["b8d"] += klt_bytes_per_point_level(WIN) * (2 * n_pts * eff_levels + n_cand * (eff_levels + eff_levels_bwd)) \
@@ -1794,7 +1915,9 @@ def run_mono(cfg, args, rank, local_rank, world, torch, V, barrier, dev):
     tot_frames, max_dt = sum(p[0] for p in per_rank), max(p[1] for p in per_rank)
     if rank != 0:
         return None, ctx
-    nl, ms = ctx.profile_get(1)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, result_arrays(last["r"]))
+    nl, ms = ctx.profile_get(1) if args.full else (0, 0.0)
     launches = max(nl, 1)
     achieved = (acc["b8d"] / launches) / (ms / launches * 1e-3) / 1e9 if nl else 0.0
     out = {
@@ -1811,12 +1934,13 @@ def run_mono(cfg, args, rank, local_rank, world, torch, V, barrier, dev):
                                   "trackBidirection) closed on the device" if closed else "; the new-point step is not part of it")
                                + "; result read back every frame; the 5-point fallback is the caller's",
                    "images": "resident in HBM", "strict_border": int(args.strict_border), "distinct_frames": F},
-        "roofline": {"bound": "hbm", "kernel": f"mono_track_kernel<{WIN}>", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
-                     "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None,
-                     "alg_bytes_per_launch": {"survey_8d": round(acc["b8d"] / launches), "design_records": round(acc["bdes"] / launches)},
-                     "avg_launch_us": round(1e3 * ms / launches, 2)},
         "per_rank_fps": [round(p[0] / p[1], 2) for p in per_rank],
     }
+    if args.full:
+        out["roofline"] = {"bound": "hbm", "kernel": f"mono_track_kernel<{WIN}>", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS,
+                           "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": None,
+                           "alg_bytes_per_launch": {"survey_8d": round(acc["b8d"] / launches), "design_records": round(acc["bdes"] / launches)},
+                           "avg_launch_us": round(1e3 * ms / launches, 2)}
     if world == 1 and not args.no_cpu_baseline and kept:
         from oracle import oracle as O
         prm_o = O.make_mono_params(*args_p)

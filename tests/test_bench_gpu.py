@@ -1,10 +1,12 @@
-"""bench.py end to end on one GPU, shortened: the JSON line carries what the contract asks for (metric / value / roofline /
-cpu_baseline / parity / secondary legs) and its own parity checks hold."""
+"""bench.py end to end on one GPU, shortened: with --full the JSON line carries what the contract asks for (metric / value /
+roofline / cpu_baseline / parity / secondary legs) and its own parity checks hold; a plain run carries the headline alone and
+computes what --full computes."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -13,7 +15,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_default_bench_line_shortened():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "40", "--warmup", "5", "--cpu-frames", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "40", "--warmup", "5", "--cpu-frames", "2",
                         "--parity-frames", "13", "--streams-per-gpu", "2", "--batch-frames", "14"],
                        capture_output=True, text=True, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
@@ -42,7 +44,7 @@ def test_default_bench_line_shortened():
                                    ["--config", "2", "--steps", "2", "--warmup", "0"], ["--mode", "closed", "--steps", "2", "--warmup", "0"]])
 def test_bench_with_very_few_steps(flags):
     """Whatever K and W the caller picks: one JSON line (a warm-up of zero frames once left a frame in flight)."""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--cpu-frames", "2", "--parity-frames", "4", "--streams-per-gpu", ""] + flags,
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--cpu-frames", "2", "--parity-frames", "4", "--streams-per-gpu", ""] + flags,
                        capture_output=True, text=True, timeout=1200, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -68,3 +70,34 @@ def test_rccl_process_group_and_gather_with_one_rank():
     d = json.loads(lines[0])
     assert d["collective"] == "nccl" and d["n_gpus"] == 1 and len(d["per_rank_fps"]) == 1
     assert abs(d["per_rank_fps"][0] - d["value"]) <= 0.02 * d["value"]
+
+
+def _bench_line(args, cwd):
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args, capture_output=True, text=True, timeout=900, cwd=cwd)
+    assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+@pytest.mark.parametrize("flags", [[], ["--config", "2"], ["--mode", "closed"], ["--config", "2", "--mode", "closed"]])
+def test_plain_run_dumps_what_the_full_run_computes(tmp_path, flags):
+    """A plain run (no --full) prints the headline fields without the roofline, baseline or secondary legs; its
+    --dump-outputs files are float32 / float64 and equal, bit for bit, what a --full run of the same arguments dumps."""
+    common = ["--gpus", "1", "--steps", "6", "--warmup", "2"] + flags
+    plain = _bench_line(common + ["--dump-outputs", str(tmp_path / "plain")], ROOT)
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain, k
+    assert plain["steps"] == 6 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert not {"roofline", "roofline_issue", "cpu_baseline", "parity", "secondary"} & set(plain)
+    full = _bench_line(common + ["--full", "--no-secondary", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / "full")], ROOT)
+    assert "roofline" in full and full["steps"] == 6
+    names = sorted(os.listdir(tmp_path / "plain"))
+    assert names and names == sorted(os.listdir(tmp_path / "full"))
+    total = 0
+    for n in names:
+        a, b = np.load(tmp_path / "plain" / n), np.load(tmp_path / "full" / n)
+        assert a.dtype in (np.float32, np.float64) and a.dtype == b.dtype and a.shape == b.shape, n
+        assert np.array_equal(a.view(np.uint8), b.view(np.uint8)), n
+        total += a.nbytes
+    assert total <= 64 << 20

@@ -1,6 +1,6 @@
 """The reference's YAML configuration files (OpenCV FileStorage dialect) through visual_odometry_ros_amd.config: a file
-written here with the reference's keys (the numbers of config/stereo/kitti_00_stereo.yaml), and — where the reference
-tree is on disk — every file under config/stereo."""
+written here with the reference's keys (the numbers of config/stereo/kitti_00_stereo.yaml), and every file of the
+reference's config/stereo (copies under tests/golden/reference_config/stereo/)."""
 import glob
 import os
 
@@ -8,6 +8,9 @@ import numpy as np
 import pytest
 
 from visual_odometry_ros_amd import config
+
+# the reference's own stereo configuration files (settings only), kept as fixtures
+REFERENCE_STEREO_YAML = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_config", "stereo")
 
 KITTI_LIKE = """%YAML:1.0
 # Camera Parameters
@@ -87,10 +90,9 @@ def test_distortion_order_and_missing_keys():
     assert c["feature_tracker"]["max_level"] == 0  # a missing FileNode converts to 0 in the reference
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/config/stereo"), reason="the reference tree is not on this machine")
 def test_every_stereo_config_of_the_reference_parses():
-    files = sorted(glob.glob("/root/reference/config/stereo/*.yaml"))
-    assert files
+    files = sorted(glob.glob(os.path.join(REFERENCE_STEREO_YAML, "*.yaml")))
+    assert len(files) == 14
     for f in files:
         c = config.load_stereo_config(f)
         assert c["camera"]["left"]["width"] > 0 and c["T_lr"].shape == (4, 4), f
@@ -143,8 +145,7 @@ def test_cpp_reader_agrees_with_the_python_reader(tmp_path):
     open(files[1], "w").write(KITTI_LIKE.replace("flagDoUndistortion: 0", "flagDoUndistortion: 1").replace("Camera.right.k1: 0.0", "Camera.right.k1: -0.31")
                               .replace("data: [1,0,0,0.5371657189, 0,1,0,0, 0,0,1,0, 0,0,0,1]",
                                        "data: [ 0.9999, 0.01, 0., 0.12,\n     -0.01, 0.9999, 0., 0.001,\n     0., 0., 1., -0.002, 0., 0., 0., 1. ]"))
-    if os.path.isdir("/root/reference/config/stereo"):
-        files += sorted(glob.glob("/root/reference/config/stereo/*.yaml"))
+    files += sorted(glob.glob(os.path.join(REFERENCE_STEREO_YAML, "*.yaml")))
     for f in files:
         rc, got = _cpp_read(exe, f)
         assert rc == 0, (f, got)

@@ -1,5 +1,5 @@
 // TYPE-CHECK STAND-IN for the reference's core/defines/define_type.h (aliases of :15-64 that the adapter uses;
-// see tests/typecheck_stubs/README.md). Where /root/reference exists the real file is checked as well.
+// see tests/typecheck_stubs/README.md).
 #ifndef VO_TYPECHECK_STUB_DEFINE_TYPE_
 #define VO_TYPECHECK_STUB_DEFINE_TYPE_
 #include <memory>

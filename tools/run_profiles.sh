@@ -14,7 +14,7 @@ NAME=${NAME:-default}
 OUT=$ROOT/gpurun_out/$RND
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-secondary $*"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-secondary $*"
 if [ "$WHAT" = stats ]; then
   timeout 900 $B > $OUT/${NAME}_prerender.log 2>&1
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_$NAME -o bench -- $B > $OUT/${NAME}_stats.log 2>&1

@@ -19,7 +19,7 @@ if [ "$FIRST" = batch ]; then
   exit 0
 fi
 rm -rf $OUT; mkdir -p $OUT
-B="python3 $ROOT/bench.py --no-cpu-baseline --no-secondary $*"
+B="python3 $ROOT/bench.py --full --no-cpu-baseline --no-secondary $*"
 timeout 600 $B > $OUT/prerender.log 2>&1
 timeout 300 rocprofv3 --kernel-trace --output-format csv -d $OUT -o tr -- $B > $OUT/log.txt 2>&1
 f=$(ls $OUT/*kernel_trace.csv $OUT/*/*kernel_trace.csv 2>/dev/null | tail -1)

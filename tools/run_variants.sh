@@ -5,7 +5,7 @@ ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 OUT=$ROOT/gpurun_out/variants
 mkdir -p $OUT
 cd $ROOT
-B="python3 bench.py --no-cpu-baseline --no-secondary --steps ${STEPS:-200}"
+B="python3 bench.py --full --no-cpu-baseline --no-secondary --steps ${STEPS:-200}"
 i=0
 for F in "$@"; do
   i=$((i+1))

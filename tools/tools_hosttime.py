@@ -14,7 +14,7 @@ def wrap(cls, name):
 for n in ("enqueue_closed_device", "result"): wrap(api.StereoFramePipeline, n)
 for n in ("set_stereo_pair_device",): wrap(api.Context, n)
 for n in ("enqueueCandidates",): wrap(api.FeatureExtractor, n)
-sys.argv = ["bench.py", "--no-cpu-baseline", "--no-secondary", "--strict-border", os.environ.get("STRICT", "1"), "--steps", "400"]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--no-secondary", "--strict-border", os.environ.get("STRICT", "1"), "--steps", "400"]
 t0 = time.perf_counter()
 try:
     runpy.run_path("bench.py", run_name="__main__")

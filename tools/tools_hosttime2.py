@@ -19,5 +19,5 @@ def g(self, *a, **k):
 api.StereoFramePipeline.enqueue_device = g
 import runpy, gc
 if os.environ.get('NOGC'): gc.disable()
-sys.argv = ["bench.py", "--no-cpu-baseline", "--strict-border", "0", "--steps", "400", "--warmup", "5"]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--strict-border", "0", "--steps", "400", "--warmup", "5"]
 runpy.run_path("bench.py", run_name="__main__")
