@@ -38,6 +38,8 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--strict-border", type=int, default=4, help="see vo_stereo_frame_set_strict_border (0: masked border taps)")
     ap.add_argument("--no-local-ba", action="store_true")
+    ap.add_argument("--sum-order", choices=("tree", "reference"), default="tree",
+                    help="see vo_set_sum_order (reference: the reference's summation order, bit-exact against it; slower)")
     args = ap.parse_args()
     import visual_odometry_ros_amd as V
     names_l, names_r = sorted(os.listdir(args.left)), sorted(os.listdir(args.right))
@@ -47,6 +49,7 @@ def main():
     if n == 0:
         raise SystemExit("no image pairs found")
     svo = V.StereoVO.from_yaml(args.config, device=args.device, strict_border=args.strict_border, local_ba=not args.no_local_ba)
+    svo.ctx.sum_order = args.sum_order
     pair = lambda k: (load_grey(os.path.join(args.left, names_l[k])), load_grey(os.path.join(args.right, names_r[k])))  # noqa: E731
     ids, poses, n_kf = [], [], 0
     cur = pair(0)

@@ -89,6 +89,24 @@ const char *vo_last_error(const vo_ctx *ctx);
 void *vo_stream(vo_ctx *ctx);
 int vo_synchronize(vo_ctx *ctx);
 
+/* Summation order of the float reductions of the IC refinement (trackWithScale: A11, A12, A22, b1, b2 and the squared
+ * error over the 264 taps) and of the pose-only Gauss-Newton (the 21 + 6 entries of JtWJ / mJtWr and the error).
+ * VO_SUM_ORDER_TREE (the default): per-lane or per-thread partials and a balanced tree. Exact against the oracle's
+ * VO_SUM_TREE, and the fast form.
+ * VO_SUM_ORDER_REFERENCE: every such sum adds its terms one after the other in the reference's order (taps in index
+ * order, feature_tracker.cpp:426-458; points in order and, within a point, rows in order, motion_estimator.cpp:713-810,
+ * :920-1040). The device then equals the oracle's VO_SUM_SEQ bit for bit, per operator and over free-running loops,
+ * so its track ids and poses follow the reference's own float arithmetic. Cost: the sums become chains of dependent
+ * adds — about 4 N adds per GN iteration for N stereo points — so a frame is several times slower (README has the
+ * measured frames/s). Meant for validation runs.
+ * It applies to every entry that runs IC or GN on this context: vo_track_with_scale, vo_gn_pose_mono /_stereo, the
+ * stereo and mono frame operators (the _closed forms included), vo_svo_* and vo_mvo_*. The order is read when work is
+ * enqueued: a change between two frames of a running stream takes effect at the next frame's enqueue. vo_batch
+ * streams stay in tree order. Any other value returns VO_ERR_INVALID and changes nothing. */
+enum { VO_SUM_ORDER_TREE = 0, VO_SUM_ORDER_REFERENCE = 1 };
+int vo_set_sum_order(vo_ctx *ctx, int order);
+int vo_get_sum_order(const vo_ctx *ctx); /* VO_SUM_ORDER_*, or VO_ERR_INVALID for a NULL context */
+
 /* ---- images & pyramids ---------------------------------------------------
  * Replaces what cv::calcOpticalFlowPyrLK does internally on every call
  * (buildOpticalFlowPyramid: pyrDown 5-tap, REFLECT_101 borders; reference call
@@ -490,6 +508,7 @@ int vo_triangulate_dlt(vo_ctx *ctx, const float *pts0, const float *pts1, int n,
  * last_ids [n_streams][ids_cap] + n_ids [n_streams] (every stream's final track-set ids), seconds [n_streams] (timed
  * wall time per stream), *wall (first start to last end). */
 typedef struct vo_batch vo_batch;
+/* (The batch's streams run in tree summation order: vo_set_sum_order does not reach them.) */
 int vo_batch_create(const vo_config *cfg, const vo_svo_params *prm, int n_streams, vo_batch **out);
 void vo_batch_destroy(vo_batch *batch);
 const char *vo_batch_last_error(const vo_batch *batch);

@@ -126,6 +126,7 @@ SYMBOLS = [
     "vo_mvo_keyframe_count", "vo_mvo_get_keyframes",
     "vo_batch_last_error", "vo_batch_run", "vo_debug_set", "vo_batch_debug_set", "vo_batch_strict_border", "vo_debug_allocation_count", "vo_svo_device_bytes",
     "vo_se3_exp", "vo_ids_reset", "vo_ids_peek", "vo_ids_new_frames", "vo_ids_new_landmarks", "vo_compact_tracks",
+    "vo_set_sum_order", "vo_get_sum_order",
 ]
 
 _lib = None
@@ -192,6 +193,8 @@ def load():
     lib.vo_batch_debug_set.argtypes = [vp, ci, ci]
     lib.vo_batch_strict_border.argtypes = [vp]
     lib.vo_debug_allocation_count.argtypes = [vp, vp]
+    lib.vo_set_sum_order.argtypes = [vp, ci]
+    lib.vo_get_sum_order.argtypes = [vp]
     lib.vo_triangulate_dlt.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp]
     lib.vo_batch_create.argtypes = [C.POINTER(VoConfig), C.POINTER(SvoParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_batch_destroy.argtypes = [vp]

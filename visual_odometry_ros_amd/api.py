@@ -38,8 +38,12 @@ def _p(a, t=C.c_float):
 class Context:
     """Owns one vo_ctx: a HIP stream, image-pyramid slots and point buffers."""
 
+    SUM_ORDERS = {"tree": 0, "reference": 1}  # include/vo_hip.h: VO_SUM_ORDER_TREE / VO_SUM_ORDER_REFERENCE
+
     def __init__(self, device=0, max_width=1241, max_height=376, max_points=4096, n_slots=4,
-                 max_level=6):
+                 max_level=6, sum_order="tree"):
+        if sum_order not in self.SUM_ORDERS:
+            raise ValueError(f"sum_order must be one of {sorted(self.SUM_ORDERS)}, not {sum_order!r}")
         self.lib = _capi.load()
         self._h = C.c_void_p()
         cfg = VoConfig(device, max_width, max_height, max_points, n_slots, max_level)
@@ -51,6 +55,7 @@ class Context:
                 self._h = C.c_void_p()
             raise VoError(rc, msg)
         self.cfg = cfg
+        self.sum_order = sum_order
         self._children = weakref.WeakSet()  # objects that hold device state of this context (StereoVO): closed before it
         # test / measurement switches (include/vo_hip.h: vo_debug_set). Neither the library nor this mirror reads them from
         # the environment in normal use: only a process started with VO_TEST_SWITCHES=1 (the test-suite's child processes,
@@ -66,6 +71,21 @@ class Context:
                     self.debug_switches[name] = v
 
     DBG_FAIL_JOIN, DBG_CONC_GRID, DBG_SBA_LDS_SOLVE, DBG_SKIP_DETECT, OPT_POLL_YIELD, DBG_MVO_HOST_ADVANCE, DBG_STAGED_DETECT = 0, 1, 2, 3, 4, 5, 6
+
+    @property
+    def sum_order(self):
+        """Summation order of the IC and GN reductions on this context: "tree" (the default) or "reference" (the
+        reference's sequential order; bit-exact against the oracle's SUM_SEQ, slower). Every operator, frame class,
+        StereoVO and MonoVO of the context follows it; a change takes effect at the next call or enqueue."""
+        order = self.lib.vo_get_sum_order(self._h)
+        self.check(order)
+        return {v: k for k, v in self.SUM_ORDERS.items()}[order]
+
+    @sum_order.setter
+    def sum_order(self, order):
+        if order not in self.SUM_ORDERS:
+            raise ValueError(f"sum_order must be one of {sorted(self.SUM_ORDERS)}, not {order!r}")
+        self.check(self.lib.vo_set_sum_order(self._h, self.SUM_ORDERS[order]))
 
     def debug_set(self, key, value):
         self.check(self.lib.vo_debug_set(self._h, int(key), int(value)))

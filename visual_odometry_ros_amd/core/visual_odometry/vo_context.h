@@ -31,6 +31,10 @@ class Context {
   Context &operator=(const Context &) = delete;
   vo_ctx *get() const { return ctx_; }
   int n_slots() const { return n_slots_; }
+  // summation order of the IC and GN reductions (vo_set_sum_order): VO_SUM_ORDER_TREE (the default) or
+  // VO_SUM_ORDER_REFERENCE; every class that shares this context follows it from its next call or frame
+  void setSumOrder(int order) { check(vo_set_sum_order(ctx_, order)); }
+  int sumOrder() const { return check(vo_get_sum_order(ctx_)); }
   // maps the reference's throw sites / return-false onto the C status codes
   int check(int rc) const {
     if (rc < 0) throw std::runtime_error(vo_last_error(ctx_));

@@ -116,7 +116,8 @@ __device__ __forceinline__ void frame_tail(const FrameArgs &a, int i, int ok, fl
 #ifndef FRAME_WAVES_PER_EU
 #define FRAME_WAVES_PER_EU 2
 #endif
-template <int WIN>
+// ORD (all three kernels): the IC sums in the reference's order (vo_set_sum_order), not the tree
+template <int WIN, bool ORD>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FRAME_WAVES_PER_EU, FRAME_WAVES_PER_EU))) void frame_track_kernel(FrameArgs a) {
   __shared__ FrameShared<WIN> sh;
   if ((int)blockIdx.x + a.wg_off >= a.n + a.n_new) return;
@@ -302,7 +303,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FRAME_WAVES_
     rf.err_flag = 0;
     if (valid1) {
       // ---- [4-1] refinement of the left pixel (pass 1: taps outside the image are masked) ----
-      rf = ic_point<false>(a.L0[0], a.L1[0], tp, l0x, l0y, k.x, k.y, scale, lane, sh.ic, S, touched, lpx, lpy, n_iter);
+      rf = ic_point<false, ORD>(a.L0[0], a.L1[0], tp, l0x, l0y, k.x, k.y, scale, lane, sh.ic, S, touched, lpx, lpy, n_iter);
       cls = rf.cls;
     }
     FSTAMP(2)
@@ -382,7 +383,7 @@ __global__ __launch_bounds__(64) void frame_gate_kernel(IcArgs a) {
 // replay wavefront and a frame-kernel wavefront share a SIMD. With more (294 were used when unconstrained) a resident
 // replay wavefront keeps the whole SIMD to itself — the concurrent pool then costs the frame kernel a quarter of the
 // chip, or, started behind it, finds no room until SIMDs drain completely.
-template <int WIN>
+template <int WIN, bool ORD>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(IC_REPLAY_VGPRS))) void frame_replay_kernel(FrameArgs a) {
   __shared__ IcReplayShared rs;
   __shared__ uint32_t s_tt[KltCfg<WIN>::TT_H * KltCfg<WIN>::TT_WD];
@@ -402,13 +403,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(IC_REPLAY_VGPRS)
                       ic_ldf(&a.pr_prior[2 * i + 1]), s_tt, s_tj, lane);
       __builtin_amdgcn_s_setprio(3);
     };
-    (void)ic_replay<true>(a.ic, rs, lane, tail);
+    (void)ic_replay<true, ORD>(a.ic, rs, lane, tail);
   } else {
     auto tail = [&](int i, const IcResult &r) {
       frame_tail<WIN>(a, i, r.ok, r.x, r.y, a.k1[2 * i], a.k1[2 * i + 1], a.pr_prior[2 * i], a.pr_prior[2 * i + 1], s_tt,
                       s_tj, lane);
     };
-    (void)ic_replay(a.ic, rs, lane, tail);
+    (void)ic_replay<false, ORD>(a.ic, rs, lane, tail);
   }
 #ifdef IC_STAMP
   if (lane == 0) atomicMax(&a.ic.tlist[IC_DBG_OFF + 2], (int)(__builtin_amdgcn_s_memrealtime() & 0x7fffffff));
@@ -417,7 +418,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_num_vgpr(IC_REPLAY_VGPRS)
 
 // sequential fallback of the replay (returns at once unless it was requested): one wavefront walks a
 // run of features, and step [5] follows each touched feature it recomputes
-template <int WIN>
+template <int WIN, bool ORD>
 __global__ __launch_bounds__(64) void frame_fallback_kernel(FrameArgs a) {
   __shared__ IcShared sh;
   __shared__ uint32_t s_tt[KltCfg<WIN>::TT_H * KltCfg<WIN>::TT_WD];
@@ -448,7 +449,7 @@ __global__ __launch_bounds__(64) void frame_fallback_kernel(FrameArgs a) {
     };
     for (int i = blockIdx.x; i < a.n; i += gridDim.x) {
       __syncthreads();
-      ic_strict_run(a.ic, sh, i, a.n, lane, tail);
+      ic_strict_run<ORD>(a.ic, sh, i, a.n, lane, tail);
     }
   }
   // This kernel is stream-ordered behind the replay: when all of its workgroups have counted, every touched feature
@@ -475,12 +476,12 @@ extern "C" int vo_debug_frame_stamps(vo_ctx *c, int *dst, int rows) {
 static int vo_frame_fallback_grid(int n) { return n < 128 ? n : 128; }
 // phase 0: the per-feature kernel; phase 1: the strict-border replay (nothing otherwise). Two phases so that
 // the caller can feed other streams while the long first kernel is already running.
-template <int WIN>
+template <int WIN, bool ORD>
 static void frame_launch(vo_ctx *c, const FrameArgs &a, int phase, int p1_target, int done_target, int conc_grid, int split_cands,
                          int *cand_done) {
   if (phase == 0) {
     vo_prof_begin(c, VO_K_KLT);
-    hipLaunchKernelGGL(frame_track_kernel<WIN>, dim3(split_cands ? a.n : a.n + a.n_new), dim3(64), 0, c->stream, a);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(frame_track_kernel<WIN, ORD>), dim3(split_cands ? a.n : a.n + a.n_new), dim3(64), 0, c->stream, a);
     vo_prof_end(c);
     return;
   }
@@ -489,17 +490,17 @@ static void frame_launch(vo_ctx *c, const FrameArgs &a, int phase, int p1_target
       FrameArgs b = a;
       b.wg_off = a.n;
       b.cand_done = cand_done;
-      hipLaunchKernelGGL(frame_track_kernel<WIN>, dim3(a.n_new), dim3(64), 0, c->stream, b);
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(frame_track_kernel<WIN, ORD>), dim3(a.n_new), dim3(64), 0, c->stream, b);
     }
     return;
   }
   if (a.strict == 2) {  // validation mode: the sequential fallback does all the work, on the main stream
     (void)hipMemsetAsync(&a.ic.jac[IC_JAC_OVF], 1, sizeof(int), c->stream);
-    hipLaunchKernelGGL(frame_fallback_kernel<WIN>, dim3(a.n < 1024 ? a.n : 1024), dim3(64), 0, c->stream, a);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(frame_fallback_kernel<WIN, ORD>), dim3(a.n < 1024 ? a.n : 1024), dim3(64), 0, c->stream, a);
   } else if (a.strict == 1) {  // the replay stream-ordered behind the frame kernel
     vo_prof_begin(c, VO_K_IC);
-    hipLaunchKernelGGL(frame_replay_kernel<WIN>, dim3(a.n < IC_JGRID ? a.n : IC_JGRID), dim3(64), 0, c->stream, a);
-    hipLaunchKernelGGL(frame_fallback_kernel<WIN>, dim3(vo_frame_fallback_grid(a.n)), dim3(64), 0, c->stream, a);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(frame_replay_kernel<WIN, ORD>), dim3(a.n < IC_JGRID ? a.n : IC_JGRID), dim3(64), 0, c->stream, a);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(frame_fallback_kernel<WIN, ORD>), dim3(vo_frame_fallback_grid(a.n)), dim3(64), 0, c->stream, a);
     vo_prof_end(c);
   } else if (a.strict == 3) {
     // The replay runs on its own stream NEXT TO the frame kernel, as a pool of IC_CONC_GRID resident workgroups that
@@ -515,10 +516,10 @@ static void frame_launch(vo_ctx *c, const FrameArgs &a, int phase, int p1_target
     hipStream_t main_stream = c->stream;
     c->stream = c->stream3;  // (the event brackets follow c->stream)
     vo_prof_begin(c, VO_K_IC);
-    hipLaunchKernelGGL(frame_replay_kernel<WIN>, dim3(b.n < conc_grid ? b.n : conc_grid), dim3(64), 0, c->stream3, b);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(frame_replay_kernel<WIN, ORD>), dim3(b.n < conc_grid ? b.n : conc_grid), dim3(64), 0, c->stream3, b);
     vo_prof_end(c);
     c->stream = main_stream;
-    hipLaunchKernelGGL(frame_fallback_kernel<WIN>, dim3(vo_frame_fallback_grid(b.n)), dim3(64), 0, c->stream3, b);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(frame_fallback_kernel<WIN, ORD>), dim3(vo_frame_fallback_grid(b.n)), dim3(64), 0, c->stream3, b);
   } else if (a.strict == 5) {
     FrameArgs b = a;
     b.sync_signal = 1;
@@ -527,10 +528,10 @@ static void frame_launch(vo_ctx *c, const FrameArgs &a, int phase, int p1_target
     hipStream_t main_stream = c->stream;
     c->stream = c->stream3;
     vo_prof_begin(c, VO_K_IC);
-    hipLaunchKernelGGL(frame_replay_kernel<WIN>, dim3(b.n < IC_JGRID ? b.n : IC_JGRID), dim3(64), 0, c->stream3, b);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(frame_replay_kernel<WIN, ORD>), dim3(b.n < IC_JGRID ? b.n : IC_JGRID), dim3(64), 0, c->stream3, b);
     vo_prof_end(c);
     c->stream = main_stream;
-    hipLaunchKernelGGL(frame_fallback_kernel<WIN>, dim3(vo_frame_fallback_grid(b.n)), dim3(64), 0, c->stream3, b);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(frame_fallback_kernel<WIN, ORD>), dim3(vo_frame_fallback_grid(b.n)), dim3(64), 0, c->stream3, b);
   }
   (void)p1_target;
   (void)done_target;
@@ -636,11 +637,21 @@ int vo_frame_fused_enqueue(vo_ctx *c, const vo_stereo_params *prm, int slot_l0, 
   }
   const int cg_dbg = c->dbg[VO_DBG_CONC_GRID];  // (tests/test_frame_gpu.py: a pool smaller than the list; experiments)
   const int cg = cg_dbg > 0 ? cg_dbg : (b.conc_grid > 0 ? b.conc_grid : IC_CONC_GRID);
+  // (every phase of a frame reads the order: vo_set_sum_order takes effect at the next frame's enqueue)
+  const bool ord = c->sum_order != 0;
   switch (prm->win) {
-    case 13: frame_launch<13>(c, a, phase, p1_target, done_target, cg, b.split_cands, b.cand_done); break;
-    case 15: frame_launch<15>(c, a, phase, p1_target, done_target, cg, b.split_cands, b.cand_done); break;
-    case 21: frame_launch<21>(c, a, phase, p1_target, done_target, cg, b.split_cands, b.cand_done); break;
-    case 31: frame_launch<31>(c, a, phase, p1_target, done_target, cg, b.split_cands, b.cand_done); break;
+#define VO_FRAME_LAUNCH(W)                                                                                 \
+  case W:                                                                                                  \
+    if (ord)                                                                                               \
+      frame_launch<W, true>(c, a, phase, p1_target, done_target, cg, b.split_cands, b.cand_done);          \
+    else                                                                                                   \
+      frame_launch<W, false>(c, a, phase, p1_target, done_target, cg, b.split_cands, b.cand_done);         \
+    break;
+    VO_FRAME_LAUNCH(13)
+    VO_FRAME_LAUNCH(15)
+    VO_FRAME_LAUNCH(21)
+    VO_FRAME_LAUNCH(31)
+#undef VO_FRAME_LAUNCH
     default: VO_FAIL(c, VO_ERR_INVALID, "fused frame kernel not instantiated for window %d", prm->win);
   }
   VO_CHECK_HIP(c, hipGetLastError());

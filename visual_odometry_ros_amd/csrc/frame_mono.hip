@@ -66,7 +66,8 @@ struct MonoShared {
   IcShared ic;
 };
 
-template <int WIN>
+// ORD (all three kernels): the IC sums in the reference's order (vo_set_sum_order), not the tree
+template <int WIN, bool ORD>
 __global__ __launch_bounds__(64) void mono_track_kernel(MonoArgs a) {
   __shared__ MonoShared<WIN> sh;
   const int i = blockIdx.x + a.wg_off;
@@ -195,7 +196,7 @@ __global__ __launch_bounds__(64) void mono_track_kernel(MonoArgs a) {
   rf.y = fwd.y;
   rf.err_flag = 0;
   if (m1) {
-    rf = ic_point<false>(a.I0[0], a.I1[0], tp, p0x, p0y, fwd.x, fwd.y, scale, lane, sh.ic, S, touched, lpx, lpy, n_iter);
+    rf = ic_point<false, ORD>(a.I0[0], a.I1[0], tp, p0x, p0y, fwd.x, fwd.y, scale, lane, sh.ic, S, touched, lpx, lpy, n_iter);
     cls = rf.cls;
   }
   const int any_t = __any(touched);
@@ -250,15 +251,17 @@ __global__ __launch_bounds__(64) void mono_track_kernel(MonoArgs a) {
 
 // strict border: the touched features (ic_replay), then the sequential fallback if it was requested.
 // (Register cap as frame_replay_kernel's: a replay wavefront shares its SIMD with frame-kernel wavefronts.)
+template <bool ORD>
 __global__ __launch_bounds__(IC_T) __attribute__((amdgpu_num_vgpr(288))) void mono_replay_kernel(MonoReplayArgs a) {
   __shared__ IcReplayShared rs;
   if (a.ic.tl2) {  // next to the frame kernel: what that kernel wrote is read past the caches
     __builtin_amdgcn_s_setprio(3);
-    (void)ic_replay<true>(a.ic, rs, threadIdx.x, [](int, const IcResult &) {});
+    (void)ic_replay<true, ORD>(a.ic, rs, threadIdx.x, [](int, const IcResult &) {});
   } else {
-    (void)ic_replay(a.ic, rs, threadIdx.x, [](int, const IcResult &) {});
+    (void)ic_replay<false, ORD>(a.ic, rs, threadIdx.x, [](int, const IcResult &) {});
   }
 }
+template <bool ORD>
 __global__ __launch_bounds__(IC_T) void mono_fallback_kernel(MonoReplayArgs a) {
   __shared__ IcShared sh;
   const int lane = threadIdx.x;
@@ -280,7 +283,7 @@ __global__ __launch_bounds__(IC_T) void mono_fallback_kernel(MonoReplayArgs a) {
   if (work)
     for (int pt = blockIdx.x; pt < a.ic.n; pt += gridDim.x) {
       __syncthreads();
-      ic_strict_run(a.ic, sh, pt, a.ic.n, lane, [](int, const IcResult &) {});
+      ic_strict_run<ORD>(a.ic, sh, pt, a.ic.n, lane, [](int, const IcResult &) {});
     }
   // stream-ordered behind the replay: when all of its workgroups have counted, every touched feature is final
   if (a.sync_signal) {
@@ -293,26 +296,46 @@ __global__ __launch_bounds__(IC_T) void mono_fallback_kernel(MonoReplayArgs a) {
 static size_t m_align16(size_t v) { return (v + 15) & ~(size_t)15; }
 
 // phase 0: features (+ candidates unless split); phase 2: the candidates as a launch of their own on c->stream (the side stream)
-template <int WIN>
+template <int WIN, bool ORD>
 static void mono_launch(vo_ctx *c, const MonoArgs &a, int phase, bool split, int *cand_done) {
   if (phase == 0) {
     vo_prof_begin(c, VO_K_KLT);
-    hipLaunchKernelGGL(mono_track_kernel<WIN>, dim3(split ? a.n : a.n + a.n_new), dim3(64), 0, c->stream, a);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(mono_track_kernel<WIN, ORD>), dim3(split ? a.n : a.n + a.n_new), dim3(64), 0, c->stream, a);
     vo_prof_end(c);
   } else if (a.n_new > 0) {
     MonoArgs b = a;
     b.wg_off = a.n;
     b.cand_done = cand_done;
-    hipLaunchKernelGGL(mono_track_kernel<WIN>, dim3(a.n_new), dim3(64), 0, c->stream, b);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(mono_track_kernel<WIN, ORD>), dim3(a.n_new), dim3(64), 0, c->stream, b);
   }
 }
-static void mono_launch_any(vo_ctx *c, int win, const MonoArgs &a, int phase, bool split, int *cand_done) {
+template <bool ORD>
+static void mono_launch_win(vo_ctx *c, int win, const MonoArgs &a, int phase, bool split, int *cand_done) {
   switch (win) {
-    case 13: mono_launch<13>(c, a, phase, split, cand_done); break;
-    case 15: mono_launch<15>(c, a, phase, split, cand_done); break;
-    case 21: mono_launch<21>(c, a, phase, split, cand_done); break;
-    default: mono_launch<31>(c, a, phase, split, cand_done); break;
+    case 13: mono_launch<13, ORD>(c, a, phase, split, cand_done); break;
+    case 15: mono_launch<15, ORD>(c, a, phase, split, cand_done); break;
+    case 21: mono_launch<21, ORD>(c, a, phase, split, cand_done); break;
+    default: mono_launch<31, ORD>(c, a, phase, split, cand_done); break;
   }
+}
+// (every phase of a frame reads the order: vo_set_sum_order takes effect at the next frame's enqueue)
+static void mono_launch_any(vo_ctx *c, int win, const MonoArgs &a, int phase, bool split, int *cand_done) {
+  if (c->sum_order)
+    mono_launch_win<true>(c, win, a, phase, split, cand_done);
+  else
+    mono_launch_win<false>(c, win, a, phase, split, cand_done);
+}
+static void mono_replay_launch(vo_ctx *c, int grid, hipStream_t s, const MonoReplayArgs &r) {
+  if (c->sum_order)
+    hipLaunchKernelGGL(mono_replay_kernel<true>, dim3(grid), dim3(IC_T), 0, s, r);
+  else
+    hipLaunchKernelGGL(mono_replay_kernel<false>, dim3(grid), dim3(IC_T), 0, s, r);
+}
+static void mono_fallback_launch(vo_ctx *c, int grid, hipStream_t s, const MonoReplayArgs &r) {
+  if (c->sum_order)
+    hipLaunchKernelGGL(mono_fallback_kernel<true>, dim3(grid), dim3(IC_T), 0, s, r);
+  else
+    hipLaunchKernelGGL(mono_fallback_kernel<false>, dim3(grid), dim3(IC_T), 0, s, r);
 }
 
 // MonoVO (mono_vo.hip): the next vo_mono_frame_enqueue* lets the BA launch build the next track set (mvo_advance_body)
@@ -528,17 +551,17 @@ static int mono_enqueue_impl(vo_ctx *c, const vo_mono_params *prm, int slot0, in
         r.sync_signal = 1;
         c->stream = c->stream3;
         vo_prof_begin(c, VO_K_IC);
-        hipLaunchKernelGGL(mono_replay_kernel, dim3(n < f->conc_grid ? n : f->conc_grid), dim3(IC_T), 0, c->stream3, r);
+        mono_replay_launch(c, n < f->conc_grid ? n : f->conc_grid, c->stream3, r);
         vo_prof_end(c);
         c->stream = s;
-        hipLaunchKernelGGL(mono_fallback_kernel, dim3(fb_grid), dim3(IC_T), 0, c->stream3, r);
+        mono_fallback_launch(c, fb_grid, c->stream3, r);
       } else {
         vo_prof_begin(c, VO_K_IC);
         if (strict == 2)
           (void)hipMemsetAsync(&a.ic.jac[IC_JAC_OVF], 1, sizeof(int), s);
         else
-          hipLaunchKernelGGL(mono_replay_kernel, dim3(n < IC_JGRID ? n : IC_JGRID), dim3(IC_T), 0, s, r);
-        hipLaunchKernelGGL(mono_fallback_kernel, dim3(strict == 2 ? (n < 1024 ? n : 1024) : fb_grid), dim3(IC_T), 0, s, r);
+          mono_replay_launch(c, n < IC_JGRID ? n : IC_JGRID, s, r);
+        mono_fallback_launch(c, strict == 2 ? (n < 1024 ? n : 1024) : fb_grid, s, r);
         vo_prof_end(c);
       }
     }

@@ -342,10 +342,13 @@ __device__ void se3_exp_dev(const float (&xi)[6], float (&T)[16]) {
   T[15] = 1.0f;
 }
 
-// residual rows of one point (motion_estimator.cpp:733-800 mono, :935-1020 stereo)
-template <bool STEREO>
+// residual rows of one point (motion_estimator.cpp:733-800 mono, :935-1020 stereo). ONE_ROW: only the terms of residual
+// row `row` (stereo Lx, Ly, Rx, Ry; mono x, y), added to A; row 0 also writes the inlier mask and counts the outlier.
+template <bool STEREO, bool ONE_ROW = false>
 __device__ __forceinline__ void gn_point(GnAcc &A, const GnArgs &a, const float (&R10)[9], const float (&t10)[3], float X0,
-                                         float X1, float X2, float plx, float ply, float prx, float pry, int i) {
+                                         float X1, float X2, float plx, float ply, float prx, float pry, int i,
+                                         int row = 0) {
+  const bool r0 = !ONE_ROW || row == 0, r1 = !ONE_ROW || row == 1, r2 = !ONE_ROW || row == 2, r3 = !ONE_ROW || row == 3;
   const float THRES_HUBER = 0.5f;
   const float fx_l = a.Kl[0], fy_l = a.Kl[1], cx_l = a.Kl[2], cy_l = a.Kl[3];
   const float fx_r = a.Kr[0], fy_r = a.Kr[1], cx_r = a.Kr[2], cy_r = a.Kr[3];
@@ -372,24 +375,32 @@ __device__ __forceinline__ void gn_point(GnAcc &A, const GnArgs &a, const float 
     absrxry *= 0.5f;
     if (absrxry >= THRES_HUBER) weight = THRES_HUBER / absrxry;
     const bool outl = absrxry >= thres;
-    a.mask[i] = outl ? 0 : 1;
-    if (outl) A.cnt += 1.0f;
-    jac_x(Jt, fx_l, iz_l, fxxiz_l, xiz_l, yiz_l);
-    acc_row_x<true>(A, weight, Jt);
-    acc_g_x(A, weight * rx_l, Jt);
-    A.err += rx_l * rx_l;
-    jac_y(Jt, fy_l, iz_l, fyyiz_l, xiz_l, yiz_l);
-    acc_row_y<true>(A, weight, Jt);
-    acc_g_y(A, weight * ry_l, Jt);
-    A.err += ry_l * ry_l;
-    jac_x(Jt, fx_r, iz_r, fxxiz_r, xiz_r, yiz_r);
-    acc_row_x<true>(A, weight, Jt);
-    acc_g_x(A, weight * rx_r, Jt);
-    A.err += rx_r * rx_r;
-    jac_y(Jt, fy_r, iz_r, fyyiz_r, xiz_r, yiz_r);
-    acc_row_y<true>(A, weight, Jt);
-    acc_g_y(A, weight * ry_r, Jt);
-    A.err += ry_r * ry_r;
+    if (r0) {
+      a.mask[i] = outl ? 0 : 1;
+      if (outl) A.cnt += 1.0f;
+      jac_x(Jt, fx_l, iz_l, fxxiz_l, xiz_l, yiz_l);
+      acc_row_x<true>(A, weight, Jt);
+      acc_g_x(A, weight * rx_l, Jt);
+      A.err += rx_l * rx_l;
+    }
+    if (r1) {
+      jac_y(Jt, fy_l, iz_l, fyyiz_l, xiz_l, yiz_l);
+      acc_row_y<true>(A, weight, Jt);
+      acc_g_y(A, weight * ry_l, Jt);
+      A.err += ry_l * ry_l;
+    }
+    if (r2) {
+      jac_x(Jt, fx_r, iz_r, fxxiz_r, xiz_r, yiz_r);
+      acc_row_x<true>(A, weight, Jt);
+      acc_g_x(A, weight * rx_r, Jt);
+      A.err += rx_r * rx_r;
+    }
+    if (r3) {
+      jac_y(Jt, fy_r, iz_r, fyyiz_r, xiz_r, yiz_r);
+      acc_row_y<true>(A, weight, Jt);
+      acc_g_y(A, weight * ry_r, Jt);
+      A.err += ry_r * ry_r;
+    }
   } else {
     const float iz = 1.0f / Xl[2];
     const float xiz = Xl[0] * iz, yiz = Xl[1] * iz;
@@ -403,17 +414,20 @@ __device__ __forceinline__ void gn_point(GnAcc &A, const GnArgs &a, const float 
       flag_weight = true;
     }
     const bool outl = absrxry >= thres;
-    a.mask[i] = outl ? 0 : 1;
-    if (outl) A.cnt += 1.0f;
-    jac_x(Jt, fx_l, iz, fxxiz, xiz, yiz);
-    if (flag_weight) {
-      acc_row_x<true>(A, weight, Jt);
-      acc_g_x(A, weight * rx, Jt);
-    } else {
-      acc_row_x<false>(A, 1.0f, Jt);
-      acc_g_x(A, rx, Jt);
+    if (r0) {
+      a.mask[i] = outl ? 0 : 1;
+      if (outl) A.cnt += 1.0f;
+      jac_x(Jt, fx_l, iz, fxxiz, xiz, yiz);
+      if (flag_weight) {
+        acc_row_x<true>(A, weight, Jt);
+        acc_g_x(A, weight * rx, Jt);
+      } else {
+        acc_row_x<false>(A, 1.0f, Jt);
+        acc_g_x(A, rx, Jt);
+      }
+      A.err += rx * rx;
     }
-    A.err += rx * rx;
+    if (!r1) return;
     jac_y(Jt, fy_l, iz, fyyiz, xiz, yiz);
     if (flag_weight) {
       const float w_ry = weight * ry;
@@ -441,10 +455,13 @@ extern "C" int vo_debug_gn_stamps(vo_ctx *c, long long out[12]) {
 #endif
 #define GN_PC 4  // points per thread kept in registers across the iterations (n <= GN_PC * GN_T: no reloads)
 
-template <bool STEREO>
+// ORD: the 28 float sums in the reference's order (vo_set_sum_order) instead of the tree; see the iteration loop
+template <bool STEREO, bool ORD>
 __global__ __launch_bounds__(GN_T) void gn_pose_kernel(GnArgs a) {
-  // thread partials, transposed: s_red[k][t]; wavefront w then reduces sums 4w .. 4w+3
-  __shared__ float s_red[GN_NACC * GN_T];
+  // thread partials, transposed: s_red[k][t]; wavefront w then reduces sums 4w .. 4w+3. ORD: per-row terms, one
+  // padding float per sum so that the 29 lanes that walk them read 29 different banks
+  constexpr int RED_LD = ORD ? GN_T + 1 : GN_T;
+  __shared__ float s_red[GN_NACC * RED_LD];
   __shared__ float s_tot[32];
   __shared__ float s_T10[16];
   __shared__ int s_stop;
@@ -618,7 +635,7 @@ __global__ __launch_bounds__(GN_T) void gn_pose_kernel(GnArgs a) {
   // the first GN_PC points of this thread stay in registers
   float cX[GN_PC][3], cP1[GN_PC][2], cP2[GN_PC][2];
 #pragma unroll
-  for (int q = 0; q < GN_PC; ++q) {
+  for (int q = 0; q < (ORD ? 0 : GN_PC); ++q) {
     const int i = tid + q * GN_T;
     const int ii = i < n ? i : 0;
     const bool ok = n > 0;
@@ -645,54 +662,90 @@ __global__ __launch_bounds__(GN_T) void gn_pose_kernel(GnArgs a) {
       for (int j = 0; j < 3; ++j) R10[i * 3 + j] = T10[i * 4 + j];
       t10[i] = T10[i * 4 + 3];
     }
-    GnAcc A;
-    gn_acc_clear(A);
+    if constexpr (ORD) {
+      // ---- reference order: every accumulator adds its terms point by point and, within a point, row by row, one
+      // dependent add after the other (motion_estimator.cpp:920-1040 stereo, :713-810 mono; oracle VO_SUM_SEQ). In
+      // chunks of GN_T / ROWS points: thread t computes the terms of row t % ROWS of point t / ROWS (the same products
+      // as the tree path, from a cleared accumulator: 0 + p == p, 0 - p == -p) into s_red[k][t], then lane k of
+      // wavefront 0 adds slots 0, 1, .. of sum k to its running total. (cnt is an exact integer in float.)
+      constexpr int ROWS = STEREO ? 4 : 2, PPC = GN_T / ROWS;
+      float run = 0.0f;
+      for (int base = 0; base < n; base += PPC) {
+        GnAcc A;
+        gn_acc_clear(A);
+        const int i = base + tid / ROWS;
+        if (i < n)
+          gn_point<STEREO, true>(A, a, R10, t10, a.X[3 * i], a.X[3 * i + 1], a.X[3 * i + 2], a.p1[2 * i], a.p1[2 * i + 1],
+                                 STEREO ? a.p2[2 * i] : 0.f, STEREO ? a.p2[2 * i + 1] : 0.f, i, tid % ROWS);
+        float AH[21], Ag[6];
+        gn_acc_unpack(A, AH, Ag);
+#pragma unroll
+        for (int k = 0; k < 21; ++k) s_red[k * RED_LD + tid] = AH[k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) s_red[(21 + k) * RED_LD + tid] = Ag[k];
+        s_red[27 * RED_LD + tid] = A.err;
+        s_red[28 * RED_LD + tid] = A.cnt;
+        __syncthreads();
+        if (wave == 0 && lane < GN_NACC) {
+          const int m = min(PPC, n - base) * ROWS;
+          const float *col = s_red + lane * RED_LD;
+#pragma unroll 8
+          for (int q = 0; q < m; ++q) run = run + col[q];
+        }
+        __syncthreads();
+      }
+      if (wave == 0 && lane < GN_NACC) s_tot[lane] = run;
+      __syncthreads();
+    } else {
+      GnAcc A;
+      gn_acc_clear(A);
 
-    // thread t: points t, t + GN_T, ... in ascending order
+      // thread t: points t, t + GN_T, ... in ascending order
 #pragma unroll
-    for (int q = 0; q < GN_PC; ++q) {
-      const int i = tid + q * GN_T;
-      if (i < n)
-        gn_point<STEREO>(A, a, R10, t10, cX[q][0], cX[q][1], cX[q][2], cP1[q][0], cP1[q][1], cP2[q][0], cP2[q][1], i);
-    }
-    for (int i = tid + GN_PC * GN_T; i < n; i += GN_T)
-      gn_point<STEREO>(A, a, R10, t10, a.X[3 * i], a.X[3 * i + 1], a.X[3 * i + 2], a.p1[2 * i], a.p1[2 * i + 1],
-                       STEREO ? a.p2[2 * i] : 0.f, STEREO ? a.p2[2 * i + 1] : 0.f, i);
+      for (int q = 0; q < GN_PC; ++q) {
+        const int i = tid + q * GN_T;
+        if (i < n)
+          gn_point<STEREO>(A, a, R10, t10, cX[q][0], cX[q][1], cX[q][2], cP1[q][0], cP1[q][1], cP2[q][0], cP2[q][1], i);
+      }
+      for (int i = tid + GN_PC * GN_T; i < n; i += GN_T)
+        gn_point<STEREO>(A, a, R10, t10, a.X[3 * i], a.X[3 * i + 1], a.X[3 * i + 2], a.p1[2 * i], a.p1[2 * i + 1],
+                         STEREO ? a.p2[2 * i] : 0.f, STEREO ? a.p2[2 * i + 1] : 0.f, i);
 
-    // ---- reduction: balanced binary tree over the GN_T thread partials in natural order ----
-    // transposed through LDS so that a lane adds 8 neighbouring partials (three tree levels) and
-    // ONE 4-way DPP butterfly per wavefront finishes the other six, instead of eight butterflies
-    {
-      float AH[21], Ag[6];
-      gn_acc_unpack(A, AH, Ag);
+      // ---- reduction: balanced binary tree over the GN_T thread partials in natural order ----
+      // transposed through LDS so that a lane adds 8 neighbouring partials (three tree levels) and
+      // ONE 4-way DPP butterfly per wavefront finishes the other six, instead of eight butterflies
+      {
+        float AH[21], Ag[6];
+        gn_acc_unpack(A, AH, Ag);
 #pragma unroll
-      for (int k = 0; k < 21; ++k) s_red[k * GN_T + tid] = AH[k];
+        for (int k = 0; k < 21; ++k) s_red[k * GN_T + tid] = AH[k];
 #pragma unroll
-      for (int k = 0; k < 6; ++k) s_red[(21 + k) * GN_T + tid] = Ag[k];
-      s_red[27 * GN_T + tid] = A.err;
-      s_red[28 * GN_T + tid] = A.cnt;
-    }
-    __syncthreads();
-    {
-      float v[4];
+        for (int k = 0; k < 6; ++k) s_red[(21 + k) * GN_T + tid] = Ag[k];
+        s_red[27 * GN_T + tid] = A.err;
+        s_red[28 * GN_T + tid] = A.cnt;
+      }
+      __syncthreads();
+      {
+        float v[4];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const int k = 4 * wave + c;
-        if (k < GN_NACC) {
-          const float4 lo = *(const float4 *)&s_red[k * GN_T + 8 * lane];
-          const float4 hi = *(const float4 *)&s_red[k * GN_T + 8 * lane + 4];
-          v[c] = ((lo.x + lo.y) + (lo.z + lo.w)) + ((hi.x + hi.y) + (hi.z + hi.w));
-        } else {
-          v[c] = 0.0f;
+        for (int c = 0; c < 4; ++c) {
+          const int k = 4 * wave + c;
+          if (k < GN_NACC) {
+            const float4 lo = *(const float4 *)&s_red[k * GN_T + 8 * lane];
+            const float4 hi = *(const float4 *)&s_red[k * GN_T + 8 * lane + 4];
+            v[c] = ((lo.x + lo.y) + (lo.z + lo.w)) + ((hi.x + hi.y) + (hi.z + hi.w));
+          } else {
+            v[c] = 0.0f;
+          }
+        }
+        wave_sum4_f32(v[0], v[1], v[2], v[3]);
+        if (lane == 0) {
+#pragma unroll
+          for (int c = 0; c < 4; ++c) s_tot[4 * wave + c] = v[c];
         }
       }
-      wave_sum4_f32(v[0], v[1], v[2], v[3]);
-      if (lane == 0) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) s_tot[4 * wave + c] = v[c];
-      }
-    }
-    __syncthreads();
+      __syncthreads();
+    }  // tree order
     // ---- wavefront 0 (all lanes alike): damped normal equations, LDLT, pose update, stop test.
     // The ~1600-instruction solve is issue-bound; run by every wavefront it would compete with
     // itself for the four SIMDs of the CU.
@@ -1138,10 +1191,15 @@ int vo_gn_enqueue(vo_ctx *c, bool stereo, bool mono_general_inverse, const float
   a.gate_thres = gate_thres;
   vo_prof_begin(c, VO_K_GN);
   const int workers = (stereo && a.adv.on) ? (a.np.bins + 63) / 64 : 0;  // StereoVO: DLT of every bin's candidate
-  if (stereo)
-    hipLaunchKernelGGL(gn_pose_kernel<true>, dim3(1 + workers), dim3(GN_T), 0, c->stream, a);
+  const bool ord = c->sum_order != 0;
+  if (stereo && ord)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_pose_kernel<true, true>), dim3(1 + workers), dim3(GN_T), 0, c->stream, a);
+  else if (stereo)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_pose_kernel<true, false>), dim3(1 + workers), dim3(GN_T), 0, c->stream, a);
+  else if (ord)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_pose_kernel<false, true>), dim3(1), dim3(GN_T), 0, c->stream, a);
   else
-    hipLaunchKernelGGL(gn_pose_kernel<false>, dim3(1), dim3(GN_T), 0, c->stream, a);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(gn_pose_kernel<false, false>), dim3(1), dim3(GN_T), 0, c->stream, a);
   vo_prof_end(c);
   VO_CHECK_HIP(c, hipGetLastError());
   return VO_OK;

@@ -134,6 +134,38 @@ __device__ __forceinline__ int ic_safe_int(float v) {
 // Wavefront sums of four per-lane partials in the canonical tree order; every lane gets the same bits.
 __device__ __forceinline__ void ic_wave_sum4(float (&v)[4]) { wave_sum4_f32(v[0], v[1], v[2], v[3]); }
 
+// Reference summation order (ORD, vo_set_sum_order(VO_SUM_ORDER_REFERENCE)): three sums of per-tap terms, each added
+// one term after the other in ascending tap index j, as feature_tracker.cpp:426-458 does (oracle VO_SUM_SEQ).
+// terms(k, t0, t1, t2) gives the lane's terms of tap lane + 64 k; they are computed slot by slot and staged in the
+// template tile, which is dead by then (ic_template is its only reader and runs again before the tile is next needed),
+// so only one slot's terms are live at a time. Lane c < 3 walks sum c, and every lane receives the three results. A
+// masked tap's term is +0: the same bits as skipping it, since these sums never become -0.
+template <typename Terms>
+__device__ __forceinline__ void ic_seq_sum3(IcShared &sh, int lane, Terms terms, float &s0, float &s1, float &s2) {
+  static_assert(3 * IC_T <= IC_TH * IC_TW, "the staged terms of one slot fit the template tile");
+  float *st = (float *)sh.tt;  // [3][IC_T]
+  const float *mine = st + (lane < 3 ? lane : 0) * IC_T;
+  float s = 0.0f;
+#pragma unroll
+  for (int k = 0; k < IC_K; ++k) {
+    float t0, t1, t2;
+    terms(k, t0, t1, t2);
+    __syncthreads();  // (one wavefront: the walk of the previous slot is done before its terms are overwritten)
+    st[lane] = t0;
+    st[IC_T + lane] = t1;
+    st[2 * IC_T + lane] = t2;
+    __syncthreads();
+    const int nk = k < 4 ? IC_T : IC_NELEM - 4 * IC_T;  // taps in slot k
+    if (lane < 3) {
+#pragma unroll 8
+      for (int l = 0; l < nk; ++l) s = s + mine[l];
+    }
+  }
+  s0 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), 0));
+  s1 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), 1));
+  s2 = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(s), 2));
+}
+
 // ---- LDS tiles: the global loads are issued first (registers), committed to LDS later, so
 // that both tiles of a point share one exposure of the memory latency ----
 template <int N>
@@ -308,7 +340,7 @@ struct IcPrep {
   float iD_A11, iD_A12, iD_A22;
   IcTile tile;  // search tile staged in sh.tj
 };
-template <bool STRICT>
+template <bool STRICT, bool ORD = false>
 __device__ __forceinline__ IcPrep ic_prepare(const vo_level &I0, const vo_level &I1, const IcTaps &tp, float pt0x,
                                              float pt0y, float pt1x, float pt1y, int lane, IcShared &sh, IcState &S,
                                              int &touched) {
@@ -327,14 +359,23 @@ __device__ __forceinline__ IcPrep ic_prepare(const vo_level &I0, const vo_level 
   const IcTile tt = {rt.x0, rt.y0};
   ic_template<STRICT>(I0, tp, pt0x, pt0y, ax, ay, axay, tt, sh, S, touched);
   float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  if constexpr (ORD) {
+    ic_seq_sum3(sh, lane, [&](int k, float &t0, float &t1, float &t2) {
+      const bool use = (S.m >> k) & 1u;
+      t0 = use ? S.du[k] * S.du[k] : 0.f;
+      t1 = use ? S.du[k] * S.dv[k] : 0.f;
+      t2 = use ? S.dv[k] * S.dv[k] : 0.f;
+    }, acc[0], acc[1], acc[2]);
+  } else {
 #pragma unroll
-  for (int k = 0; k < IC_K; ++k) {
-    const bool use = (S.m >> k) & 1u;
-    acc[0] = use ? acc[0] + S.du[k] * S.du[k] : acc[0];
-    acc[1] = use ? acc[1] + S.du[k] * S.dv[k] : acc[1];
-    acc[2] = use ? acc[2] + S.dv[k] * S.dv[k] : acc[2];
+    for (int k = 0; k < IC_K; ++k) {
+      const bool use = (S.m >> k) & 1u;
+      acc[0] = use ? acc[0] + S.du[k] * S.du[k] : acc[0];
+      acc[1] = use ? acc[1] + S.du[k] * S.dv[k] : acc[1];
+      acc[2] = use ? acc[2] + S.dv[k] * S.dv[k] : acc[2];
+    }
+    ic_wave_sum4(acc);
   }
-  ic_wave_sum4(acc);
   const float A11 = acc[0], A12 = acc[1], A22 = acc[2];
   const float D = A11 * A22 - A12 * A12;
   if (D < 1e-4f) return pr;
@@ -350,10 +391,10 @@ __device__ __forceinline__ IcPrep ic_prepare(const vo_level &I0, const vo_level 
 }
 
 // The iterations of one prepared feature (feature_tracker.cpp:398-503).
-template <bool STRICT>
+template <bool STRICT, bool ORD = false>
 __device__ __forceinline__ IcResult ic_iterate(const vo_level &I1, const IcTaps &tp, const IcPrep &pr, float pt0x,
                                                float pt0y, float pt1x, float pt1y, float scale, int lane,
-                                               const IcShared &sh, IcState &S, int &touched, float &last_pux,
+                                               IcShared &sh, IcState &S, int &touched, float &last_pux,
                                                float &last_puy, int &n_iter) {
   IcResult res;
   res.cls = pr.cls;
@@ -389,18 +430,32 @@ __device__ __forceinline__ IcResult ic_iterate(const vo_level &I1, const IcTaps 
     ic_sample_I1<STRICT>(I1, tp, sx, sy, pux, puy, ax, ay, axay, S, touched, tile, sh);
     float v[4] = {0.f, 0.f, 0.f, 0.f};  // b1, b2, sum r^2, count
     const unsigned both = S.m & (S.m >> 8);
+    if constexpr (ORD) {
+      int cnt = 0;  // (an exact integer: its order does not matter)
 #pragma unroll
-    for (int k = 0; k < IC_K; ++k) {
-      // An unused tap adds (+-0) * finite = +-0 to sums that are never -0 (they start at +0 and x + (-x) = +0): the
-      // same bits as skipping the addition, one select instead of four.
-      const bool use = (both >> k) & 1u;
-      const float r = use ? S.I1[k] - S.I0[k] : 0.f;
-      v[0] = v[0] + S.du[k] * r;
-      v[1] = v[1] + S.dv[k] * r;
-      v[2] = v[2] + r * r;
-      v[3] = v[3] + (use ? 1.0f : 0.f);
+      for (int k = 0; k < IC_K; ++k) cnt += __popcll(__ballot((both >> k) & 1u));
+      ic_seq_sum3(sh, lane, [&](int k, float &t0, float &t1, float &t2) {
+        const bool use = (both >> k) & 1u;
+        const float r = use ? S.I1[k] - S.I0[k] : 0.f;
+        t0 = S.du[k] * r;
+        t1 = S.dv[k] * r;
+        t2 = r * r;
+      }, v[0], v[1], v[2]);
+      v[3] = (float)cnt;
+    } else {
+#pragma unroll
+      for (int k = 0; k < IC_K; ++k) {
+        // An unused tap adds (+-0) * finite = +-0 to sums that are never -0 (they start at +0 and x + (-x) = +0): the
+        // same bits as skipping the addition, one select instead of four.
+        const bool use = (both >> k) & 1u;
+        const float r = use ? S.I1[k] - S.I0[k] : 0.f;
+        v[0] = v[0] + S.du[k] * r;
+        v[1] = v[1] + S.dv[k] * r;
+        v[2] = v[2] + r * r;
+        v[3] = v[3] + (use ? 1.0f : 0.f);
+      }
+      ic_wave_sum4(v);
     }
-    ic_wave_sum4(v);
     ++n_iter;
     b1 = v[0];
     b2 = v[1];
@@ -441,21 +496,22 @@ __device__ __forceinline__ IcResult ic_iterate(const vo_level &I1, const IcTaps 
 
 // One point, feature_tracker.cpp:336-503: template at pt0 in I0, refinement in I1 from the prior
 // pt1. All 64 lanes call it together with the same arguments; nothing is written to memory.
-template <bool STRICT>
+template <bool STRICT, bool ORD = false>
 __device__ __forceinline__ IcResult ic_point(const vo_level &I0, const vo_level &I1, const IcTaps &tp, float pt0x,
                                              float pt0y, float pt1x, float pt1y, float scale, int lane, IcShared &sh,
                                              IcState &S, int &touched, float &last_pux, float &last_puy, int &n_iter) {
-  const IcPrep pr = ic_prepare<STRICT>(I0, I1, tp, pt0x, pt0y, pt1x, pt1y, lane, sh, S, touched);
-  return ic_iterate<STRICT>(I1, tp, pr, pt0x, pt0y, pt1x, pt1y, scale, lane, sh, S, touched, last_pux, last_puy, n_iter);
+  const IcPrep pr = ic_prepare<STRICT, ORD>(I0, I1, tp, pt0x, pt0y, pt1x, pt1y, lane, sh, S, touched);
+  return ic_iterate<STRICT, ORD>(I1, tp, pr, pt0x, pt0y, pt1x, pt1y, scale, lane, sh, S, touched, last_pux, last_puy,
+                                 n_iter);
 }
 
 // ic_point on array operands: inputs of point `pt` from a.pts0 / a.pts_prior / a.scale, results to
 // a.mask / a.pts_track (the prior when the refinement is rejected) / a.flags.
-template <bool STRICT>
+template <bool STRICT, bool ORD = false>
 __device__ __forceinline__ IcResult ic_point_io(const IcArgs &a, const IcTaps &tp, int pt, int lane, IcShared &sh,
                                                 IcState &S, int &touched, float &last_pux, float &last_puy,
                                                 int &n_iter) {
-  const IcResult r = ic_point<STRICT>(a.I0, a.I1, tp, a.pts0[2 * pt], a.pts0[2 * pt + 1], a.pts_prior[2 * pt],
+  const IcResult r = ic_point<STRICT, ORD>(a.I0, a.I1, tp, a.pts0[2 * pt], a.pts0[2 * pt + 1], a.pts_prior[2 * pt],
                                       a.pts_prior[2 * pt + 1], a.scale[pt], lane, sh, S, touched, last_pux, last_puy,
                                       n_iter);
   if (lane == 0) {
@@ -709,7 +765,7 @@ __device__ __forceinline__ void ic_find_writers(IcReplayShared &rs, unsigned wan
 // producer wait, and a waiting workgroup only ever waits for entries with a lower feature index or for the producer,
 // so the dependency chains start as soon as their members are through pass 1 instead of after the producer's last
 // wavefront. The quiescence vote additionally requires that the producer had finished before the voter's pass began.
-template <bool CONC = false, typename AfterRun>
+template <bool CONC = false, bool ORD = false, typename AfterRun>
 __device__ __forceinline__ int ic_replay(const IcArgs &a, IcReplayShared &rs, int lane, AfterRun after_run) {
   IcShared &sh = rs.sh;
   int n_touched = CONC ? 0 : a.jac[IC_JAC_NT];
@@ -876,7 +932,7 @@ __device__ __forceinline__ int ic_replay(const IcArgs &a, IcReplayShared &rs, in
         if (single) {
           // S0 becomes the state after the feature's own template evaluation (static, like its inputs)
           int dummy_t = 0;
-          prep = ic_prepare<true>(a.I0, a.I1, tp, p0x, p0y, ic_in<CONC>(&a.pts_prior[2 * pt]),
+          prep = ic_prepare<true, ORD>(a.I0, a.I1, tp, p0x, p0y, ic_in<CONC>(&a.pts_prior[2 * pt]),
                                   ic_in<CONC>(&a.pts_prior[2 * pt + 1]), lane, sh, S0, dummy_t);
         }
         ic_state_put(rs.s0, S0, lane);
@@ -1111,8 +1167,8 @@ __device__ __forceinline__ int ic_replay(const IcArgs &a, IcReplayShared &rs, in
       {
         const float q1x = ic_in<CONC>(&a.pts_prior[2 * pt]), q1y = ic_in<CONC>(&a.pts_prior[2 * pt + 1]);
         IcPrep pr = prep;
-        if (!single) pr = ic_prepare<true>(a.I0, a.I1, tp, p0x, p0y, q1x, q1y, lane, sh, S, dummy);
-        res_pt = ic_iterate<true>(a.I1, tp, pr, p0x, p0y, q1x, q1y, ic_in<CONC>(&a.scale[pt]), lane, sh, S, dummy, lx, ly, n_iter);
+        if (!single) pr = ic_prepare<true, ORD>(a.I0, a.I1, tp, p0x, p0y, q1x, q1y, lane, sh, S, dummy);
+        res_pt = ic_iterate<true, ORD>(a.I1, tp, pr, p0x, p0y, q1x, q1y, ic_in<CONC>(&a.scale[pt]), lane, sh, S, dummy, lx, ly, n_iter);
 #ifdef IC_REPLAY_EXTRA_SLEEP  // measurement build: every replayed iteration made LONGER by s_sleep(IC_REPLAY_EXTRA_SLEEP) — 64 cycles
         // each — to read off how much of an iteration's cost is on the frame's critical path
         for (int q = 0; q < n_iter; ++q) __builtin_amdgcn_s_sleep(IC_REPLAY_EXTRA_SLEEP);
@@ -1249,7 +1305,7 @@ __device__ __forceinline__ int ic_replay(const IcArgs &a, IcReplayShared &rs, in
 // ic_replay): one wavefront walks the run, the carried tap state lives in registers. Returns at once
 // unless `pt` is the first touched feature of its run. `after_point(p, result)` is called for every
 // touched feature replayed.
-template <typename AfterPoint>
+template <bool ORD = false, typename AfterPoint>
 __device__ __forceinline__ void ic_strict_run(const IcArgs &a, IcShared &sh, int pt, int n, int lane,
                                               AfterPoint after_point) {
   if (!a.touched[pt]) return;
@@ -1312,7 +1368,7 @@ __device__ __forceinline__ void ic_strict_run(const IcArgs &a, IcShared &sh, int
       continue;
     }
     float lx, ly;
-    const IcResult r = ic_point_io<true>(a, tp, p, lane, sh, S, dummy, lx, ly, n_iter);
+    const IcResult r = ic_point_io<true, ORD>(a, tp, p, lane, sh, S, dummy, lx, ly, n_iter);
     after_point(p, r);
   }
 }

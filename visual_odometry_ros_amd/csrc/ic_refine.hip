@@ -42,6 +42,8 @@
 #include "vo_kernels.hpp"
 
 // ---- pass 1: every point in parallel -------------------------------------------
+// ORD: the sums in the reference's order (ic_seq_sum3) instead of the tree, in all three kernels
+template <bool ORD>
 __global__ __launch_bounds__(IC_T) void ic_refine_kernel(IcArgs a) {
   __shared__ IcShared sh;
   const int n = a.d_n ? *a.d_n : a.n;
@@ -58,7 +60,7 @@ __global__ __launch_bounds__(IC_T) void ic_refine_kernel(IcArgs a) {
   IcState S;
   ic_state_clear(S);
   if (entry) {
-    cls = ic_point_io<false>(a, tp, pt, lane, sh, S, touched, lpx, lpy, n_iter).cls;
+    cls = ic_point_io<false, ORD>(a, tp, pt, lane, sh, S, touched, lpx, lpy, n_iter).cls;
   } else if (lane == 0) {
     a.pts_track[2 * pt] = a.pts_prior[2 * pt];
     a.pts_track[2 * pt + 1] = a.pts_prior[2 * pt + 1];
@@ -87,12 +89,14 @@ __global__ __launch_bounds__(IC_T) void ic_refine_kernel(IcArgs a) {
 }
 
 // ---- pass 2a: parallel fixed-point replay of the touched points (ic_device.hpp: ic_replay) ----
+template <bool ORD>
 __global__ __launch_bounds__(IC_T) void ic_jacobi_kernel(IcArgs a) {
   __shared__ IcReplayShared rs;
-  (void)ic_replay(a, rs, threadIdx.x, [](int, const IcResult &) {});
+  (void)ic_replay<false, ORD>(a, rs, threadIdx.x, [](int, const IcResult &) {});
 }
 
 // ---- pass 2: sequential replay of the runs that contain touched points (ic_device.hpp: ic_strict_run) ----
+template <bool ORD>
 __global__ __launch_bounds__(IC_T) void ic_strict_kernel(IcArgs a) {
   __shared__ IcShared sh;
   const int n = a.d_n ? *a.d_n : a.n;
@@ -100,7 +104,7 @@ __global__ __launch_bounds__(IC_T) void ic_strict_kernel(IcArgs a) {
   if (pt >= n) return;
   // with the parallel replay in front, this kernel only runs when that did not finish
   if (a.jac && a.jac[IC_JAC_OVF] == 0) return;
-  ic_strict_run(a, sh, pt, n, threadIdx.x, [](int, const IcResult &) {});
+  ic_strict_run<ORD>(a, sh, pt, n, threadIdx.x, [](int, const IcResult &) {});
 }
 
 static int ic_args(vo_ctx *c, int slot0, int slot1, IcArgs &a, int *d_flags) {
@@ -158,7 +162,10 @@ int vo_ic_frame_args(vo_ctx *c, int slot0, int slot1, IcArgs *a, int *ctl, bool 
   return VO_OK;
 }
 void vo_ic_strict_launch(vo_ctx *c, const IcArgs &a) {
-  hipLaunchKernelGGL(ic_strict_kernel, dim3(a.n), dim3(IC_T), 0, c->stream, a);
+  if (c->sum_order)
+    hipLaunchKernelGGL(ic_strict_kernel<true>, dim3(a.n), dim3(IC_T), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(ic_strict_kernel<false>, dim3(a.n), dim3(IC_T), 0, c->stream, a);
 }
 
 // pass 1. d_prior and d_pts_track must be different buffers. with_records: also write the tap
@@ -189,7 +196,10 @@ int vo_ic_enqueue(vo_ctx *c, int slot0, int slot1, const float *d_pts0, const fl
   a.n = n_max;
   a.d_n = d_n;
   vo_prof_begin(c, VO_K_IC);
-  hipLaunchKernelGGL(ic_refine_kernel, dim3(n_max), dim3(IC_T), 0, c->stream, a);
+  if (c->sum_order)
+    hipLaunchKernelGGL(ic_refine_kernel<true>, dim3(n_max), dim3(IC_T), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(ic_refine_kernel<false>, dim3(n_max), dim3(IC_T), 0, c->stream, a);
   vo_prof_end(c);
   VO_CHECK_HIP(c, hipGetLastError());
   return VO_OK;
@@ -219,11 +229,17 @@ int vo_ic_strict_enqueue(vo_ctx *c, int slot0, int slot1, const float *d_pts0, c
   a.n = n_max;
   a.d_n = d_n;
   vo_prof_begin(c, VO_K_IC);
+  const bool ord = c->sum_order != 0;
   if (sequential_only)  // validation mode: request the fallback up front
     VO_CHECK_HIP(c, hipMemsetAsync(&a.jac[IC_JAC_OVF], 1, sizeof(int), c->stream));
+  else if (ord)
+    hipLaunchKernelGGL(ic_jacobi_kernel<true>, dim3(n_max < IC_JGRID ? n_max : IC_JGRID), dim3(IC_T), 0, c->stream, a);
   else
-    hipLaunchKernelGGL(ic_jacobi_kernel, dim3(n_max < IC_JGRID ? n_max : IC_JGRID), dim3(IC_T), 0, c->stream, a);
-  hipLaunchKernelGGL(ic_strict_kernel, dim3(n_max), dim3(IC_T), 0, c->stream, a);
+    hipLaunchKernelGGL(ic_jacobi_kernel<false>, dim3(n_max < IC_JGRID ? n_max : IC_JGRID), dim3(IC_T), 0, c->stream, a);
+  if (ord)
+    hipLaunchKernelGGL(ic_strict_kernel<true>, dim3(n_max), dim3(IC_T), 0, c->stream, a);
+  else
+    hipLaunchKernelGGL(ic_strict_kernel<false>, dim3(n_max), dim3(IC_T), 0, c->stream, a);
   vo_prof_end(c);
   VO_CHECK_HIP(c, hipGetLastError());
   return VO_OK;

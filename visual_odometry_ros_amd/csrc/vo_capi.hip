@@ -27,6 +27,16 @@ extern "C" int vo_synchronize(vo_ctx *ctx) {
   return VO_OK;
 }
 
+extern "C" int vo_set_sum_order(vo_ctx *ctx, int order) {
+  if (!ctx) return VO_ERR_INVALID;
+  if (order != VO_SUM_ORDER_TREE && order != VO_SUM_ORDER_REFERENCE)
+    VO_FAIL(ctx, VO_ERR_INVALID, "sum order %d: expected VO_SUM_ORDER_TREE (0) or VO_SUM_ORDER_REFERENCE (1)", order);
+  ctx->sum_order = order;
+  return VO_OK;
+}
+
+extern "C" int vo_get_sum_order(const vo_ctx *ctx) { return ctx ? ctx->sum_order : VO_ERR_INVALID; }
+
 template <typename T>
 static hipError_t dalloc(vo_ctx *c, T **p, size_t n) {
   return vo_dev_malloc(c, (void **)p, n * sizeof(T));

@@ -81,6 +81,7 @@ struct vo_ctx {
   int frame_conc_off;      // a device-side join timed out once: the concurrent arrangements (3, 5, 4 -> 3) are off for good
   int frame_slots_busy;    // a frame is in flight and reads frame_slot[0..2]
   int frame_slot[3];
+  int sum_order;           // VO_SUM_ORDER_*: read by every launch of the IC and GN kernels (0: tree, the default)
   // profiling
   vo_prof_rec *prof;
   int prof_cap, prof_n;
