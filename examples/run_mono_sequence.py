@@ -1,0 +1,76 @@
+"""Monocular visual odometry over an image sequence on disk, configured by one of the reference's YAML files — what
+`ros2 run visual_odometry mono_vo_node` does with a rosbag, without ROS and without OpenCV: the essential-matrix pose of the
+initialisation and of the 5-point fallback is the library's own (FivePointRansac, motion_estimator.thres_5p_error).
+
+    python examples/run_mono_sequence.py --config config/mono/kitti_00.yaml \
+        --images /data/kitti/sequences/00/image_0 --trajectory frame_poses.txt [--keyframes keyframes.txt] [--max-frames N]
+
+Images: 8-bit grey PNG / PGM / JPEG ... (whatever PIL opens; colour is converted), in sorted file-name order. The next image
+is handed over while the current one is tracked (vo_mvo_prefetch). Output: the reference's trajectory format (`id` + the 12
+numbers of [R|t], `%.4f`), one line per frame; optionally every keyframe's current pose after the last frame. Monocular
+poses carry the scale of the first motion (unit length)."""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def load_grey(path):
+    from PIL import Image
+    im = Image.open(path)
+    if im.mode != "L":
+        im = im.convert("L")
+    return np.ascontiguousarray(np.asarray(im, dtype=np.uint8))
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--config", required=True, help="a config/mono/*.yaml file of the reference")
+    ap.add_argument("--images", required=True, help="directory of the images")
+    ap.add_argument("--trajectory", default="frame_poses.txt")
+    ap.add_argument("--keyframes", default=None, help="also write the keyframes' current poses there")
+    ap.add_argument("--max-frames", type=int, default=0)
+    ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--strict-border", type=int, default=4, help="see vo_stereo_frame_set_strict_border (0: masked border taps)")
+    ap.add_argument("--no-local-ba", action="store_true")
+    args = ap.parse_args()
+    import visual_odometry_ros_amd as V
+    names = sorted(os.listdir(args.images))
+    n = len(names) if not args.max_frames else min(len(names), args.max_frames)
+    if n == 0:
+        raise SystemExit("no images found")
+    mvo = V.MonoVO.from_yaml(args.config, device=args.device, strict_border=args.strict_border, local_ba=not args.no_local_ba)
+    image = lambda k: load_grey(os.path.join(args.images, names[k]))  # noqa: E731
+    ids, poses, n_kf, n_5p = [], [], 0, 0
+    cur = image(0)
+    t0 = time.perf_counter()
+    for k in range(n):
+        mvo.enqueue(cur)
+        nxt = image(k + 1) if k + 1 < n else None  # (decoded while the GPU tracks frame k)
+        if nxt is not None:
+            mvo.prefetch(nxt)
+        info = mvo.result()
+        ids.append(info.frame_id)
+        poses.append(np.array(info.T_wc, np.float32).reshape(4, 4))
+        n_kf += int(info.is_keyframe)
+        n_5p += int(info.used_five_point)
+        if k % 100 == 0 or k == n - 1:
+            t = poses[-1][:3, 3]
+            print(f"frame {k:6d}: {info.n_tracks_out:5d} tracks, {n_kf:4d} keyframes, {n_5p:4d} 5-point poses, "
+                  f"position ({t[0]:9.3f} {t[1]:9.3f} {t[2]:9.3f})", flush=True)
+        cur = nxt
+    dt = time.perf_counter() - t0
+    V.write_trajectory(args.trajectory, ids, np.stack(poses))
+    if args.keyframes:
+        kfs = mvo.getKeyframes()
+        V.write_trajectory(args.keyframes, list(range(len(kfs))), np.stack([T for T, _ in kfs]) if kfs else np.zeros((0, 4, 4), np.float32))
+    mvo.close()
+    print(f"{n} frames in {dt:.2f} s ({n / dt:.1f} frames/s incl. image decoding); trajectory -> {args.trajectory}")
+
+
+if __name__ == "__main__":
+    main()

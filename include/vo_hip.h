@@ -625,8 +625,8 @@ int vo_mono_frame_new_points(vo_ctx *ctx, float *pts1_new, float *pts0_new, uint
  * (keyframes.cpp:47-126), and at a keyframe addNewKeyframe (:30-45), the reconstruction of landmarks seen on more than
  * two keyframes (:1032-1076) and the mono local BA (motion_estimator.cpp:1090-1205, sparse_ba_parameters.h:292-466 with
  * one observation per keyframe and at least two window keyframes per landmark; setBundled / setDead on the way back).
- * The 5-point / essential-matrix pose (MotionEstimator::calcPose5PointsAlgorithm, motion_estimator.cpp:21-203: OpenCV
- * calib3d, out of scope per SURVEY §2) is a CALLER HOOK: called at the initialisation and whenever the pose-only BA
+ * The 5-point / essential-matrix pose (MotionEstimator::calcPose5PointsAlgorithm, motion_estimator.cpp:21-203) is a HOOK
+ * (the library's own: vo_mvo_params_set_five_point + vo_five_point_*, below; or the caller's): called at the initialisation and whenever the pose-only BA
  * yields no pose (:909-949). pts0 / pts1: n pixel pairs (previous, current image); K = fx, fy, cx, cy; outputs R10
  * (row-major 3x3), t10 (any length; the driver rescales it as the reference does) and mask[n] (inliers). Return non-zero
  * on success; 0 ends the call with VO_ERR_GN_FAILED (the reference throws).
@@ -686,6 +686,85 @@ int vo_mvo_get_tracks(vo_mvo *mvo, int32_t *ids, float *pts, float *Xw, uint8_t 
 /* stats_keyframe (mono_vo.cpp:1130-1155), as vo_svo_keyframe_count / vo_svo_get_keyframes */
 int vo_mvo_keyframe_count(vo_mvo *mvo, int *n_keyframes);
 int vo_mvo_get_keyframes(vo_mvo *mvo, float *T_wc, int32_t *n_points, float *mappoints, size_t cap_points, size_t *total_points);
+
+/* ---- 5-point RANSAC pose: MotionEstimator::calcPose5PointsAlgorithm ------------------------------------------------
+ * motion_estimator.cpp:21-123 + findCorrectRT (:205-263): cv::findEssentialMat(pts0, pts1, K, RANSAC, confidence, thres_px)
+ * followed by the reference's SVD decomposition and chirality test, on the device (csrc/five_point.hip). The library's
+ * replacement for the caller hook of MonoVO (vo_mvo_params_set_five_point).
+ *
+ * One call (vo_five_point_pose), n pixel pairs pts0 (previous image) / pts1 (current), K = fx, fy, cx, cy:
+ *  1. n < 5: VO_ERR_GN_FAILED (findEssentialMat has no model there).
+ *  2. n == 5: the minimal solver once; its first solution; all five points inliers (OpenCV's count == modelPoints branch).
+ *     No solution: VO_ERR_GN_FAILED.
+ *  3. Points are normalised in double: ((u - cx) / fx, (v - cy) / fy); t = thres_px / ((fx + fy) / 2). A point is an inlier of
+ *     E when its Sampson error, in double and rounded to float, is <= (float)(t * t). The arithmetic, in this order:
+ *       a = (E0 x0 + E1 y0) + E2, b = (E3 x0 + E4 y0) + E5, c = (E6 x0 + E7 y0) + E8, d = (E0 x1 + E3 y1) + E6,
+ *       e = (E1 x1 + E4 y1) + E7, r = (x1 a + y1 b) + c, err = (float)((r r) / (((a a + b b) + d d) + e e))  (E row-major).
+ *  4. Samples s = 0 .. max_iters - 1 (all of them are evaluated, in one batch). Sample s draws indices until it has five
+ *     distinct ones, at most 256 draws; draw j (j = 0, 1, ...; repeats rejected) is, in uint64 arithmetic,
+ *       k = s * 256 + j;  z = seed + (k + 1) * 0x9E3779B97F4A7C15;
+ *       z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9;  z = (z ^ (z >> 27)) * 0x94D049BB133111EB;  z ^= z >> 31;
+ *       index = ((z >> 32) * n) >> 32
+ *     (splitmix64 of a counter). The stream depends on (seed, s, n) only: a call carries nothing over from earlier calls.
+ *  5. The minimal solver (Nister's 5-point method, in double) gives each sample at most 10 unit-Frobenius essential
+ *     matrices: the null space of the 5x9 epipolar system, the ten cubic constraints det E = 0 and 2 EE^T E - tr(EE^T) E = 0,
+ *     Gauss-Jordan, the hidden-variable 3x3 in z, the real roots of its degree-10 determinant (derivative-separated
+ *     bisection on [-1, 1] for z and for 1/z, so ascending z in [-1, 1] first, then ascending 1/z), back substitution. A
+ *     root whose E leaves a constraint residual above 1e-8 is dropped.
+ *  6. Selection is OpenCV's sequential rule over that stream: samples in order, models in solver order; a model becomes
+ *     the best when its inlier count is > max(best, 4); after each replacement niters = RANSACUpdateNumIters(p, (n -
+ *     best) / n, 5, niters) with p = (double)confidence: d = 1 - (1 - ep)^5 (as ((q q)(q q)) q), d < DBL_MIN -> 0;
+ *     num = log(max(1 - p, DBL_MIN)), den = log(d); niters if den >= 0 or -num >= niters (-den), else rint(num / den).
+ *     The walk stops once s + 1 >= niters. The result does not depend on how the work is batched or launched.
+ *  7. The best E is rounded to float (cv::cv2eigen into Mat33): E10. mask_5p = its inliers (3.), all five for n == 5.
+ *  8. motion_estimator.cpp:64-127: Eigen's JacobiSVD of E10 in f32 (full U, V; restated as svo_svd4_nullvec restates the
+ *     4x4), the last column of U / V negated where its determinant is negative, R = U W V^T, U W^T V^T, t = +-U.col(2) in
+ *     the reference's order, mapping::triangulateDLT of EVERY point under each, the first candidate with a strictly larger
+ *     count of points with both depths > 0 wins. mask = chirality AND mask_5p. Success even when fewer than half the points
+ *     pass (findCorrectRT only warns); when no point passes under any candidate, VO_ERR_GN_FAILED (the reference's (R, t)
+ *     would be uninitialised).
+ *  9. Out: R10 (row-major), t10 (unit length), mask[n], info (may be NULL).
+ * Bit parity with OpenCV is not the goal and cannot be had: OpenCV's random stream and its polynomial solver are its own.
+ * Everything from 7. on is the reference's arithmetic.
+ *
+ * The solver owns its device workspace and pinned staging, sized at creation from max_points (<= 0: the context's) and
+ * max_iters (1 .. 4096) through the context's counted allocations; a call allocates nothing. A call runs on the context's
+ * main stream (one upload, three launches, one download) and waits for that stream only. It does not read the context's
+ * summation order (its sums are integer counts or per-lane sequential arithmetic). Destroy it before its context. */
+typedef struct {
+  float thres_px;       /* motion_estimator.thres_5p_error (pixels) */
+  float confidence;     /* 0.999 in the reference */
+  int max_iters;        /* OpenCV's default 1000 */
+  unsigned long long seed;
+} vo_five_point_params;
+typedef struct {
+  float E10[9];         /* the selected essential matrix as the decomposition used it (float, row-major) */
+  int n_inliers_5p;     /* |mask_5p| */
+  int n_inliers;        /* |mask| = |mask_5p AND chirality| */
+  int iterations;       /* samples walked: the stop index */
+  int models;           /* models of those samples */
+  int best_sample;      /* sample of the selected model (-1: none) */
+} vo_five_point_info;
+typedef struct vo_five_point vo_five_point;
+int vo_five_point_create(vo_ctx *ctx, const vo_five_point_params *prm, int max_points, vo_five_point **out);
+void vo_five_point_destroy(vo_five_point *fp);
+/* VO_OK, VO_ERR_GN_FAILED where the reference has no pose (see above), VO_ERR_CAPACITY for n > max_points */
+int vo_five_point_pose(vo_five_point *fp, const float *pts0, const float *pts1, int n, const float K[4], float R10[9],
+                       float t10[3], uint8_t *mask, vo_five_point_info *info);
+/* fills prm->five_point / five_point_user with the library's own hook bound to fp (no host callback on that path); fp must
+ * outlive the vo_mvo created from prm */
+int vo_mvo_params_set_five_point(vo_mvo_params *prm, vo_five_point *fp);
+/* test hooks. minimal: n_sets sets of five NORMALISED pairs (x0, x1: n_sets x 5 x 2 doubles) through the minimal solver:
+ * E[s * 90 + m * 9 + k] for m < n_sol[s]. samples: of the last vo_five_point_pose call (0 samples for n == 5, or after
+ * vo_five_point_minimal): the five indices of every sample (-1 where it was given up), its number of models and its largest
+ * inlier count (-1: no model); all three may be NULL to ask for *n_samples only; VO_ERR_CAPACITY when cap is too small. */
+int vo_five_point_minimal(vo_five_point *fp, const double *x0, const double *x1, int n_sets, double *E, int *n_sol);
+int vo_five_point_samples(const vo_five_point *fp, int32_t *subsets, int32_t *n_models, int32_t *best_count, int cap,
+                          int *n_samples);
+/* test hook: the inlier count of every model of every sample of the last vo_five_point_pose call, counts[s * 10 + m] in
+ * solver order, -1 past the sample's models (so that the sequential rule can be walked model by model); NULL counts asks for
+ * *n_samples only; VO_ERR_CAPACITY when cap (in samples) is too small */
+int vo_five_point_counts(const vo_five_point *fp, int32_t *counts, int cap, int *n_samples);
 
 /* ---- sparse local bundle adjustment -----------------------------------------
  * SparseBundleAdjustmentSolver::solveForFiniteIterations

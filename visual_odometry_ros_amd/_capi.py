@@ -102,6 +102,15 @@ class MvoFrameInfo(C.Structure):
                 ("lba_err_last", C.c_double), ("lba_landmarks", C.c_int), ("lba_observations", C.c_int)]
 
 
+class FivePointParams(C.Structure):
+    _fields_ = [("thres_px", C.c_float), ("confidence", C.c_float), ("max_iters", C.c_int), ("seed", C.c_ulonglong)]
+
+
+class FivePointInfo(C.Structure):
+    _fields_ = [("E10", C.c_float * 9), ("n_inliers_5p", C.c_int), ("n_inliers", C.c_int), ("iterations", C.c_int),
+                ("models", C.c_int), ("best_sample", C.c_int)]
+
+
 # every symbol include/vo_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
     "vo_abi_version", "vo_device_count", "vo_create", "vo_destroy", "vo_last_error", "vo_stream",
@@ -127,6 +136,8 @@ SYMBOLS = [
     "vo_batch_last_error", "vo_batch_run", "vo_debug_set", "vo_batch_debug_set", "vo_batch_strict_border", "vo_debug_allocation_count", "vo_svo_device_bytes",
     "vo_se3_exp", "vo_ids_reset", "vo_ids_peek", "vo_ids_new_frames", "vo_ids_new_landmarks", "vo_compact_tracks",
     "vo_set_sum_order", "vo_get_sum_order",
+    "vo_five_point_create", "vo_five_point_destroy", "vo_five_point_pose", "vo_mvo_params_set_five_point",
+    "vo_five_point_minimal", "vo_five_point_samples", "vo_five_point_counts",
 ]
 
 _lib = None
@@ -195,6 +206,14 @@ def load():
     lib.vo_debug_allocation_count.argtypes = [vp, vp]
     lib.vo_set_sum_order.argtypes = [vp, ci]
     lib.vo_get_sum_order.argtypes = [vp]
+    lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
+    lib.vo_five_point_destroy.argtypes = [vp]
+    lib.vo_five_point_destroy.restype = None
+    lib.vo_five_point_pose.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, C.POINTER(FivePointInfo)]
+    lib.vo_mvo_params_set_five_point.argtypes = [C.POINTER(MvoParams), vp]
+    lib.vo_five_point_minimal.argtypes = [vp, vp, vp, ci, vp, vp]
+    lib.vo_five_point_samples.argtypes = [vp, vp, vp, vp, ci, vp]
+    lib.vo_five_point_counts.argtypes = [vp, vp, ci, vp]
     lib.vo_triangulate_dlt.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp]
     lib.vo_batch_create.argtypes = [C.POINTER(VoConfig), C.POINTER(SvoParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_batch_destroy.argtypes = [vp]

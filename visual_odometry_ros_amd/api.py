@@ -16,7 +16,7 @@ import weakref
 import numpy as np
 
 from . import _capi
-from ._capi import (FIVE_POINT_FN, BinParams, FrameCounts, GnInfo, MonoCounts, MonoParams, MvoFrameInfo, MvoParams, OrbParams,
+from ._capi import (FIVE_POINT_FN, BinParams, FivePointInfo, FivePointParams, FrameCounts, GnInfo, MonoCounts, MonoParams, MvoFrameInfo, MvoParams, OrbParams,
                     SbaProblem, StereoParams, SvoFrameInfo, SvoParams, VoConfig, VoError)
 
 KLT_USE_INITIAL_FLOW = 4
@@ -327,6 +327,8 @@ class MotionEstimator:
         self.lib = ctx.lib
         self.is_stereo_mode_ = bool(is_stereo_mode)
         self.T_left2right_ = np.eye(4, dtype=np.float32) if T_left2right is None else _f32(T_left2right)
+        self.thres_1p_, self.thres_5p_ = 10.0, 1.5  # motion_estimator.cpp:6-7
+        self._five_point = None
 
     def poseOnlyBundleAdjustment(self, X, pts1, K, thres_reproj_outlier, R01, t01, variant=GN_CORE):
         X, pts1 = _f32(X).reshape(-1, 3), _f32(pts1).reshape(-1, 2)
@@ -366,6 +368,18 @@ class MotionEstimator:
 
     def setThres5p(self, thres_5p):  # :660-663
         self.thres_5p_ = float(thres_5p)
+
+    def calcPose5PointsAlgorithm(self, pts0, pts1, K):
+        """motion_estimator.cpp:21-123: the essential-matrix pose of pts0 -> pts1 with the RANSAC threshold thres_5p_ (pixels),
+        on the device (FivePointRansac). Returns (ok, R10, t10 (unit length), mask); ok is False where the reference has no
+        pose (fewer than 5 pairs, no model). X0_true of the reference is not returned."""
+        fp = self._five_point
+        if fp is None or fp.thres_px != np.float32(self.thres_5p_):
+            if fp is not None:
+                fp.close()
+            fp = self._five_point = FivePointRansac(self.ctx, K, thres_px=self.thres_5p_)
+        ok, R, t, mask, _ = fp.estimate(pts0, pts1, K)
+        return ok, R, t, mask
 
     # ---- epipolar gates (motion_estimator.cpp:538-653) ----
     @staticmethod
@@ -1305,17 +1319,100 @@ class SparseBundleAdjustmentSolver:
         return bool(rc), T.reshape(-1, 4, 4), Xo, err[: int(MAX_ITER)]
 
 
+class FivePointRansac:
+    """MotionEstimator::calcPose5PointsAlgorithm (motion_estimator.cpp:21-123): cv::findEssentialMat(..., RANSAC, confidence,
+    thres_px) + the reference's SVD decomposition and chirality test, on the device (include/vo_hip.h: vo_five_point_*).
+    `solver(pts0, pts1) -> (ok, R10, t10, mask)` is the hook shape MonoVO takes; a MonoVO given this object calls it natively.
+    A child of the context: closed with it at the latest. The workspace is sized here (max_points: the context's by default,
+    max_iters) and no call allocates."""
+
+    def __init__(self, ctx, K, thres_px=2.0, confidence=0.999, max_iters=1000, seed=0, max_points=None):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.K = _f32(K).reshape(4).copy()
+        self.prm = FivePointParams(float(thres_px), float(confidence), int(max_iters), int(seed))
+        self.thres_px = np.float32(thres_px)
+        self.max_points = int(ctx.cfg.max_points if max_points is None else max_points)
+        self._h = C.c_void_p()
+        ctx.check(self.lib.vo_five_point_create(ctx.handle, C.byref(self.prm), self.max_points, C.byref(self._h)))
+        ctx._children.add(self)
+
+    @property
+    def handle(self):
+        return self._h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self.lib.vo_five_point_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def estimate(self, pts0, pts1, K=None):
+        """(ok, R10 3x3, t10 (unit), mask (bool, n), info): info = vo_five_point_info (E10, n_inliers_5p, n_inliers, iterations,
+        models, best_sample). ok is False where the reference has no pose; other errors raise VoError."""
+        p0, p1 = _f32(pts0).reshape(-1, 2), _f32(pts1).reshape(-1, 2)
+        if p0.shape[0] != p1.shape[0]:  # motion_estimator.cpp:27-28
+            raise VoError(-4, "calcPose5PointsAlgorithm(): pts0.size() != pts1.size()")
+        n = p0.shape[0]
+        Kc = self.K if K is None else _f32(K).reshape(4)
+        R, t = np.zeros(9, np.float32), np.zeros(3, np.float32)
+        mask = np.zeros(max(n, 1), np.uint8)
+        info = FivePointInfo()
+        rc = self.lib.vo_five_point_pose(self._h, p0.ctypes.data, p1.ctypes.data, n, Kc.ctypes.data, R.ctypes.data, t.ctypes.data,
+                                         mask.ctypes.data, C.byref(info))
+        if rc == -9:  # VO_ERR_GN_FAILED: no pose
+            return False, R.reshape(3, 3), t, np.zeros(n, bool), info
+        self.ctx.check(rc)
+        return True, R.reshape(3, 3), t, mask[:n].astype(bool), info
+
+    def __call__(self, pts0, pts1):
+        ok, R, t, mask, _ = self.estimate(pts0, pts1)
+        return ok, R, t, mask
+
+    def minimal(self, x0, x1):
+        """The minimal solver alone (test hook): sets of five NORMALISED pairs (n_sets x 5 x 2 each) -> (E n_sets x 10 x 3 x 3,
+        n_sol n_sets)."""
+        x0 = np.ascontiguousarray(x0, np.float64).reshape(-1, 5, 2)
+        x1 = np.ascontiguousarray(x1, np.float64).reshape(-1, 5, 2)
+        m = x0.shape[0]
+        E = np.zeros((max(m, 1), 10, 3, 3), np.float64)
+        ns = np.zeros(max(m, 1), np.int32)
+        self.ctx.check(self.lib.vo_five_point_minimal(self._h, x0.ctypes.data, x1.ctypes.data, m, E.ctypes.data, ns.ctypes.data))
+        return E[:m], ns[:m]
+
+    def samples(self):
+        """Of the last call (test hook): dict(subsets (S x 5), n_models (S), best_count (S), counts (S x 10: every model's
+        inlier count in solver order, -1 past the sample's models))."""
+        S = C.c_int()
+        self.ctx.check(self.lib.vo_five_point_samples(self._h, None, None, None, 0, C.addressof(S)))
+        k = S.value
+        sub, nm, bc = np.zeros((max(k, 1), 5), np.int32), np.zeros(max(k, 1), np.int32), np.zeros(max(k, 1), np.int32)
+        cnt = np.full((max(k, 1), 10), -1, np.int32)
+        if k:
+            self.ctx.check(self.lib.vo_five_point_samples(self._h, sub.ctypes.data, nm.ctypes.data, bc.ctypes.data, k, C.addressof(S)))
+            self.ctx.check(self.lib.vo_five_point_counts(self._h, cnt.ctypes.data, k, C.addressof(S)))
+        return dict(subsets=sub[:k], n_models=nm[:k], best_count=bc[:k], counts=cnt[:k])
+
+
 class MonoVO:
     """MonoVO (core/visual_odometry/mono_vo/mono_vo.h:235-243, :267): trackImage(img, timestamp) / getStatistics(), the track
-    set, the keyframes and the mono local BA carried on the device (vo_mvo_*). `five_point(pts0, pts1) -> (ok, R10, t10,
-    mask)` stands for MotionEstimator::calcPose5PointsAlgorithm (OpenCV calib3d: the caller's; called for the second image
-    and whenever the pose-only BA yields no pose)."""
+    set, the keyframes and the mono local BA carried on the device (vo_mvo_*). `five_point` is MotionEstimator::
+    calcPose5PointsAlgorithm, called for the second image and whenever the pose-only BA yields no pose: None (the default)
+    builds the library's FivePointRansac(ctx, K, thres_px=thres_5p_error); a FivePointRansac is wired natively (no Python
+    callback; this object keeps it alive); any other callable `(pts0, pts1) -> (ok, R10, t10, mask)` is called back."""
 
-    def __init__(self, ctx, width, height, K, n_bins_u, n_bins_v, five_point, thres_fastscore=15, window_size=15, max_level=5,
+    def __init__(self, ctx, width, height, K, n_bins_u, n_bins_v, five_point=None, thres_fastscore=15, window_size=15, max_level=5,
                  thres_error=20.0, thres_bidirection=1.0, thres_poseba_error=5, thres_sampson=1.0, thres_parallax=1.0,
                  thres_overlap_ratio=0.7, thres_rotation=3.0, thres_translation=3.0, n_max_keyframes_in_window=9, strict_border=4,
-                 local_ba=True, rectify=False):
+                 local_ba=True, rectify=False, thres_5p_error=2.0):
         self.ctx, self.lib = ctx, ctx.lib
+        self._own_fp = None
+        if five_point is None:
+            five_point = self._own_fp = FivePointRansac(ctx, K, thres_px=thres_5p_error)
         fe = FeatureExtractor(ctx)
         fe.initParams(width, height, n_bins_u, n_bins_v, THRES_FAST=thres_fastscore)
         p = MvoParams()
@@ -1342,20 +1439,80 @@ class MonoVO:
                 np.ctypeslib.as_array(mask, shape=(n,))[:] = np.asarray(m, bool).astype(np.uint8)
             return 1
 
-        self._cb = FIVE_POINT_FN(_hook)  # (kept alive with the object)
-        p.five_point = self._cb
-        p.five_point_user = None
+        if isinstance(five_point, FivePointRansac):
+            self._cb = None
+            ctx.check(self.lib.vo_mvo_params_set_five_point(C.byref(p), five_point.handle))
+        else:
+            self._cb = FIVE_POINT_FN(_hook)  # (kept alive with the object)
+            p.five_point = self._cb
+            p.five_point_user = None
         self.prm, self.width, self.height = p, width, height
         self._h = C.c_void_p()
-        ctx.check(self.lib.vo_mvo_create(ctx.handle, C.byref(p), C.byref(self._h)))
+        try:
+            ctx.check(self.lib.vo_mvo_create(ctx.handle, C.byref(p), C.byref(self._h)))
+        except Exception:
+            if self._own_fp is not None:
+                self._own_fp.close()
+            raise
         ctx._children.add(self)
         self._info = MvoFrameInfo()
         self.stats_frame = []
+
+    @classmethod
+    def from_yaml(cls, path, device=0, max_points=None, **overrides):
+        """MonoVO(mode = "rosbag", directory_intrinsic = path) of the reference (mono_vo.cpp:15-60, :137-225): the object
+        configured by one of its config/mono/*.yaml files, with the library's 5-point solver at motion_estimator.
+        thres_5p_error. The context is created here (sized by the file) and closed with the object. With flagDoUndistortion
+        the images go through the camera's undistortion map (mono_vo.cpp:509-513). `overrides`: keyword arguments of the
+        constructor (five_point, strict_border, local_ba, ...). `max_points`: capacity of a track set (default 2 * bins +
+        1024, as StereoVO.from_yaml)."""
+        from . import config as _config
+        cfg = _config.load_mono_config(path)
+        cam = cfg["camera"]
+        W, H = cam["width"], cam["height"]
+        fe, ft, me, ku = cfg["feature_extractor"], cfg["feature_tracker"], cfg["motion_estimator"], cfg["keyframe_update"]
+        cap = int(max_points) if max_points else 2 * fe["n_bins_u"] * fe["n_bins_v"] + 1024
+        ctx = Context(device=device, max_width=W, max_height=H, max_points=cap, n_slots=3, max_level=max(ft["max_level"], 1))
+        try:
+            if cfg["flagDoUndistortion"]:
+                Camera(ctx, 0).initParams(W, H, cam["K"], cam["D"])
+            # (keys the file does not have keep the constructor's defaults: a 0 there is refused or meaningless — mono0.yaml
+            # has no motion_estimator.* and no keyframe window)
+            names = {"feature_extractor.thres_fastscore": ("thres_fastscore", fe["thres_fastscore"]),
+                     "feature_tracker.window_size": ("window_size", ft["window_size"]),
+                     "feature_tracker.max_level": ("max_level", ft["max_level"]),
+                     "feature_tracker.thres_error": ("thres_error", ft["thres_error"]),
+                     "feature_tracker.thres_bidirection": ("thres_bidirection", ft["thres_bidirection"]),
+                     "feature_tracker.thres_sampson": ("thres_sampson", ft["thres_sampson"]),
+                     "motion_estimator.thres_poseba_error": ("thres_poseba_error", int(me["thres_poseba_error"])),
+                     "motion_estimator.thres_5p_error": ("thres_5p_error", me["thres_5p_error"]),
+                     "map_update.thres_parallax": ("thres_parallax", cfg["map_update"]["thres_parallax"]),
+                     "keyframe_update.thres_overlap_ratio": ("thres_overlap_ratio", ku["thres_overlap_ratio"]),
+                     "keyframe_update.thres_rotation": ("thres_rotation", ku["thres_rotation"]),
+                     "keyframe_update.thres_translation": ("thres_translation", ku["thres_translation"]),
+                     "keyframe_update.n_max_keyframes_in_window": ("n_max_keyframes_in_window", ku["n_max_keyframes_in_window"])}
+            kw = {arg: v for key, (arg, v) in names.items() if key not in cfg["missing"]}
+            kw["rectify"] = bool(cfg["flagDoUndistortion"])
+            kw.update(overrides)
+            obj = cls(ctx, W, H, cam["K"], fe["n_bins_u"], fe["n_bins_v"], **kw)
+        except Exception:
+            ctx.close()
+            raise
+        obj._own_ctx, obj.config = ctx, cfg
+        return obj
 
     def close(self):
         if getattr(self, "_h", None):
             self.lib.vo_mvo_destroy(self._h)
             self._h = C.c_void_p()
+        fp = getattr(self, "_own_fp", None)
+        if fp is not None:
+            self._own_fp = None
+            fp.close()
+        own = getattr(self, "_own_ctx", None)
+        if own is not None:
+            self._own_ctx = None
+            own.close()
 
     def __del__(self):
         try:

@@ -75,3 +75,38 @@ def load_stereo_config(path_or_text):
                              thres_trans=_num(d, "keyframe_update.thres_trans"), thres_rotation=_num(d, "keyframe_update.thres_rotation"),
                              n_max_keyframes_in_window=_num(d, "keyframe_update.n_max_keyframes_in_window", int)),
     )
+
+
+def load_mono_config(path_or_text):
+    """The numbers of a config/mono/*.yaml file as MonoVO::loadCameraIntrinsicAndUserParameters reads them
+    (mono_vo.cpp:137-225), named as MonoVO::AlgorithmParameters names them (mono_vo.h:57-110); the camera as (fx, fy, cx, cy)
+    + (k1, k2, p1, p2, k3), the order fed to OpenCV (:160-166). map_update.thres_parallax stays in DEGREES (the reference
+    multiplies it by D2R; MonoVO takes degrees). A missing key reads as 0, as in load_stereo_config; `missing` lists them."""
+    d = load_yaml(path_or_text)
+    keys = ["flagDoUndistortion"] + ["Camera." + k for k in ("fx", "fy", "cx", "cy", "k1", "k2", "p1", "p2", "k3", "width", "height")]
+    keys += ["feature_tracker." + k for k in ("thres_error", "thres_bidirection", "thres_sampson", "window_size", "max_level")]
+    keys += ["feature_extractor." + k for k in ("n_features", "n_bins_u", "n_bins_v", "thres_fastscore", "radius")]
+    keys += ["motion_estimator." + k for k in ("thres_1p_error", "thres_5p_error", "thres_poseba_error")]
+    keys += ["keyframe_update." + k for k in ("thres_translation", "thres_rotation", "thres_overlap_ratio", "n_max_keyframes_in_window")]
+    keys += ["map_update.thres_parallax"]
+    return dict(
+        missing=[k for k in keys if k not in d],
+        flagDoUndistortion=_num(d, "flagDoUndistortion", int),
+        camera=dict(K=np.array([_num(d, "Camera.fx"), _num(d, "Camera.fy"), _num(d, "Camera.cx"), _num(d, "Camera.cy")], np.float32),
+                    D=np.array([_num(d, "Camera.k1"), _num(d, "Camera.k2"), _num(d, "Camera.p1"), _num(d, "Camera.p2"),
+                                _num(d, "Camera.k3")], np.float32),
+                    width=_num(d, "Camera.width", int), height=_num(d, "Camera.height", int)),
+        feature_tracker=dict(thres_error=_num(d, "feature_tracker.thres_error"), thres_bidirection=_num(d, "feature_tracker.thres_bidirection"),
+                             thres_sampson=_num(d, "feature_tracker.thres_sampson"), window_size=_num(d, "feature_tracker.window_size", int),
+                             max_level=_num(d, "feature_tracker.max_level", int)),
+        feature_extractor=dict(n_features=_num(d, "feature_extractor.n_features", int), n_bins_u=_num(d, "feature_extractor.n_bins_u", int),
+                               n_bins_v=_num(d, "feature_extractor.n_bins_v", int), thres_fastscore=_num(d, "feature_extractor.thres_fastscore"),
+                               radius=_num(d, "feature_extractor.radius")),
+        motion_estimator=dict(thres_1p_error=_num(d, "motion_estimator.thres_1p_error"), thres_5p_error=_num(d, "motion_estimator.thres_5p_error"),
+                              thres_poseba_error=_num(d, "motion_estimator.thres_poseba_error")),
+        keyframe_update=dict(thres_translation=_num(d, "keyframe_update.thres_translation"),
+                             thres_rotation=_num(d, "keyframe_update.thres_rotation"),
+                             thres_overlap_ratio=_num(d, "keyframe_update.thres_overlap_ratio"),
+                             n_max_keyframes_in_window=_num(d, "keyframe_update.n_max_keyframes_in_window", int)),
+        map_update=dict(thres_parallax=_num(d, "map_update.thres_parallax")),
+    )

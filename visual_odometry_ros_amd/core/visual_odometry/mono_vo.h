@@ -3,9 +3,9 @@
 // Same public surface as the reference's class: trackImage(img, timestamp), getStatistics(); the statistics structs carry
 // the reference's field names. What trackImage does — the track set carried from frame to frame with every landmark's
 // first observation, age and parallax, the initialisation, new landmarks, keyframes, reconstruction, the mono local bundle
-// adjustment — runs inside libvo_hip.so with the track set on the device (csrc/mono_vo.hip). One piece stays with the
-// caller: MotionEstimator::calcPose5PointsAlgorithm (motion_estimator.cpp:21-203, OpenCV calib3d — out of scope per
-// SURVEY §2), handed over as `five_point`; it is called for the second image and whenever the pose-only BA gives no pose.
+// adjustment — runs inside libvo_hip.so with the track set on the device (csrc/mono_vo.hip). MotionEstimator::
+// calcPose5PointsAlgorithm (motion_estimator.cpp:21-203), called for the second image and whenever the pose-only BA gives no
+// pose, is either the library's (MonoVO(ctx, params): vo::FivePointRansac, csrc/five_point.hip) or a caller's `five_point`.
 #ifndef VO_AMD_MONO_VO_H_
 #define VO_AMD_MONO_VO_H_
 
@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -53,6 +54,43 @@ struct MonoVOParams {
   bool keyframe_statistics = false;  // stats_keyframe rewritten at every keyframe (RECORD_KEYFRAME_STAT, mono_vo.cpp:1130-1155)
 };
 
+// MotionEstimator::calcPose5PointsAlgorithm (motion_estimator.cpp:21-123) on the device: RAII over vo_five_point
+// (include/vo_hip.h). Callable as MonoVO::FivePoint; MonoVO(ctx, params) binds it natively (no std::function on that path).
+class FivePointRansac {
+ public:
+  FivePointRansac(ContextPtr ctx, float thres_px, float confidence = 0.999f, int max_iters = 1000, unsigned long long seed = 0,
+                  int max_points = 0)
+      : ctx_(std::move(ctx)) {
+    vo_five_point_params q;
+    q.thres_px = thres_px;
+    q.confidence = confidence;
+    q.max_iters = max_iters;
+    q.seed = seed;
+    ctx_->check(vo_five_point_create(ctx_->get(), &q, max_points, &fp_));
+  }
+  ~FivePointRansac() {
+    if (fp_) vo_five_point_destroy(fp_);
+  }
+  FivePointRansac(const FivePointRansac &) = delete;
+  FivePointRansac &operator=(const FivePointRansac &) = delete;
+  // false where the reference has no pose (fewer than 5 pairs, no model); other errors throw
+  bool operator()(const PixelVec &pts0, const PixelVec &pts1, const float K[4], float R10[9], float t10[3],
+                  std::vector<std::uint8_t> &mask, vo_five_point_info *info = nullptr) const {
+    if (pts0.size() != pts1.size()) throw std::runtime_error("calcPose5PointsAlgorithm(): pts0.size() != pts1.size()");
+    mask.assign(pts0.size(), 0);
+    const int rc = vo_five_point_pose(fp_, reinterpret_cast<const float *>(pts0.data()), reinterpret_cast<const float *>(pts1.data()),
+                                      (int)pts0.size(), K, R10, t10, mask.data(), info);
+    if (rc == VO_ERR_GN_FAILED) return false;
+    ctx_->check(rc);
+    return true;
+  }
+  vo_five_point *get() const { return fp_; }
+
+ private:
+  ContextPtr ctx_;
+  vo_five_point *fp_ = nullptr;
+};
+
 class MonoVO {
  public:
   // calcPose5PointsAlgorithm(pts0, pts1, cam, R10, t10, X0, mask): true on success
@@ -84,6 +122,26 @@ class MonoVO {
 
   MonoVO(ContextPtr ctx, const MonoVOParams &p, FivePoint five_point) : ctx_(std::move(ctx)), prm_(p), hook_(std::move(five_point)) {
     if (!hook_) throw std::runtime_error("MonoVO: the 5-point pose hook is missing");
+    vo_mvo_params q = make_params(p);
+    q.five_point = &MonoVO::trampoline;
+    q.five_point_user = this;
+    ctx_->check(vo_mvo_create(ctx_->get(), &q, &mvo_));
+  }
+  // The library's own 5-point solver (vo::FivePointRansac at p.motion_estimator.thres_5p_error), bound natively
+  MonoVO(ContextPtr ctx, const MonoVOParams &p) : ctx_(std::move(ctx)), prm_(p) {
+    fp_.reset(new FivePointRansac(ctx_, p.motion_estimator.thres_5p_error));
+    vo_mvo_params q = make_params(p);
+    ctx_->check(vo_mvo_params_set_five_point(&q, fp_->get()));
+    ctx_->check(vo_mvo_create(ctx_->get(), &q, &mvo_));
+  }
+  ~MonoVO() {
+    if (mvo_) vo_mvo_destroy(mvo_);
+  }
+  MonoVO(const MonoVO &) = delete;
+  MonoVO &operator=(const MonoVO &) = delete;
+
+ private:
+  vo_mvo_params make_params(const MonoVOParams &p) {
     vo_mvo_params q;
     std::memset(&q, 0, sizeof(q));
     q.frame.width = p.width;
@@ -117,15 +175,10 @@ class MonoVO {
     q.thres_parallax_deg = p.map_update.thres_parallax;
     q.strict_border = p.strict_border;
     q.local_ba = p.local_ba ? 1 : 0;
-    q.five_point = &MonoVO::trampoline;
-    q.five_point_user = this;
-    ctx_->check(vo_mvo_create(ctx_->get(), &q, &mvo_));
+    return q;
   }
-  ~MonoVO() {
-    if (mvo_) vo_mvo_destroy(mvo_);
-  }
-  MonoVO(const MonoVO &) = delete;
-  MonoVO &operator=(const MonoVO &) = delete;
+
+ public:
 
   // MonoVO::trackImage (mono_vo.cpp:496-1194). Throws std::runtime_error where the reference throws.
   void trackImage(const Image &img, const double &timestamp) {
@@ -224,6 +277,7 @@ class MonoVO {
   ContextPtr ctx_;
   MonoVOParams prm_;
   FivePoint hook_;
+  std::unique_ptr<FivePointRansac> fp_;  // (declared before mvo_'s destruction in ~MonoVO: destroyed after it)
   vo_mvo *mvo_ = nullptr;
   AlgorithmStatistics stat_;
   vo_mvo_frame_info last_{};
