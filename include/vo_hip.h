@@ -221,7 +221,8 @@ int vo_bucket_argmax(vo_ctx *ctx, const float *kp_xy, const float *kp_response, 
  * with non-max suppression, runByImageBorder, retainBest on the FAST score, HarrisResponses, retainBest on the
  * Harris response, pt *= scale — is restated (oracle/oracle_orb.c says what could not be verified here).
  * Keypoints come back as level-0 pixel coordinates, Harris response and octave, ordered by level and then
- * raster order (cv's own order is unspecified). Orientation is not computed (the reference does not read it). */
+ * raster order (cv's own order is unspecified). Orientation and descriptors: vo_orb_compute / vo_orb_detect_and_compute
+ * below. */
 typedef struct {
   int nfeatures;        /* setMaxFeatures(10000), feature_extractor.cpp:48 */
   double scale_factor;  /* 1.2 */
@@ -253,6 +254,63 @@ int vo_orb_hamming(vo_ctx *ctx, const uint8_t *a, int na, const uint8_t *b, int 
 /* nearest / second-nearest + the test/test_orbmatching.cpp:87-137 accept rule */
 int vo_orb_match(vo_ctx *ctx, const uint8_t *a, int na, const uint8_t *b, int nb, int th_low,
                  float ratio, int32_t *best_idx, uint16_t *best_dist, uint16_t *second_dist);
+
+/* ---- ORB orientation and descriptors: FeatureExtractor::extractAndComputeORB ----------------------------------------
+ * feature_extractor.cpp:321-332: extractor_orb_->detectAndCompute(...) with the settings of initParams (:49-57: WTA_K 2,
+ * patch 31, Harris score). cv::ORB::compute is OpenCV (not in the reference tree): restated here as far as it is known to
+ * the author (orb.cpp ICAngles / computeOrbDescriptors, fastAtan2), unpinned like the detector; what is this library's own
+ * choice is marked (own). Everything is integer arithmetic or individually rounded float operations (no fused
+ * multiply-add), so a restatement written from this text reproduces the bits (csrc/orb_describe.hpp is the device text).
+ *
+ * For one keypoint (x, y, octave) — level-0 pixels and octave as vo_orb_detect returns them — on the ORB pyramid of the
+ * image in `slot` (the detector's levels: vo_orb_get_level), with edge = vo_orb_params.edge_threshold:
+ *  1. Level and centre. s = the float scale of the level ((float)pow(scale_factor, octave)); inv = 1.f / s;
+ *     xf = rint(x * inv), yf = rint(y * inv) (float product, round half to even). The keypoint is VALID when
+ *     0 <= octave < n_levels and edge <= xf < w - edge and edge <= yf < h - edge (float compares; w x h = the level's size).
+ *     An invalid keypoint gets valid = 0, angle = 0 and 32 zero bytes (own: OpenCV drops it; the detector returns none).
+ *     cx = (int)xf, cy = (int)yf. A pixel outside the level is BORDER_REFLECT_101 of the level, iterated
+ *     (p < 0 -> -p, p >= n -> 2n - 2 - p, until inside).
+ *  2. Orientation (ICAngles) on the unblurred level: m10 = sum u I(cx + u, cy + v), m01 = sum v I(cx + u, cy + v) over
+ *     v = -15 .. 15, |u| <= umax[|v|], umax = 15 15 15 15 14 14 14 13 13 12 11 10 9 8 6 3 (integers: any order).
+ *     angle = fastAtan2((float)m01, (float)m10), degrees in [0, 360), in float: K = (float)(180 / pi);
+ *     p1 = 0.9997878412794807f * K, p3 = -0.3258083974640975f * K, p5 = 0.1555786518463281f * K,
+ *     p7 = -0.04432655554792128f * K (each a float product); ax = |x|, ay = |y|, eps = (float)DBL_EPSILON;
+ *     ax >= ay: c = ay / (ax + eps), c2 = c * c, a = (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+ *     else:     c = ax / (ay + eps), c2 = c * c, a = 90.f - (((p7 * c2 + p5) * c2 + p3) * c2 + p1) * c;
+ *     x < 0: a = 180.f - a; then y < 0: a = 360.f - a.   steer = 0: the moments are skipped and angle = 0 (plain BRIEF).
+ *  3. Smoothing: GaussianBlur(7 x 7, sigma 2, BORDER_REFLECT_101) in fixed point with the 8-bit kernel
+ *     k = 18 34 49 54 49 34 18 (sum 256): B(q) = (sum_ij k_i k_j I(q + (i - 3, j - 3)) + 2^15) >> 16, for any position q,
+ *     also outside the level, I being the reflected level of 1. (own where a sample leaves the level: OpenCV blurs the level
+ *     only; with the reference's edge threshold 31 no sample does).
+ *  4. Steered BRIEF, WTA_K 2: r = (double)(angle * (float)(pi / 180)); a = (float)cos(r), b = (float)sin(r) (double
+ *     functions, rounded once). Pattern point (px, py): ix = rint(px * a - py * b), iy = rint(px * b + py * a) (float products,
+ *     one float subtraction / addition). Bit j of byte i = B(c + rot(pattern[16 i + 2 j])) < B(c + rot(pattern[16 i + 2 j + 1])).
+ *  5. Pattern: 512 points x (x, y), int8 in [-15, 15], pattern[2 p] = x, pattern[2 p + 1] = y of point p. OpenCV's learned
+ *     table (bit_pattern_31_) is not reproduced (own). The default, vo_orb_default_pattern: entry k = 0 .. 1023 from the
+ *     splitmix64 stream of the 5-point sampler (below), z = 0x4F52423331 + (k + 1) * 0x9E3779B97F4A7C15, the same three
+ *     mixing lines, value = (int)(((z >> 32) * 31) >> 32) - 15. vo_orb_set_pattern replaces the table of a context (an
+ *     integrator with OpenCV loads bit_pattern_31_ and gets that table's descriptors). Descriptors are comparable only
+ *     between sets made with the same table and the same `steer`.
+ * On an upright stereo pair steering costs recall (fewer accepted matches at equal precision): `steer` is the caller's choice.
+ *
+ * All calls run on the context's main stream and allocate only when a capacity grows. */
+int vo_orb_default_pattern(int8_t pattern[1024]);
+int vo_orb_get_pattern(vo_ctx *ctx, int8_t pattern[1024]);
+/* VO_ERR_INVALID (nothing changes) when a coordinate is outside [-15, 15] */
+int vo_orb_set_pattern(vo_ctx *ctx, const int8_t pattern[1024]);
+/* descriptors of the caller's n keypoints on the image in `slot` (builds the slot's ORB pyramid). angle_out[n],
+ * desc_out[32 n], valid_out[n]; each may be NULL. */
+int vo_orb_compute(vo_ctx *ctx, int slot, const vo_orb_params *prm, const float *kp_xy, const int32_t *kp_octave, int n,
+                   int steer, float *angle_out, uint8_t *desc_out, uint8_t *valid_out);
+/* extractAndComputeORB: the detection of vo_orb_detect (same order, same bits) and the descriptors of all its keypoints,
+ * which do not leave the device in between. `set` (0 / 1): one of two descriptor sets that stay resident on the device for
+ * vo_orb_match_sets. kp_* / desc (32 bytes per keypoint) may each be NULL. */
+int vo_orb_detect_and_compute(vo_ctx *ctx, int slot, const vo_orb_params *prm, int steer, int set, float *kp_xy,
+                              float *kp_response, int32_t *kp_octave, float *kp_angle, uint8_t *desc, int max_kp, int *n_out);
+/* vo_orb_match on two resident sets (no upload, not limited by max_points): outputs hold one entry per keypoint of set_a
+ * (the n_out of its vo_orb_detect_and_compute) */
+int vo_orb_match_sets(vo_ctx *ctx, int set_a, int set_b, int th_low, float ratio, int32_t *best_idx, uint16_t *best_dist,
+                      uint16_t *second_dist);
 
 /* ---- landmark mask compaction (landmark.cpp:291-332, :194-231) ----------- */
 /* stable compaction indices of mask && alive && tracked; returns count in *n_out */

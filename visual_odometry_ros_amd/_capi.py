@@ -138,6 +138,8 @@ SYMBOLS = [
     "vo_set_sum_order", "vo_get_sum_order",
     "vo_five_point_create", "vo_five_point_destroy", "vo_five_point_pose", "vo_mvo_params_set_five_point",
     "vo_five_point_minimal", "vo_five_point_samples", "vo_five_point_counts",
+    "vo_orb_default_pattern", "vo_orb_get_pattern", "vo_orb_set_pattern", "vo_orb_compute", "vo_orb_detect_and_compute",
+    "vo_orb_match_sets",
 ]
 
 _lib = None
@@ -214,6 +216,12 @@ def load():
     lib.vo_five_point_minimal.argtypes = [vp, vp, vp, ci, vp, vp]
     lib.vo_five_point_samples.argtypes = [vp, vp, vp, vp, ci, vp]
     lib.vo_five_point_counts.argtypes = [vp, vp, ci, vp]
+    lib.vo_orb_default_pattern.argtypes = [vp]
+    lib.vo_orb_get_pattern.argtypes = [vp, vp]
+    lib.vo_orb_set_pattern.argtypes = [vp, vp]
+    lib.vo_orb_compute.argtypes = [vp, ci, C.POINTER(OrbParams), vp, vp, ci, ci, vp, vp, vp]
+    lib.vo_orb_detect_and_compute.argtypes = [vp, ci, C.POINTER(OrbParams), ci, ci, vp, vp, vp, vp, vp, ci, vp]
+    lib.vo_orb_match_sets.argtypes = [vp, ci, ci, ci, C.c_float, vp, vp, vp]
     lib.vo_triangulate_dlt.argtypes = [vp, vp, vp, ci, vp, vp, vp, vp, vp]
     lib.vo_batch_create.argtypes = [C.POINTER(VoConfig), C.POINTER(SvoParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_batch_destroy.argtypes = [vp]

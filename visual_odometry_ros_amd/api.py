@@ -456,6 +456,63 @@ class FeatureExtractor:
                                               _p(octv, C.c_int32), max_kp, C.byref(n)))
         return xy[: n.value].copy(), resp[: n.value].copy(), octv[: n.value].copy()
 
+    def extractAndComputeORB(self, slot, set=0, steer=True, max_kp=60000):
+        """extractAndComputeORB (feature_extractor.cpp:321-332) on the image in `slot`: detection as detect() and the
+        descriptors of all keypoints, which also stay on the device as descriptor set `set` (0 / 1) for matchSets:
+        (xy, response, octave, angle [degrees], size [31 * scale, as cv::KeyPoint::size], desc [n, 32])."""
+        xy = np.zeros((max_kp, 2), np.float32)
+        resp, ang = np.zeros(max_kp, np.float32), np.zeros(max_kp, np.float32)
+        octv = np.zeros(max_kp, np.int32)
+        desc = np.zeros((max_kp, 32), np.uint8)
+        n = C.c_int()
+        self.ctx.check(self.lib.vo_orb_detect_and_compute(
+            self.ctx.handle, slot, C.byref(self.orb), int(bool(steer)), int(set), xy.ctypes.data, resp.ctypes.data,
+            octv.ctypes.data, ang.ctypes.data, desc.ctypes.data, max_kp, C.addressof(n)))
+        n = n.value
+        if not hasattr(self, "_set_size"):
+            self._set_size = {}
+        self._set_size[int(set)] = n
+        octv = octv[:n].copy()
+        size = np.float32(31.0) * np.power(float(self.orb.scale_factor), octv.astype(np.float64)).astype(np.float32)
+        return xy[:n].copy(), resp[:n].copy(), octv, ang[:n].copy(), size, desc[:n].copy()
+
+    def compute(self, slot, xy, octave, steer=True):
+        """cv::ORB::compute restated (include/vo_hip.h) for the caller's keypoints on the image in `slot`:
+        (angle, desc [n, 32], valid); a keypoint too close to its level's border or of an octave that does not exist is
+        invalid: angle 0, zero descriptor."""
+        xy, octave = _f32(xy).reshape(-1, 2), np.ascontiguousarray(octave, np.int32).reshape(-1)
+        if xy.shape[0] != octave.shape[0]:
+            raise VoError(-4, "keypoint positions / octaves differ in length")
+        n = xy.shape[0]
+        ang, desc, valid = np.zeros(max(n, 1), np.float32), np.zeros((max(n, 1), 32), np.uint8), np.zeros(max(n, 1), np.uint8)
+        self.ctx.check(self.lib.vo_orb_compute(self.ctx.handle, slot, C.byref(self.orb), xy.ctypes.data, octave.ctypes.data, n,
+                                               int(bool(steer)), ang.ctypes.data, desc.ctypes.data, valid.ctypes.data))
+        return ang[:n], desc[:n], valid[:n].astype(bool)
+
+    def getPattern(self):
+        """The 512 x (x, y) sampling table of the descriptor (int8, each coordinate in [-15, 15])."""
+        pat = np.zeros((512, 2), np.int8)
+        self.ctx.check(self.lib.vo_orb_get_pattern(self.ctx.handle, pat.ctypes.data))
+        return pat
+
+    def setPattern(self, pattern):
+        """Replaces the context's table (e.g. by OpenCV's bit_pattern_31_); VoError -1 for a coordinate outside [-15, 15]."""
+        pat = np.asarray(pattern)
+        if pat.size != 1024 or np.any(pat < -128) or np.any(pat > 127):
+            raise VoError(-1, "a pattern is 512 x 2 int8")
+        pat = np.ascontiguousarray(pat, np.int8).reshape(512, 2)
+        self.ctx.check(self.lib.vo_orb_set_pattern(self.ctx.handle, pat.ctypes.data))
+
+    def matchSets(self, a, b, th_low=50, ratio=0.6):
+        """match() on two descriptor sets left on the device by extractAndComputeORB(set=a / b): no upload, any size."""
+        na = getattr(self, "_set_size", {}).get(int(a))
+        if na is None or int(b) not in self._set_size:
+            raise VoError(-1, "matchSets: extractAndComputeORB has not filled both sets through this object")
+        bi, bd, sd = np.zeros(max(na, 1), np.int32), np.zeros(max(na, 1), np.uint16), np.zeros(max(na, 1), np.uint16)
+        self.ctx.check(self.lib.vo_orb_match_sets(self.ctx.handle, int(a), int(b), th_low, C.c_float(ratio), bi.ctypes.data,
+                                                  bd.ctypes.data, sd.ctypes.data))
+        return bi[:na], bd[:na], sd[:na]
+
     def extractORBwithBinning_fast(self, slot):
         """feature_extractor.cpp:211-318 with flag_nonmax_ (the branch initParams selects, :37): detection and the
         per-bin arg-max on the device; returns pts_extracted."""

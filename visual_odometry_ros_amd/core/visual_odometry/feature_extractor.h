@@ -1,6 +1,6 @@
 // feature_extractor.h — FeatureExtractor::descriptorDistance
 // (core/visual_odometry/feature_extractor.cpp:338-357) for descriptor sets, and the bucketing around
-// cv::ORB::detect (feature_extractor.h:58-135, feature_extractor.cpp:241-277).
+// cv::ORB::detect (feature_extractor.h:58-135, feature_extractor.cpp:241-277), and extractAndComputeORB (:321-332).
 #ifndef VO_AMD_FEATURE_EXTRACTOR_H_
 #define VO_AMD_FEATURE_EXTRACTOR_H_
 
@@ -52,6 +52,56 @@ class FeatureExtractor {
     response.resize((size_t)n);
     octave.resize((size_t)n);
   }
+  // extractAndComputeORB (:321-332): detect() and the descriptors of all its keypoints (cv::ORB::compute restated, include/vo_hip.h);
+  // angle in degrees, size = 31 * scale (cv::KeyPoint::size), desc 32 bytes per keypoint. The descriptors also stay on the
+  // device as set 0 / 1 for matchSets.
+  void extractAndComputeORB(int slot, PixelVec &kp, std::vector<float> &response, std::vector<std::int32_t> &octave,
+                            std::vector<float> &angle, std::vector<float> &size, std::vector<std::uint8_t> &desc, int set = 0,
+                            bool steer = true, int max_kp = 60000) {
+    kp.assign((size_t)max_kp, Pixel{0.f, 0.f});
+    response.assign((size_t)max_kp, 0.f);
+    octave.assign((size_t)max_kp, 0);
+    angle.assign((size_t)max_kp, 0.f);
+    desc.assign((size_t)max_kp * 32, 0);
+    int n = 0;
+    ctx_->check(vo_orb_detect_and_compute(ctx_->get(), slot, &orb_, steer ? 1 : 0, set, &kp.data()->x, response.data(), octave.data(),
+                                          angle.data(), desc.data(), max_kp, &n));
+    kp.resize((size_t)n);
+    response.resize((size_t)n);
+    octave.resize((size_t)n);
+    angle.resize((size_t)n);
+    desc.resize((size_t)n * 32);
+    size.resize((size_t)n);
+    for (int i = 0; i < n; ++i) size[(size_t)i] = 31.0f * (float)std::pow(orb_.scale_factor, (double)octave[(size_t)i]);
+    set_size_[set] = n;
+  }
+  // descriptors of the caller's keypoints; valid[i] = 0 (angle 0, zero descriptor) for a keypoint too close to its level's border
+  void compute(int slot, const PixelVec &kp, const std::vector<std::int32_t> &octave, std::vector<float> &angle,
+               std::vector<std::uint8_t> &desc, std::vector<std::uint8_t> &valid, bool steer = true) {
+    if (kp.size() != octave.size()) throw std::runtime_error("keypoint positions / octaves differ in length");
+    const int n = (int)kp.size();
+    angle.assign((size_t)n, 0.f);
+    desc.assign((size_t)n * 32, 0);
+    valid.assign((size_t)n, 0);
+    ctx_->check(vo_orb_compute(ctx_->get(), slot, &orb_, n ? &kp.data()->x : zero_, octave.data(), n, steer ? 1 : 0, angle.data(),
+                               desc.data(), valid.data()));
+  }
+  void getPattern(std::int8_t pattern[1024]) { ctx_->check(vo_orb_get_pattern(ctx_->get(), pattern)); }
+  void setPattern(const std::int8_t pattern[1024]) { ctx_->check(vo_orb_set_pattern(ctx_->get(), pattern)); }
+  // the accept rule of test/test_orbmatching.cpp:87-137 on two resident sets: one entry per keypoint of set a
+  void matchSets(int a, int b, std::vector<std::int32_t> &best_idx, std::vector<std::uint16_t> &best_dist,
+                 std::vector<std::uint16_t> &second_dist, int th_low = 50, float ratio = 0.6f) {
+    if (a < 0 || a > 1 || b < 0 || b > 1 || set_size_[a] < 0 || set_size_[b] < 0)
+      throw std::runtime_error("matchSets: extractAndComputeORB has not filled both sets through this object");
+    const size_t na = (size_t)set_size_[a];
+    best_idx.assign(na + 1, -1);
+    best_dist.assign(na + 1, 0);
+    second_dist.assign(na + 1, 0);
+    ctx_->check(vo_orb_match_sets(ctx_->get(), a, b, th_low, ratio, best_idx.data(), best_dist.data(), second_dist.data()));
+    best_idx.resize(na);
+    best_dist.resize(na);
+    second_dist.resize(na);
+  }
   // extractORBwithBinning_fast (:211-318) with flag_nonmax_ (set by initParams, :37): detection and the per-bin
   // arg-max chained on the device. The image is the one held by `slot`.
   void extractORBwithBinning_fast(int slot, PixelVec &pts_extracted) {
@@ -100,6 +150,7 @@ class FeatureExtractor {
   std::vector<std::int32_t> weight_;
   vo_orb_params orb_{10000, 1.2, 8, 31, 15};
   float zero_[2] = {0.f, 0.f};
+  int set_size_[2] = {-1, -1};
 };
 
 }  // namespace vo

@@ -291,8 +291,9 @@ class MotionEstimator {
 };
 
 // ===== FeatureExtractor (core/visual_odometry/feature_extractor.h) ======================================
-// cv::ORB::detect + the per-bucket arg-max run on the device; extractAndComputeORB / extractORBwithBinning (the
-// non-"_fast" variants, descriptors) are not on the frame path and are not provided.
+// cv::ORB::detect + the per-bucket arg-max run on the device. extractAndComputeORB is vo::FeatureExtractor's (descriptors on the
+// device); it has no overload here because it needs cv::KeyPoint — INTEGRATION.md gives the five-line binding. extractORBwithBinning
+// (the non-"_fast" variant) is not on the frame path and is not provided.
 class FeatureExtractor {
  public:
   FeatureExtractor() {}

@@ -601,8 +601,8 @@ static int orb_tile_enqueue(vo_ctx *c, int slot, const vo_bin_params *bp, vo_can
   return VO_OK;
 }
 
-// enqueue the detection of the image in `slot`; results stay on the device (S->o_oxy, ...)
-static int orb_enqueue(vo_ctx *c, int slot, const vo_orb_params *p, int max_bins) {
+// the slot and the parameters are usable; the arena is laid out for them; c->stream is ordered behind the slot's build
+static int orb_begin(vo_ctx *c, int slot, const vo_orb_params *p, int max_bins) {
   if (slot < 0 || slot >= c->cfg.n_slots || c->slots[slot].n_levels <= 0) VO_FAIL(c, VO_ERR_INVALID, "slot holds no image");
   if (p->n_levels < 1 || p->n_levels > ORB_MAX_LEVELS || p->nfeatures < 0 || p->edge_threshold < 4 ||
       !(p->scale_factor > 1.0) || p->fast_threshold < 0 || p->fast_threshold > 254)
@@ -612,6 +612,35 @@ static int orb_enqueue(vo_ctx *c, int slot, const vo_orb_params *p, int max_bins
   int rc = orb_prepare(c, P.w, P.h, p, max_bins);
   if (rc) return rc;
   if (vo_slot_acquire(c, slot) < 0) return VO_ERR_HIP;
+  return VO_OK;
+}
+
+// levels 1 .. n_levels - 1 of the slot's image into the arena, on c->stream
+static void orb_resize_enqueue(vo_ctx *c, const vo_pyramid &P, int n_levels) {
+  vo_orb_state *S = c->orb;
+  uint8_t *A = S->arena;
+  for (int l = 1; l < n_levels; ++l) {
+    OrbResizeArgs a;
+    a.src = l > 1 ? A + S->o_img[l - 1] : P.lv[0].origin();
+    a.sw = S->lw[l - 1];
+    a.sh = S->lh[l - 1];
+    a.sstride = l > 1 ? S->lw[l - 1] : P.lv[0].stride;
+    a.dst = A + S->o_img[l];
+    a.dw = S->lw[l];
+    a.dh = S->lh[l];
+    a.ox = (const int *)(A + S->o_tab[l][0]);
+    a.cx = (const int *)(A + S->o_tab[l][1]);
+    a.oy = (const int *)(A + S->o_tab[l][2]);
+    a.cy = (const int *)(A + S->o_tab[l][3]);
+    hipLaunchKernelGGL(orb_resize_kernel, dim3((a.dw + 255) / 256, a.dh), dim3(256), 0, c->stream, a);
+  }
+}
+
+// enqueue the detection of the image in `slot`; results stay on the device (S->o_oxy, ...)
+static int orb_enqueue(vo_ctx *c, int slot, const vo_orb_params *p, int max_bins) {
+  int rc = orb_begin(c, slot, p, max_bins);
+  if (rc) return rc;
+  const vo_pyramid &P = c->slots[slot];
   vo_orb_state *S = c->orb;
   hipStream_t s = c->stream;
   uint8_t *A = S->arena;
@@ -652,21 +681,7 @@ static int orb_enqueue(vo_ctx *c, int slot, const vo_orb_params *p, int max_bins
   VO_CHECK_HIP(c, hipMemsetAsync(A + S->o_hist, 0, S->o_cx - S->o_hist, s));
   S->tile_clean = false;  // (level totals and, with the bucketing behind this, the keys are left as they come out)
   vo_prof_begin(c, VO_K_AUX);
-  for (int l = 1; l < p->n_levels; ++l) {
-    OrbResizeArgs a;
-    a.src = d.L[l - 1].img;
-    a.sw = d.L[l - 1].w;
-    a.sh = d.L[l - 1].h;
-    a.sstride = d.L[l - 1].stride;
-    a.dst = A + S->o_img[l];
-    a.dw = S->lw[l];
-    a.dh = S->lh[l];
-    a.ox = (const int *)(A + S->o_tab[l][0]);
-    a.cx = (const int *)(A + S->o_tab[l][1]);
-    a.oy = (const int *)(A + S->o_tab[l][2]);
-    a.cy = (const int *)(A + S->o_tab[l][3]);
-    hipLaunchKernelGGL(orb_resize_kernel, dim3((a.dw + 255) / 256, a.dh), dim3(256), 0, s, a);
-  }
+  orb_resize_enqueue(c, P, p->n_levels);
   const int rows = P.h - 2 * p->edge_threshold;
   hipLaunchKernelGGL(orb_score_kernel, dim3((P.w + 255) / 256, P.h, p->n_levels), dim3(256), 0, s, d);
   if (rows > 0) hipLaunchKernelGGL(orb_count_kernel, dim3(rows, 1, p->n_levels), dim3(64), 0, s, d);
@@ -720,6 +735,37 @@ extern "C" int vo_orb_get_level(vo_ctx *c, int level, uint8_t *host, int *width,
   if (height) *height = S->lh[level];
   return VO_OK;
 }
+
+// for orb_describe.hip: the ORB pyramid of the slot's image (detect: the whole detection) enqueued on c->stream, and where
+// its results lie on the device
+int vo_orb_levels_enqueue(vo_ctx *c, int slot, const vo_orb_params *p, bool detect, vo_orb_view *v) {
+  int rc = detect ? orb_enqueue(c, slot, p, 0) : orb_begin(c, slot, p, 0);
+  if (rc) return rc;
+  vo_orb_state *S = c->orb;
+  const vo_pyramid &P = c->slots[slot];
+  if (!detect) {
+    orb_resize_enqueue(c, P, p->n_levels);
+    VO_CHECK_HIP(c, hipGetLastError());
+  }
+  uint8_t *A = S->arena;
+  v->n_levels = p->n_levels;
+  v->edge = p->edge_threshold;
+  v->max_out = S->max_out;
+  for (int l = 0; l < p->n_levels; ++l) {
+    v->img[l] = l ? A + S->o_img[l] : P.lv[0].origin();
+    v->w[l] = S->lw[l];
+    v->h[l] = S->lh[l];
+    v->stride[l] = l ? S->lw[l] : P.lv[0].stride;
+    v->scale[l] = S->lscale[l];
+  }
+  v->xy = (const float *)(A + S->o_oxy);
+  v->resp = (const float *)(A + S->o_oresp);
+  v->oct = (const int32_t *)(A + S->o_ooct);
+  v->n_dev = (const int *)(A + S->o_on);
+  v->flags_dev = (const int *)(A + S->o_flags);
+  return VO_OK;
+}
+int vo_orb_check_flags(vo_ctx *c, int flags) { return orb_check_flags(c, flags); }
 
 // FeatureExtractor::extractORBwithBinning_fast with flag_nonmax_ (feature_extractor.cpp:211-277): detection and
 // the per-bin arg-max chained on the device; only the bucketed pixels come back

@@ -96,6 +96,7 @@ struct vo_ctx {
   int32_t next_landmark_id, next_frame_id;
   struct vo_sba_state *sba;  // device arena of the sparse local BA (sba.hip)
   struct vo_orb_state *orb;  // pyramid, score planes and candidate lists of the keypoint detector (orb_detect.hip)
+  struct vo_orb_desc_state *orb_desc;  // pattern table, resident descriptor sets (orb_describe.hip)
   // every device / pinned allocation made on behalf of this context (vo_dev_malloc / vo_host_malloc): what
   // vo_debug_allocation_count reports, so that a test can assert that a steady-state frame allocates nothing
   long long n_allocs;

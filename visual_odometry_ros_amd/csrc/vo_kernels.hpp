@@ -71,6 +71,20 @@ void vo_sba_free(vo_ctx *c);
 
 // orb_detect.hip
 void vo_orb_free(vo_ctx *c);
+struct vo_orb_view {  // the ORB pyramid and the last detection's results on the device
+  int n_levels, edge, max_out;
+  const uint8_t *img[12];
+  int w[12], h[12], stride[12];
+  float scale[12];
+  const float *xy, *resp;
+  const int32_t *oct;
+  const int *n_dev, *flags_dev;
+};
+int vo_orb_levels_enqueue(vo_ctx *c, int slot, const vo_orb_params *p, bool detect, vo_orb_view *v);
+int vo_orb_check_flags(vo_ctx *c, int flags);
+
+// orb_describe.hip
+void vo_orb_describe_free(vo_ctx *c);
 
 // klt_track.hip
 int vo_klt_enqueue(vo_ctx *c, int slot0, int slot1, const float *d_pts0, const float *d_pts1_init,
