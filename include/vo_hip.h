@@ -590,6 +590,20 @@ int vo_svo_get_keyframes(vo_svo *svo, float *T_wc, int32_t *n_points, float *map
 /* Device memory this StereoVO holds for its keyframes (landmark table, keyframe ring, keyframe pool, the local BA's window
  * scratch and arena): ~32 MB at BASELINE configs[1] (max_points 4024, window of 9), all of it allocated by vo_svo_create. */
 int vo_svo_device_bytes(const vo_svo *svo, size_t *bytes);
+/* img_debug_ of the reference's StereoVO: with the option on, every tracked frame draws what stereo_vo.cpp:685-688 draws,
+ * showTrackingBA(I1_left, {}, lmtrack_final.pts_l1) = vo_draw_tracking_ba (below) on level 0 of the current left image with
+ * pts empty and pts_proj = the frame's surviving landmarks' left pixels (the first n_final entries of the track set the frame
+ * leaves behind). Off by default; with it off no launch, allocation or result differs from a driver without the option.
+ * vo_svo_set_debug_image(svo, 1) allocates an index plane, the picture on the device and a pinned host picture — the
+ * option's only allocation; VO_ERR_INVALID while a frame is in flight. The rendering is enqueued behind the frame's last
+ * launch on the context's side stream, with the copy to the host behind it; vo_svo_result does not wait for it, and poses,
+ * ids, flags and keyframe decisions are the same bits with the option on and off.
+ * vo_svo_get_debug_image waits for the last picture only and copies it into `out` (height x width x 3 bytes, row pitch
+ * out_stride >= 3 * width; NULL: the size only). A frame that does not draw (the first pair of a stream) keeps the previous
+ * picture; before the first one *width = *height = 0 and the call returns VO_OK.
+ * MonoVO has no such option yet: its getDebugImage stays empty. */
+int vo_svo_set_debug_image(vo_svo *svo, int on);
+int vo_svo_get_debug_image(vo_svo *svo, uint8_t *out, int out_stride, int *width, int *height);
 
 /* ---- undistortion / stereo rectification in front of the trackers ----------
  * core/visual_odometry/camera.cpp. A context holds the maps of two cameras
@@ -615,6 +629,76 @@ int vo_set_image_rectified_device(vo_ctx *ctx, int slot, const void *dev, int wi
 /* left image through cam 0's map, right image through cam 1's, one launch chain */
 int vo_set_stereo_pair_rectified_device(vo_ctx *ctx, int slot_l, const void *dev_l, int slot_r, const void *dev_r,
                                         int width, int height, int stride);
+/* The pixel format of the images given to the three entry points above and, through them, to vo_svo_* / vo_mvo_*
+ * created with rectify = 1 (synchronous call, prefetch / enqueue, run; host and device images). It is a property of the
+ * context; the default is VO_PIX_MONO8, with which nothing changes. `stride` stays in BYTES for every format and need
+ * not be a multiple of the sample size; `host` / `dev` point at the first byte of the image whatever its type.
+ *
+ * The reference's ingestion with flagDoUndistortion (camera.cpp:163-183, :300-336; stereo_vo.cpp:414-421;
+ * mono_vo.cpp:509-513) takes any cv::Mat: a 3-channel image goes through cvtColor(COLOR_RGB2GRAY), any depth through
+ * convertTo(CV_32FC1), cv::remap (INTER_LINEAR, BORDER_CONSTANT 0) and convertTo(CV_8UC1). Per format, one output byte is:
+ *   VO_PIX_RGB8     every tap is gray = (c0*9798 + c1*19235 + c2*3735 + 16384) >> 15 of its three bytes c0 c1 c2 — OpenCV
+ *                   4.5's 8-bit RGB2Gray with 15-bit coefficients, restated from memory and NOT pinned against an OpenCV
+ *                   build (like every third-party restatement here). Channel 0 is weighted as R whatever
+ *                   the message called it: that is what the reference's COLOR_RGB2GRAY does to a bgr8 image, so this is
+ *                   the format for every 3-channel image of an unmodified node. The u8 gray taps then go through the
+ *                   integer remap of VO_PIX_MONO8 unchanged (pyramid.hip / ingest_formats.hpp: remap_sample).
+ *   VO_PIX_BGR8     the same with c0 and c2 exchanged. For callers who know their data; not the reference's behaviour.
+ *   VO_PIX_MONO16U / VO_PIX_MONO16S / VO_PIX_F32
+ *                   a tap is a float (16-bit values convert exactly). The map coordinates are quantised to 1/32 px as
+ *                   for u8: fx = cvRound(map_u*32), sx = fx >> 5, ax = fx & 31 (the same for y; a NaN coordinate is far
+ *                   outside). Taps outside the source are 0. Weights w00 = (32-ay)(32-ax)/1024, w01 = (32-ay)ax/1024,
+ *                   w10 = ay(32-ax)/1024, w11 = ay*ax/1024, exact in float. The sum is
+ *                   ((v00*w00 + v01*w01) + v10*w10) + v11*w11 with every product and every sum rounded to float on its
+ *                   own (no FMA): OpenCV's scalar remapBilinear<float>. convertTo(CV_8UC1) of that sum s: NaN gives 0;
+ *                   |s| >= 2^31 gives 0 (x86 cvRound returns the integer-indefinite value, the convention the
+ *                   coordinates already follow — unpinned as well); anything else is rounded half to even and clamped
+ *                   to [0, 255].
+ * vo_set_input_format grows the context's pinned-host and device staging images to 3 (RGB8, BGR8), 2 (16-bit) or 4 (F32)
+ * bytes per pixel the first time a format needs it; it is the only place that allocates for this. It returns
+ * VO_ERR_INVALID for an unknown format and while a frame is in flight.
+ * The entry points WITHOUT a remap — vo_set_image, vo_set_image_device, vo_set_stereo_pair_device,
+ * vo_set_stereo_pair_host_async, and the drivers created with rectify = 0 — return VO_ERR_INVALID while the format is not
+ * VO_PIX_MONO8: in the reference a colour image on that path reaches the trackers unconverted, there is no behaviour to
+ * mirror. Undistorted colour / 16-bit / float data goes through the rectifying entry points with identity maps
+ * (vo_rectify_set_maps with map_u[v][u] = u, map_v[v][u] = v: integer coordinates sample one tap with weight 1). */
+enum { VO_PIX_MONO8 = 0, VO_PIX_RGB8 = 1, VO_PIX_BGR8 = 2, VO_PIX_MONO16U = 3, VO_PIX_MONO16S = 4, VO_PIX_F32 = 5 };
+int vo_set_input_format(vo_ctx *ctx, int format);
+int vo_get_input_format(vo_ctx *ctx, int *format);
+
+/* ---- the drivers' debug image: showTracking / showTrackingBA -----------------------------------------------------
+ * Both drivers share one text for each (stereo_vo.cpp:685-688 -> showTrackingBA; mono_vo.cpp:554-555, :626-627 ->
+ * showTracking, :903-904 -> showTrackingBA) and draw into img_debug_, which the ROS 1 nodes publish as bgr8
+ * (stereo_vo_ros1.cpp:199-203, mono_vo_ros1.cpp:245-248). `out` is a HOST image of height x width x 3 bytes (row pitch
+ * out_stride >= 3 * width) of the size of the slot's image: level 0 of `slot` replicated into the three channels
+ * (CV_GRAY2RGB) with the primitives on top. Channel k receives component k of the reference's cv::Scalar, so in the
+ * published bgr8 buffer (0,255,0) is green and (0,0,255) is red. Points are x y pairs in HOST memory; n <=
+ * vo_config.max_points per set; a NULL set with n = 0 is an empty set.
+ *   vo_draw_tracking, primitives in this order:
+ *     for i < n1: the line pts0[i] -> pts1[i] in (0,255,255); n1 <= n0, VO_ERR_INVALID otherwise
+ *     for each of pts0:    circle(3, 2) in (0,0,0), then circle(2, 1) in (255,0,255)
+ *     for each of pts1:    circle(3, 2) in (0,0,0), then circle(2, 1) in (0,255,0)
+ *     for each of pts_new: circle(3, 2) in (0,0,0), then circle(2, 1) in (255,0,0)
+ *   vo_draw_tracking_ba:
+ *     for each of pts:      circle(1, 4) in (0,0,255)
+ *     for each of pts_proj: rect(6, 2) in (0,255,0)
+ * The rasterisation is the library's OWN: it is modelled on the look of cv::line / cv::circle / cv::rectangle and is NOT
+ * pixel parity with them (as §10's RANSAC is not OpenCV's). Its rules, all in integers:
+ *   centre      c = (rint(x), rint(y)), halves to even. A point with a NaN coordinate or with |coordinate| >= 2^30 is
+ *               skipped; a line is skipped when either of its end points is.
+ *   circle(r,t) the pixels c + (dx, dy) with max(0, 2r - t)^2 <= 4 (dx^2 + dy^2) <= (2r + t)^2
+ *   rect(h,t)   the pixels c + (dx, dy) with 2h - t <= 2 max(|dx|, |dy|) <= 2h + t
+ *   line a -> b between the two centres: n = max(|bx - ax|, |by - ay|); the pixels
+ *               (ax + floor((2k(bx - ax) + n) / (2n)), ay + floor((2k(by - ay) + n) / (2n))) for k = 0 .. n, floor
+ *               division; for n = 0 the one pixel a.
+ *   clipping    pixels outside the image are dropped, primitive by primitive.
+ *   overlap     primitives are numbered from 0 in the order above; a pixel takes the colour of the highest-numbered
+ *               primitive that covers it, else its gray value. The result does not depend on scheduling.
+ * The first call allocates the context's drawing buffers (an index plane, the picture on the device and pinned). */
+int vo_draw_tracking(vo_ctx *ctx, int slot, const float *pts0, int n0, const float *pts1, int n1, const float *pts_new,
+                     int n_new, uint8_t *out, int out_stride);
+int vo_draw_tracking_ba(vo_ctx *ctx, int slot, const float *pts, int n, const float *pts_proj, int n_proj, uint8_t *out,
+                        int out_stride);
 
 /* ---- steady-state mono frame ----------------------------------------------
  * The operator sequence of MonoVO::trackImage

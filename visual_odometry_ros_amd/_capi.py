@@ -125,6 +125,8 @@ SYMBOLS = [
     "vo_sba_solve", "vo_orb_detect", "vo_orb_get_level", "vo_extract_orb_with_binning",
     "vo_extract_orb_with_binning_enqueue", "vo_extract_orb_with_binning_result", "vo_rectify_init_mono", "vo_rectify_init_stereo", "vo_rectify_set_maps", "vo_rectify_get_maps",
     "vo_set_image_rectified", "vo_set_image_rectified_device", "vo_set_stereo_pair_rectified_device",
+    "vo_set_input_format", "vo_get_input_format", "vo_draw_tracking", "vo_draw_tracking_ba",
+    "vo_svo_set_debug_image", "vo_svo_get_debug_image",
     "vo_profile_enable", "vo_profile_reset", "vo_profile_get", "vo_profile_set_classes",
     "vo_set_stereo_pair_device", "vo_set_pyramid_window_hint",
     "vo_set_ingest_side_stream", "vo_set_stereo_pair_host_async", "vo_new_point_candidates_enqueue",
@@ -207,6 +209,12 @@ def load():
     lib.vo_batch_strict_border.argtypes = [vp]
     lib.vo_debug_allocation_count.argtypes = [vp, vp]
     lib.vo_set_sum_order.argtypes = [vp, ci]
+    lib.vo_set_input_format.argtypes = [vp, ci]
+    lib.vo_get_input_format.argtypes = [vp, vp]
+    lib.vo_draw_tracking.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci, vp, ci]
+    lib.vo_draw_tracking_ba.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci]
+    lib.vo_svo_set_debug_image.argtypes = [vp, ci]
+    lib.vo_svo_get_debug_image.argtypes = [vp, vp, ci, vp, vp]
     lib.vo_get_sum_order.argtypes = [vp]
     lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_five_point_destroy.argtypes = [vp]

@@ -146,10 +146,46 @@ class Context:
         if rc < 0:
             self.check(rc)
 
+    # include/vo_hip.h: VO_PIX_*; what an array of each format looks like: (dtype, trailing channels)
+    INPUT_FORMATS = {"mono8": 0, "rgb8": 1, "bgr8": 2, "mono16u": 3, "mono16s": 4, "f32": 5}
+    _FORMAT_ARRAYS = {"mono8": (np.uint8, 0), "rgb8": (np.uint8, 3), "bgr8": (np.uint8, 3), "mono16u": (np.uint16, 0),
+                      "mono16s": (np.int16, 0), "f32": (np.float32, 0)}
+    _fmt = "mono8"
+
+    def set_input_format(self, fmt):
+        """Pixel format of the images the RECTIFYING entry points take (vo_set_input_format): "mono8" (default), "rgb8"
+        (what the reference makes of any 3-channel image: channel 0 weighted as R), "bgr8", "mono16u", "mono16s", "f32".
+        set_image_rectified, Camera.undistortImage, StereoCamera.rectifyStereoImages and StereoVO / MonoVO created with
+        rectify=True then take (H, W, 3) uint8 or (H, W) uint16 / int16 / float32 arrays; everything else keeps
+        requiring uint8 planes. Refused while a frame is in flight."""
+        if fmt not in self.INPUT_FORMATS:
+            raise ValueError(f"input format must be one of {sorted(self.INPUT_FORMATS)}, not {fmt!r}")
+        self.check(self.lib.vo_set_input_format(self._h, self.INPUT_FORMATS[fmt]))
+        self._fmt = fmt
+
+    @property
+    def input_format(self):
+        f = C.c_int()
+        self.check(self.lib.vo_get_input_format(self._h, C.byref(f)))
+        return {v: k for k, v in self.INPUT_FORMATS.items()}[f.value]
+
+    def _format_image(self, img):
+        """`img` as the C-contiguous array the rectifying entry points read: for "mono8" what _u8 makes of it (as always),
+        for the other formats an array of exactly the format's dtype and shape, VoError otherwise."""
+        if self._fmt == "mono8":
+            return _u8(img)
+        dt, ch = self._FORMAT_ARRAYS[self._fmt]
+        if not isinstance(img, np.ndarray) or img.dtype != dt or img.ndim != (3 if ch else 2) or (ch and img.shape[2] != ch):
+            want = f"(H, W, {ch}) " if ch else "(H, W) "
+            got = f"{getattr(img, 'shape', None)} {getattr(img, 'dtype', type(img).__name__)}"
+            raise VoError(-1, f"input format {self._fmt!r} takes {want}{np.dtype(dt).name} arrays, not {got}")
+        return np.ascontiguousarray(img)
+
     def set_image_rectified(self, slot, img, cam=0):
-        img = _u8(img)
-        assert img.ndim == 2
-        self.check(self.lib.vo_set_image_rectified(self._h, slot, _p(img, C.c_uint8), img.shape[1], img.shape[0],
+        img = self._format_image(img)
+        if img.ndim != 2 and self._fmt == "mono8":
+            raise VoError(-1, f"input format 'mono8' takes (H, W) uint8 planes, not an array of shape {img.shape}")
+        self.check(self.lib.vo_set_image_rectified(self._h, slot, C.c_void_p(img.ctypes.data), img.shape[1], img.shape[0],
                                                    img.strides[0], cam))
 
     def set_image_rectified_device(self, slot, dev_ptr, width, height, stride, cam=0):
@@ -159,6 +195,23 @@ class Context:
     def set_stereo_pair_rectified_device(self, slot_l, ptr_l, slot_r, ptr_r, width, height, stride):
         self.check(self.lib.vo_set_stereo_pair_rectified_device(self._h, slot_l, C.c_void_p(ptr_l), slot_r,
                                                                 C.c_void_p(ptr_r), width, height, stride))
+
+    # ---- debug image (include/vo_hip.h: vo_draw_tracking, vo_draw_tracking_ba) -----------------------------------
+    def _draw(self, fn, slot, sets):
+        h, w = self.get_level(slot, 0).shape  # (the picture has the size of the slot's image)
+        out = np.zeros((h, w, 3), np.uint8)
+        sets = [_f32(pts).reshape(-1, 2) for pts in sets]
+        args = [a for pts in sets for a in (pts.ctypes.data if len(pts) else None, len(pts))]
+        self.check(fn(self._h, slot, *args, out.ctypes.data, out.strides[0]))
+        return out
+
+    def draw_tracking(self, slot, pts0, pts1, pts_new):
+        """showTracking on level 0 of `slot`: (H, W, 3) uint8, lines pts0[i] -> pts1[i] and the three point sets' markers"""
+        return self._draw(self.lib.vo_draw_tracking, slot, (pts0, pts1, pts_new))
+
+    def draw_tracking_ba(self, slot, pts, pts_proj):
+        """showTrackingBA on level 0 of `slot`: (H, W, 3) uint8, discs at pts and hollow squares at pts_proj"""
+        return self._draw(self.lib.vo_draw_tracking_ba, slot, (pts, pts_proj))
 
     def set_pyramid_window_hint(self, win):
         self.check(self.lib.vo_set_pyramid_window_hint(self._h, win))
@@ -869,8 +922,10 @@ class StereoVO:
 
     def __init__(self, ctx, width, height, Kl, Kr, T_lr, n_bins_u, n_bins_v, thres_fastscore=15, window_size=21, max_level=6,
                  thres_error=80.0, thres_bidirection=0.5, thres_poseba_error=3.0, thres_alive_ratio=0.6, thres_rotation=15.0,
-                 thres_trans=10.0, n_max_keyframes_in_window=9, strict_border=4, local_ba=True, rectify=False, thres_sampson=60.0):
-        """rectify=True is system_flags_.flagDoUndistortion: the context's stereo rectification maps (StereoCamera.
+                 thres_trans=10.0, n_max_keyframes_in_window=9, strict_border=4, local_ba=True, rectify=False, thres_sampson=60.0,
+                 debug_image=False):
+        """debug_image=True: every tracked frame draws the reference's img_debug_ on the device (getDebugImage).
+        rectify=True is system_flags_.flagDoUndistortion: the context's stereo rectification maps (StereoCamera.
         initStereoCameraToRectify on the same context) are applied to every incoming pair; Kl / Kr / T_lr are then the
         rectified camera and extrinsics (getRectifiedCamera / getRectifiedStereoPoseLeft2Right)."""
         self.ctx, self.lib = ctx, ctx.lib
@@ -887,18 +942,21 @@ class StereoVO:
         self._h = C.c_void_p()
         ctx.check(self.lib.vo_svo_create(ctx.handle, C.byref(p), C.byref(self._h)))
         ctx._children.add(self)
+        if debug_image:
+            ctx.check(self.lib.vo_svo_set_debug_image(self._h, 1))
         self._info = SvoFrameInfo()
         self.stats_frame = []  # AlgorithmStatistics::FrameStatistics::Twc per frame (stereo_vo.cpp:979-980)
 
     @classmethod
-    def from_yaml(cls, path, device=0, max_points=None, **overrides):
+    def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", **overrides):
         """StereoVO(mode = "rosbag", directory_intrinsic = path) of the reference (stereo_vo.cpp:15-57, :118-280): the
         object configured by one of its config/stereo/*.yaml files. The context is created here (sized by the file) and
         closed with the object. With flagDoUndistortion the pairs go through the rectification maps and the loop runs on
         the rectified camera (:414-427); without, on the raw cameras and T_lr of the file. `overrides`: keyword
         arguments of the constructor that the file does not know (strict_border, local_ba). `max_points`: capacity of a
         track set (default 2 * bins + 1024; the reference has no such bound — several survivors may share a bin while
-        every empty bin adds a landmark — so a caller that sees VO_ERR_CAPACITY raises it)."""
+        every empty bin adds a landmark — so a caller that sees VO_ERR_CAPACITY raises it). `input_format`: the pairs'
+        pixel format (Context.set_input_format); anything but "mono8" needs flagDoUndistortion in the file."""
         from . import config as _config
         cfg = _config.load_stereo_config(path)
         cl, cr = cfg["camera"]["left"], cfg["camera"]["right"]
@@ -908,6 +966,8 @@ class StereoVO:
         ctx = Context(device=device, max_width=W, max_height=H, max_points=cap, n_slots=5,
                       max_level=ft["max_level"])
         try:
+            if input_format != "mono8":
+                ctx.set_input_format(input_format)
             Kl, Kr, T_lr, rectify = cl["K"], cr["K"], cfg["T_lr"], False
             if cfg["flagDoUndistortion"]:
                 cam = StereoCamera(ctx)
@@ -943,11 +1003,19 @@ class StereoVO:
         except Exception:
             pass
 
-    @staticmethod
-    def _ptrs(left, right):
+    def _img(self, a):
+        """a host image as the library reads it: a u8 plane, or — with rectify=True — an array of the context's input format"""
+        if self.prm.rectify and self.ctx._fmt != "mono8":
+            return self.ctx._format_image(a)
+        return _u8(a)
+
+    def _nd(self):
+        return 3 if self.prm.rectify and self.ctx._fmt in ("rgb8", "bgr8") else 2
+
+    def _ptrs(self, left, right):
         if isinstance(left, np.ndarray):
-            left, right = _u8(left), _u8(right)
-            if left.ndim != 2 or left.shape != right.shape:
+            left, right = self._img(left), self._img(right)
+            if left.ndim != self._nd() or left.shape != right.shape:
                 raise ValueError("images must be two u8 planes of one size")
             return left, right, left.ctypes.data, right.ctypes.data, left.strides[0], 0
         return left, right, int(left[0]), int(right[0]), int(left[1]), 1  # (device address, stride) pairs
@@ -997,9 +1065,9 @@ class StereoVO:
         host = n > 0 and isinstance(pairs[0][0], np.ndarray)
         if host:  # (the arrays themselves are handed to the library: they are kept alive with the list, below)
             if getattr(self, "_seq_ref", None) is not pairs or len(getattr(self, "_seq_host", ())) != n:
-                self._seq_host = [(_u8(L), _u8(R)) for L, R in pairs]
+                self._seq_host = [(self._img(L), self._img(R)) for L, R in pairs]
                 st0 = self._seq_host[0][0].strides[0]
-                if any(a.ndim != 2 or a.shape != b.shape or a.strides[0] != st0 or b.strides[0] != st0 for a, b in self._seq_host):
+                if any(a.ndim != self._nd() or a.shape != b.shape or a.strides[0] != st0 or b.strides[0] != st0 for a, b in self._seq_host):
                     raise ValueError("runSequence: host images must be u8 planes of one size and row stride")
             src = [((a.ctypes.data, a.strides[0]), (b.ctypes.data, b.strides[0])) for a, b in self._seq_host]
         else:
@@ -1030,6 +1098,16 @@ class StereoVO:
         for i in out:
             self.stats_frame.append(np.array(i.T_wc, np.float32).reshape(4, 4))
         return out, stamps[:m]
+
+    def getDebugImage(self):
+        """img_debug_ of the last frame that drew one (debug_image=True): an (H, W, 3) uint8 array — published as bgr8 by the
+        reference's nodes, (0, 255, 0) is green — or an empty (0, 0, 3) array before the first one and with the option off."""
+        w, h = C.c_int(), C.c_int()
+        self.ctx.check(self.lib.vo_svo_get_debug_image(self._h, None, 0, C.addressof(w), C.addressof(h)))
+        out = np.zeros((h.value, w.value, 3), np.uint8)
+        if out.size:
+            self.ctx.check(self.lib.vo_svo_get_debug_image(self._h, out.ctypes.data, out.strides[0], C.addressof(w), C.addressof(h)))
+        return out
 
     def getTracks(self):
         """The track set the next frame starts from: dict(ids, pts_l, pts_r, Xw, flags)."""
@@ -1249,8 +1327,8 @@ class Camera:
         return _get_maps(self.ctx, self.cam)
 
     def undistortImage(self, raw, slot):
-        raw = _u8(raw)
-        if raw.size == 0 or raw.shape != (self.n_rows, self.n_cols):  # camera.cpp:168-169
+        raw = self.ctx._format_image(raw)  # (an array of the context's input format: Context.set_input_format)
+        if raw.size == 0 or raw.shape[:2] != (self.n_rows, self.n_cols):  # camera.cpp:168-169
             raise VoError(-4, "undistort image: provided image has not the same size as the camera model!")
         self.ctx.set_image_rectified(slot, raw, self.cam)
 
@@ -1312,7 +1390,7 @@ class StereoCamera:
     def rectifyStereoImages(self, img_left, img_right, slot_l, slot_r):
         self._need_init("rectifyStereoImages()")
         for im in (img_left, img_right):  # camera.cpp:307, :324
-            if np.asarray(im).shape != (self.n_rows, self.n_cols):
+            if np.asarray(im).shape[:2] != (self.n_rows, self.n_cols):
                 raise VoError(-4, "In 'rectifyStereoImages()': provided image has not the same size as the camera model!")
         self.ctx.set_image_rectified(slot_l, img_left, 0)
         self.ctx.set_image_rectified(slot_r, img_right, 1)
@@ -1516,13 +1594,14 @@ class MonoVO:
         self.stats_frame = []
 
     @classmethod
-    def from_yaml(cls, path, device=0, max_points=None, **overrides):
+    def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", **overrides):
         """MonoVO(mode = "rosbag", directory_intrinsic = path) of the reference (mono_vo.cpp:15-60, :137-225): the object
         configured by one of its config/mono/*.yaml files, with the library's 5-point solver at motion_estimator.
         thres_5p_error. The context is created here (sized by the file) and closed with the object. With flagDoUndistortion
         the images go through the camera's undistortion map (mono_vo.cpp:509-513). `overrides`: keyword arguments of the
         constructor (five_point, strict_border, local_ba, ...). `max_points`: capacity of a track set (default 2 * bins +
-        1024, as StereoVO.from_yaml)."""
+        1024, as StereoVO.from_yaml). `input_format`: the images' pixel format (Context.set_input_format); anything but
+        "mono8" needs flagDoUndistortion in the file."""
         from . import config as _config
         cfg = _config.load_mono_config(path)
         cam = cfg["camera"]
@@ -1531,6 +1610,8 @@ class MonoVO:
         cap = int(max_points) if max_points else 2 * fe["n_bins_u"] * fe["n_bins_v"] + 1024
         ctx = Context(device=device, max_width=W, max_height=H, max_points=cap, n_slots=3, max_level=max(ft["max_level"], 1))
         try:
+            if input_format != "mono8":
+                ctx.set_input_format(input_format)
             if cfg["flagDoUndistortion"]:
                 Camera(ctx, 0).initParams(W, H, cam["K"], cam["D"])
             # (keys the file does not have keep the constructor's defaults: a 0 there is refused or meaningless — mono0.yaml
@@ -1577,11 +1658,12 @@ class MonoVO:
         except Exception:
             pass
 
-    @staticmethod
-    def _ptr(img):
+    _img, _nd = StereoVO._img, StereoVO._nd
+
+    def _ptr(self, img):
         if isinstance(img, np.ndarray):
-            img = _u8(img)
-            if img.ndim != 2:
+            img = self._img(img)
+            if img.ndim != self._nd():
                 raise ValueError("the image must be one u8 plane")
             return img, img.ctypes.data, img.strides[0], 0
         return img, int(img[0]), int(img[1]), 1  # (device address, stride)
@@ -1627,9 +1709,9 @@ class MonoVO:
         host = n > 0 and isinstance(images[0], np.ndarray)
         if host:
             if getattr(self, "_seq_ref", None) is not images or len(getattr(self, "_seq_host", ())) != n:
-                self._seq_host = [_u8(I) for I in images]
+                self._seq_host = [self._img(I) for I in images]
                 st0 = self._seq_host[0].strides[0]
-                if any(a.ndim != 2 or a.shape != self._seq_host[0].shape or a.strides[0] != st0 for a in self._seq_host):
+                if any(a.ndim != self._nd() or a.shape != self._seq_host[0].shape or a.strides[0] != st0 for a in self._seq_host):
                     raise ValueError("runSequence: host images must be u8 planes of one size and row stride")
             src = [(a.ctypes.data, a.strides[0]) for a in self._seq_host]
         else:

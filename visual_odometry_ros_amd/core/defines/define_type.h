@@ -39,8 +39,10 @@ struct Image {
   const std::uint8_t *data;
   int width, height, stride;
   std::uint64_t id;
-  Image(const std::uint8_t *d, int w, int h, int s, std::uint64_t id_ = 0)
-      : data(d), width(w), height(h), stride(s), id(id_) {}
+  int format;  // VO_PIX_* (include/vo_hip.h): 0 = a u8 plane; the others only where an image is undistorted / rectified.
+               // `data` points at the first byte and `stride` is in bytes whatever the format
+  Image(const std::uint8_t *d, int w, int h, int s, std::uint64_t id_ = 0, int format_ = 0)
+      : data(d), width(w), height(h), stride(s), id(id_), format(format_) {}
 };
 
 struct Camera {  // the accessors MotionEstimator uses (core/visual_odometry/camera.h fx(), fy(), cx(), cy())

@@ -33,6 +33,7 @@ class DistortedCamera {
   void undistortImage(const Image &raw, int slot) {
     if (!raw.data || raw.width != n_cols_ || raw.height != n_rows_)
       throw std::runtime_error("undistort image: provided image has not the same size as the camera model!\n");
+    ctx_->checkFormat(raw.format, true);
     ctx_->check(vo_set_image_rectified(ctx_->get(), slot, raw.data, raw.width, raw.height, raw.stride, cam_));
   }
   int cols() const { return n_cols_; }
@@ -79,6 +80,8 @@ class StereoCamera {
       if (!im->data || im->width != n_cols_ || im->height != n_rows_)
         throw std::runtime_error(
             "In 'rectifyStereoImages()': provided image has not the same size as the camera model!\n");
+    ctx_->checkFormat(img_left.format, true);
+    ctx_->checkFormat(img_right.format, true);
     ctx_->check(vo_set_image_rectified(ctx_->get(), slot_l, img_left.data, img_left.width, img_left.height,
                                        img_left.stride, 0));
     ctx_->check(vo_set_image_rectified(ctx_->get(), slot_r, img_right.data, img_right.width, img_right.height,

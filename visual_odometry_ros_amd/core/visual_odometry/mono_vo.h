@@ -183,6 +183,7 @@ class MonoVO {
   // MonoVO::trackImage (mono_vo.cpp:496-1194). Throws std::runtime_error where the reference throws.
   void trackImage(const Image &img, const double &timestamp) {
     if (img.width != prm_.width || img.height != prm_.height) throw std::runtime_error("MonoVO: image size differs from the camera model");
+    ctx_->checkFormat(img.format, prm_.flagDoUndistortion);
     const auto t0 = std::chrono::steady_clock::now();
     vo_mvo_frame_info info;
     ctx_->check(vo_mvo_track(mvo_, img.data, img.stride, 0, timestamp, &info));
@@ -191,6 +192,7 @@ class MonoVO {
   // NOT in the reference: the next image handed over early (see vo_mvo_prefetch)
   void enqueueImage(const Image &img, const double &timestamp) {
     t_enq_ = std::chrono::steady_clock::now();
+    ctx_->checkFormat(img.format, prm_.flagDoUndistortion);
     ctx_->check(vo_mvo_enqueue(mvo_, img.data, img.stride, 0, timestamp));
   }
   void prefetchImage(const Image &img) { ctx_->check(vo_mvo_prefetch(mvo_, img.data, img.stride, 0)); }

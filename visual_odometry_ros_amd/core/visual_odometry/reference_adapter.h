@@ -105,6 +105,43 @@ inline vo::Image view(const cv::Mat &m, std::uint64_t stamp = 0) {
   if (m.type() != CV_8UC1) throw std::runtime_error("libvo_hip adapter: CV_8UC1 image expected");
   return vo::Image(m.data, m.cols, m.rows, (int)m.step, image_id(m, stamp));
 }
+// OpenCV's type codes (depth + ((channels - 1) << 3)) where a reduced header set does not bring them
+#ifndef CV_8UC3
+#define CV_8UC3 16
+#endif
+#ifndef CV_16UC1
+#define CV_16UC1 2
+#endif
+#ifndef CV_16SC1
+#define CV_16SC1 3
+#endif
+// The drivers' images. With flagDoUndistortion the reference's ingestion takes what the ROS nodes wrap (bgr8 / rgb8 / mono16 /
+// 32FC1: stereo_vo_ros2.cpp:3-21, :96-99): a 3-channel Mat goes through COLOR_RGB2GRAY whatever its channel order (VO_PIX_RGB8),
+// any depth through convertTo(CV_32FC1). The first image sets the context's input format, a later image of another type
+// throws. 4-channel images keep throwing (the reference makes a 4-channel "gray" image of them, which nothing downstream
+// can use). Without flagDoUndistortion: CV_8UC1 only, as above.
+inline int pixel_format(const cv::Mat &m) {
+  switch (m.type()) {
+    case CV_8UC1: return VO_PIX_MONO8;
+    case CV_8UC3: return VO_PIX_RGB8;
+    case CV_16UC1: return VO_PIX_MONO16U;
+    case CV_16SC1: return VO_PIX_MONO16S;
+    case CV_32FC1: return VO_PIX_F32;
+  }
+  return -1;
+}
+inline vo::Image view(const cv::Mat &m, vo::Context &ctx, bool do_undistortion, bool &format_is_set) {
+  if (!do_undistortion) return view(m);
+  const int f = pixel_format(m);
+  if (f < 0) throw std::runtime_error("libvo_hip adapter: CV_8UC1, CV_8UC3, CV_16UC1, CV_16SC1 or CV_32FC1 image expected");
+  if (!format_is_set) {
+    if (f != ctx.inputFormat()) ctx.setInputFormat(f);
+    format_is_set = true;
+  } else if (f != ctx.inputFormat()) {
+    throw std::runtime_error("libvo_hip adapter: the image's type differs from the first image's");
+  }
+  return vo::Image(m.data, m.cols, m.rows, (int)m.step, 0, f);
+}
 inline vo::Camera intrinsics(CameraConstPtr &cam) { return vo::Camera{cam->fx(), cam->fy(), cam->cx(), cam->cy()}; }
 
 // ---- one device context per adapter object, sized from what the calls bring --------------------------
@@ -340,7 +377,9 @@ class FeatureExtractor {
 // the whole frame — track set carried from frame to frame, new landmarks, keyframes, local BA — runs in libvo_hip.so
 // with the track set on the device (vo::StereoVO, stereo_vo.h next to this file). The reference's constructor
 // (mode, YAML directory) loads a cv::FileStorage: that stays the caller's, the parameters arrive as vo::StereoVOParams
-// (the YAML's numbers). getDebugImage() returns an empty image (no GUI on this path).
+// (the YAML's numbers). getDebugImage(): after setDebugImage(true) — NOT in the reference, where the image is always drawn —
+// the CV_8UC3 picture of the last tracked frame, drawn on the device as stereo_vo.cpp:685-688 draws it (vo_svo_set_debug_image;
+// no window is opened: SURVEY F9); otherwise the empty image.
 class StereoVO {
  public:
   struct AlgorithmStatistics {  // the members the ROS nodes read (ros*/visual_odometry/stereo_vo_ros*.cpp)
@@ -368,11 +407,13 @@ class StereoVO {
       : ctx_(std::make_shared<vo::Context>(device, p.width, p.height,
                                            2 * p.feature_extractor.n_bins_u * p.feature_extractor.n_bins_v + 1024, 5,
                                            p.feature_tracker.max_level)),
-        impl_(ctx_, p) {}
+        impl_(ctx_, p),
+        undistort_(p.flagDoUndistortion) {}
   ~StereoVO() noexcept(false) {}
 
   void trackStereoImages(const cv::Mat &img_left, const cv::Mat &img_right, const double &timestamp) {
-    impl_.trackStereoImages(vo_adapter::view(img_left), vo_adapter::view(img_right), timestamp);
+    const vo::Image il = vo_adapter::view(img_left, *ctx_, undistort_, format_is_set_);
+    impl_.trackStereoImages(il, vo_adapter::view(img_right, *ctx_, undistort_, format_is_set_), timestamp);
     const auto &s = impl_.getStatistics();
     AlgorithmStatistics::FrameStatistics f;
     vo_adapter::from_row_major(s.stats_frame.back().Twc, f.Twc);
@@ -394,7 +435,17 @@ class StereoVO {
     }
   }
   const AlgorithmStatistics &getStatistics() const { return stat_; }
-  const cv::Mat &getDebugImage() { return img_debug_; }
+  void setDebugImage(bool on) {
+    impl_.setDebugImage(on);
+    debug_on_ = on;
+    if (!on) img_debug_ = cv::Mat();
+  }
+  const cv::Mat &getDebugImage() {
+    int w = 0, h = 0;
+    if (debug_on_ && impl_.getDebugImage(debug_rgb_, w, h))
+      img_debug_ = cv::Mat(h, w, CV_8UC3, debug_rgb_.data(), (size_t)3 * (size_t)w);  // (a header over debug_rgb_, valid until the next call)
+    return img_debug_;
+  }
   vo::StereoVO &device() { return impl_; }
 
  private:
@@ -404,7 +455,9 @@ class StereoVO {
   }
   vo::ContextPtr ctx_;
   vo::StereoVO impl_;
+  bool undistort_ = false, format_is_set_ = false, debug_on_ = false;
   AlgorithmStatistics stat_;
+  std::vector<std::uint8_t> debug_rgb_;
   cv::Mat img_debug_;
 };
 
@@ -443,13 +496,14 @@ class MonoVO {
                                            2 * p.feature_extractor.n_bins_u * p.feature_extractor.n_bins_v + 1024, 3,
                                            p.feature_tracker.max_level)),
         impl_(ctx_, p, [this](const vo::PixelVec &a, const vo::PixelVec &b, const float K[4], float R10[9], float t10[3],
-                              std::vector<std::uint8_t> &mask) { return this->five_point(a, b, K, R10, t10, mask); }) {}
+                              std::vector<std::uint8_t> &mask) { return this->five_point(a, b, K, R10, t10, mask); }),
+        undistort_(p.flagDoUndistortion) {}
   ~MonoVO() noexcept(false) {}
 
   void setFivePointSolver(FivePointSolver f) { solver_ = std::move(f); }
 
   void trackImage(const cv::Mat &img, const double &timestamp) {
-    impl_.trackImage(vo_adapter::view(img), timestamp);
+    impl_.trackImage(vo_adapter::view(img, *ctx_, undistort_, format_is_set_), timestamp);
     const auto &s = impl_.getStatistics();
     AlgorithmStatistics::FrameStatistics f;
     vo_adapter::from_row_major(s.stats_frame.back().Twc, f.Twc);
@@ -505,6 +559,7 @@ class MonoVO {
   }
   vo::ContextPtr ctx_;
   vo::MonoVO impl_;
+  bool undistort_ = false, format_is_set_ = false;
   FivePointSolver solver_;
   AlgorithmStatistics stat_;
   cv::Mat img_debug_;

@@ -153,6 +153,8 @@ class StereoVO {
     if (img_left.width != prm_.width || img_left.height != prm_.height || img_right.width != prm_.width ||
         img_right.height != prm_.height || img_left.stride != img_right.stride)
       throw std::runtime_error("StereoVO: image size differs from the camera model");
+    ctx_->checkFormat(img_left.format, prm_.flagDoUndistortion);
+    ctx_->checkFormat(img_right.format, prm_.flagDoUndistortion);
     const auto t0 = std::chrono::steady_clock::now();
     vo_svo_frame_info info;
     ctx_->check(vo_svo_track(svo_, img_left.data, img_right.data, img_left.stride, 0, timestamp, &info));
@@ -163,6 +165,8 @@ class StereoVO {
   // until that pair has been tracked.
   void enqueueStereoImages(const Image &l, const Image &r, const double &timestamp) {
     t_enq_ = std::chrono::steady_clock::now();
+    ctx_->checkFormat(l.format, prm_.flagDoUndistortion);
+    ctx_->checkFormat(r.format, prm_.flagDoUndistortion);
     ctx_->check(vo_svo_enqueue(svo_, l.data, r.data, l.stride, 0, timestamp));
   }
   void prefetchStereoImages(const Image &l, const Image &r) { ctx_->check(vo_svo_prefetch(svo_, l.data, r.data, l.stride, 0)); }
@@ -216,6 +220,17 @@ class StereoVO {
     }
   }
   const vo_svo_frame_info &lastFrameInfo() const { return last_; }
+  // img_debug_ of the reference (stereo_vo.cpp:685-688), drawn on the device (vo_svo_set_debug_image): off by default
+  void setDebugImage(bool on) { ctx_->check(vo_svo_set_debug_image(svo_, on ? 1 : 0)); }
+  // the last picture: rows of width x 3 bytes (cv::Scalar component k in channel k: published as bgr8, (0,255,0) is green);
+  // returns false and leaves `rgb` empty before the first drawn frame
+  bool getDebugImage(std::vector<std::uint8_t> &rgb, int &width, int &height) {
+    ctx_->check(vo_svo_get_debug_image(svo_, nullptr, 0, &width, &height));
+    rgb.assign((size_t)width * (size_t)height * 3, 0);
+    if (rgb.empty()) return false;
+    ctx_->check(vo_svo_get_debug_image(svo_, rgb.data(), 3 * width, &width, &height));
+    return true;
+  }
   // stframe_prev_'s tracked pixels and landmarks (ids, flags: VO_LM_*), for inspection
   void getTracks(std::vector<std::int32_t> &ids, PixelVec &pts_l, PixelVec &pts_r, PointVec &Xw, std::vector<std::uint8_t> &flags) {
     int n = 0;

@@ -35,6 +35,20 @@ class Context {
   // VO_SUM_ORDER_REFERENCE; every class that shares this context follows it from its next call or frame
   void setSumOrder(int order) { check(vo_set_sum_order(ctx_, order)); }
   int sumOrder() const { return check(vo_get_sum_order(ctx_)); }
+  // pixel format of the images the undistorting / rectifying ingestion takes (vo_set_input_format): VO_PIX_MONO8 (the
+  // default) .. VO_PIX_F32. Camera::undistortImage, StereoCamera::rectifyStereoImages and StereoVO / MonoVO with
+  // flagDoUndistortion then take vo::Image of that format; everything else keeps taking u8 planes.
+  void setInputFormat(int format) {
+    check(vo_set_input_format(ctx_, format));
+    format_ = format;
+  }
+  int inputFormat() const { return format_; }
+  // an image handed to the rectifying ingestion (rectifying = true) must be of the context's format, any other a u8 plane
+  void checkFormat(int image_format, bool rectifying) const {
+    if (image_format != (rectifying ? format_ : (int)VO_PIX_MONO8))
+      throw std::runtime_error(rectifying ? "libvo_hip: the image's pixel format differs from the context's (Context::setInputFormat)"
+                                          : "libvo_hip: only the undistorting / rectifying ingestion converts pixel formats: a u8 plane expected");
+  }
   // maps the reference's throw sites / return-false onto the C status codes
   int check(int rc) const {
     if (rc < 0) throw std::runtime_error(vo_last_error(ctx_));
@@ -44,6 +58,7 @@ class Context {
  private:
   vo_ctx *ctx_ = nullptr;
   int n_slots_ = 0;
+  int format_ = VO_PIX_MONO8;
 };
 using ContextPtr = std::shared_ptr<Context>;
 

@@ -598,6 +598,9 @@ extern "C" int vo_debug_set(vo_ctx *c, int key, int value) {
   c->dbg[key] = value;
   return VO_OK;
 }
+// a frame operator of this context (stereo or mono) has been enqueued and its result not collected
+bool vo_frame_in_flight(const vo_ctx *c) { return (c->frame && c->frame->pending) || c->frame_slots_busy; }
+
 extern "C" int vo_debug_allocation_count(const vo_ctx *c, long long *count) {
   if (!c || !count) return VO_ERR_INVALID;
   *count = c->n_allocs;

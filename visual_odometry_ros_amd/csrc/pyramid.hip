@@ -23,6 +23,7 @@
 #include "vo_kernels.hpp"
 #define PYR_SET_PRIO()
 #include "pyr_plan.hpp"
+#include "ingest_formats.hpp"  // remap_sample (MONO8) and the samples of the other input formats
 
 // level 0 of an image that goes through Camera::undistortImage / StereoCamera::rectifyStereoImages first
 // (core/visual_odometry/camera.cpp:166-183, :300-336: convertTo(CV_32FC1), cv::remap with float maps,
@@ -38,21 +39,10 @@ struct RemapArgs {
   uint8_t *dst[2];
   int w, h, sstride, dstride;
 };
-__device__ __forceinline__ int remap_sample(const uint8_t *__restrict__ src, int w, int h, int sstride, float mu,
-                                            float mv) {
-  if (!(mu == mu) || !(mv == mv)) return 0;  // cvRound(NaN) = INT_MIN on the CPU: far outside
-  const int fxq = (int)__builtin_rintf(mu * 32.0f), fyq = (int)__builtin_rintf(mv * 32.0f);  // saturating cvt
-  const int sx = fxq >> 5, sy = fyq >> 5, ax = fxq & 31, ay = fyq & 31;
-  if (sx >= w || sx + 1 < 0 || sy >= h || sy + 1 < 0) return 0;
-  const bool x0 = sx >= 0, x1 = sx + 1 < w, y0 = sy >= 0, y1 = sy + 1 < h;
-  const uint8_t *p = src + (ptrdiff_t)sy * sstride + sx;
-  const int s00 = (x0 && y0) ? p[0] : 0, s01 = (x1 && y0) ? p[1] : 0;
-  const int s10 = (x0 && y1) ? p[sstride] : 0, s11 = (x1 && y1) ? p[sstride + 1] : 0;
-  const int sum = s00 * ((32 - ay) * (32 - ax)) + s01 * ((32 - ay) * ax) + s10 * (ay * (32 - ax)) + s11 * (ay * ax);
-  return (sum + 511 + ((sum >> 10) & 1)) >> 10;  // round half to even of sum / 1024 (<= 255)
-}
 // One lane per padded pixel: the two map loads of a wavefront are 256 contiguous bytes each (the maps are
 // 80 % of this kernel's bytes); four neighbouring lanes then pack their bytes so that the store is a dword.
+// FMT = VO_PIX_*: the source's pixel format (vo_set_input_format); VO_PIX_MONO8 is the kernel of the u8 path as it always was.
+template <int FMT>
 __global__ __launch_bounds__(256) void remap_level0_kernel(RemapArgs a) {
   const int pxp = blockIdx.x * blockDim.x + threadIdx.x;  // padded column (the padded row is a multiple of 4 wide)
   const int py = blockIdx.y;
@@ -63,7 +53,7 @@ __global__ __launch_bounds__(256) void remap_level0_kernel(RemapArgs a) {
     const int y = reflect101_dev(py - VO_PAD, a.h);
     const int x = reflect101_dev(pxp - VO_PAD, a.w);
     const size_t o = (size_t)y * a.w + x;
-    val = remap_sample(a.src[z], a.w, a.h, a.sstride, a.mu[z][o], a.mv[z][o]);
+    val = ingest_sample<FMT>(a.src[z], a.w, a.h, a.sstride, a.mu[z][o], a.mv[z][o]);
   }
   uint32_t v = (uint32_t)val;
   v |= (uint32_t)__shfl_down(val, 1) << 8;
@@ -145,7 +135,14 @@ static int build(vo_ctx *c, int slot_l, const uint8_t *d_l, int slot_r, const ui
     a.sstride = stride;
     a.dstride = P[0]->lv[0].stride;
     dim3 grid((w + 2 * VO_PAD + 3 + 255) / 256, h + 2 * VO_PAD, nimg);
-    hipLaunchKernelGGL(remap_level0_kernel, grid, dim3(256), 0, c->stream, a);
+    switch (c->input_format) {
+      case VO_PIX_MONO8: hipLaunchKernelGGL(remap_level0_kernel<VO_PIX_MONO8>, grid, dim3(256), 0, c->stream, a); break;
+      case VO_PIX_RGB8: hipLaunchKernelGGL(remap_level0_kernel<VO_PIX_RGB8>, grid, dim3(256), 0, c->stream, a); break;
+      case VO_PIX_BGR8: hipLaunchKernelGGL(remap_level0_kernel<VO_PIX_BGR8>, grid, dim3(256), 0, c->stream, a); break;
+      case VO_PIX_MONO16U: hipLaunchKernelGGL(remap_level0_kernel<VO_PIX_MONO16U>, grid, dim3(256), 0, c->stream, a); break;
+      case VO_PIX_MONO16S: hipLaunchKernelGGL(remap_level0_kernel<VO_PIX_MONO16S>, grid, dim3(256), 0, c->stream, a); break;
+      default: hipLaunchKernelGGL(remap_level0_kernel<VO_PIX_F32>, grid, dim3(256), 0, c->stream, a); break;
+    }
   }
   // every level (and, unless the remap wrote it, level 0 with its border) by ONE launch per PYR_NL_MAX levels
   vo_level L[2][VO_MAX_LEVELS];

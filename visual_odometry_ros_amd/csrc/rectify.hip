@@ -270,6 +270,54 @@ extern "C" int vo_rectify_get_maps(vo_ctx *c, int cam, float *map_u, float *map_
 }
 
 // ---- image ingestion through the maps ---------------------------------------------------
+static int fmt_bytes(int format) {
+  switch (format) {
+    case VO_PIX_MONO8: return 1;
+    case VO_PIX_RGB8:
+    case VO_PIX_BGR8: return 3;
+    case VO_PIX_MONO16U:
+    case VO_PIX_MONO16S: return 2;
+    case VO_PIX_F32: return 4;
+  }
+  return 0;
+}
+
+// The pixel format of what the rectifying entry points are given. The staging buffers of host images grow here, once per
+// size, and nowhere else; a frame in flight may still read them, so the format cannot change under it.
+extern "C" int vo_set_input_format(vo_ctx *c, int format) {
+  if (!c) return VO_ERR_INVALID;
+  const int bpp = fmt_bytes(format);
+  if (!bpp) VO_FAIL(c, VO_ERR_INVALID, "unknown input format %d (VO_PIX_MONO8 .. VO_PIX_F32)", format);
+  if (vo_frame_in_flight(c)) VO_FAIL(c, VO_ERR_INVALID, "a frame is in flight: collect its result before changing the input format");
+  if (bpp > c->stage_bpp) {
+    VO_CHECK_HIP(c, hipSetDevice(c->device));
+    VO_CHECK_HIP(c, hipStreamSynchronize(c->stream2));  // the staging buffers' last use, whichever stream it was on
+    VO_CHECK_HIP(c, hipStreamSynchronize(c->stream_main));
+    const size_t px = (size_t)c->cfg.max_width * c->cfg.max_height;
+    uint8_t *h = nullptr, *d = nullptr;
+    const size_t h_bytes = px * bpp + (c->h_stage_bytes - px);
+    VO_CHECK_HIP(c, vo_host_malloc(c, (void **)&h, h_bytes, hipHostMallocDefault));
+    if (vo_dev_malloc(c, (void **)&d, px * bpp) != hipSuccess) {
+      (void)hipHostFree(h);
+      VO_FAIL(c, VO_ERR_HIP, "no device memory for a staging image of %d bytes per pixel", bpp);
+    }
+    (void)hipHostFree(c->h_stage);
+    (void)hipFree(c->d_img_stage);
+    c->h_stage = h;
+    c->h_stage_bytes = h_bytes;
+    c->d_img_stage = d;
+    c->stage_bpp = bpp;
+  }
+  c->input_format = format;
+  return VO_OK;
+}
+
+extern "C" int vo_get_input_format(vo_ctx *c, int *format) {
+  if (!c || !format) return VO_ERR_INVALID;
+  *format = c->input_format;
+  return VO_OK;
+}
+
 extern "C" int vo_set_image_rectified_device(vo_ctx *c, int slot, const void *dev, int width, int height, int stride,
                                              int cam) {
   if (!c || !dev) return VO_ERR_INVALID;
@@ -294,9 +342,10 @@ extern "C" int vo_set_image_rectified(vo_ctx *c, int slot, const uint8_t *host, 
   VO_CHECK_HIP(c, hipSetDevice(c->device));
   vo_ingest_scope ingest(c);
   SYNC();  // the previous use of the staging buffers must have drained
-  for (int y = 0; y < height; ++y) memcpy(c->h_stage + (size_t)y * width, host + (size_t)y * stride, (size_t)width);
-  H2D(c->d_img_stage, c->h_stage, (size_t)width * height);
-  int rc = vo_pyramid_build_rectified(c, slot, c->d_img_stage, width, height, width, cam);
+  const size_t row = (size_t)width * fmt_bytes(c->input_format);  // (vo_set_input_format sized both buffers for it)
+  for (int y = 0; y < height; ++y) memcpy(c->h_stage + (size_t)y * row, host + (size_t)y * stride, row);
+  H2D(c->d_img_stage, c->h_stage, row * height);
+  int rc = vo_pyramid_build_rectified(c, slot, c->d_img_stage, width, height, (int)row, cam);
   if (rc) return rc;
   SYNC();
   return VO_OK;

@@ -267,6 +267,10 @@ extern "C" void vo_svo_destroy(vo_svo *s) {
   if (s->d_acc_bin) (void)hipFree(s->d_acc_bin);
   if (s->d_hdr) (void)hipFree(s->d_hdr);
   if (s->h_hdr) (void)hipHostFree(s->h_hdr);
+  if (s->dbg.have) (void)hipEventSynchronize(s->dbg.done);
+  vo_draw_buffers_free(&s->dbg.buf);
+  if (s->dbg.fork) (void)hipEventDestroy(s->dbg.fork);
+  if (s->dbg.done) (void)hipEventDestroy(s->dbg.done);
   vo_svo_lba_free(s);
   delete s;
 }
@@ -323,6 +327,53 @@ extern "C" int vo_svo_prefetch(vo_svo *s, const void *left, const void *right, i
 }
 
 static int svo_first_frame(vo_svo *s);
+
+// showTrackingBA("stereo_tracking", I1_left, PixelVec(), lmtrack_final.pts_l1) (stereo_vo.cpp:685-688) for the frame just
+// enqueued: behind its last launch, on the side stream. lmtrack_final = the survivors = the first n_surv entries of the track set
+// the BA launch leaves behind; the count is read on the device. One picture is in flight at most: the previous one (a frame
+// old) has long arrived, so the wait below costs nothing and keeps the buffers and the slot it read from being reused under it.
+static int svo_draw(vo_svo *s) {
+  vo_ctx *c = s->c;
+  if (s->dbg.have) VO_CHECK_HIP(c, hipEventSynchronize(s->dbg.done));
+  VO_CHECK_HIP(c, hipEventRecord(s->dbg.fork, c->stream_main));
+  VO_CHECK_HIP(c, hipStreamWaitEvent(c->stream2, s->dbg.fork, 0));
+  RC(vo_draw_ba_enqueue(c, c->stream2, s->slot[S_CL], s->ts[s->cur ^ 1].pts_l, &s->d_hdr->n_surv, s->cap, &s->dbg.buf));
+  VO_CHECK_HIP(c, hipEventRecord(s->dbg.done, c->stream2));
+  s->dbg.have = true;
+  s->dbg.w = s->prm.frame.width;
+  s->dbg.h = s->prm.frame.height;
+  s->dbg.recoveries = c->frame_recoveries;
+  return VO_OK;
+}
+
+extern "C" int vo_svo_set_debug_image(vo_svo *s, int on) {
+  if (!s) return VO_ERR_INVALID;
+  vo_ctx *c = s->c;
+  if (s->pending) VO_FAIL(c, VO_ERR_INVALID, "call vo_svo_result first");
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  if (on && !s->dbg.buf.idx) {  // the only allocation of the option
+    RC(vo_draw_buffers_alloc(c, &s->dbg.buf));
+    VO_CHECK_HIP(c, hipEventCreateWithFlags(&s->dbg.fork, hipEventDisableTiming));
+    VO_CHECK_HIP(c, hipEventCreateWithFlags(&s->dbg.done, hipEventDisableTiming));
+  }
+  s->dbg.on = on != 0;
+  return VO_OK;
+}
+
+extern "C" int vo_svo_get_debug_image(vo_svo *s, uint8_t *out, int out_stride, int *width, int *height) {
+  if (!s || !width || !height) return VO_ERR_INVALID;
+  vo_ctx *c = s->c;
+  *width = *height = 0;
+  if (!s->dbg.have) return VO_OK;  // no frame has drawn yet (the first pair of a stream does not)
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  VO_CHECK_HIP(c, hipEventSynchronize(s->dbg.done));  // that picture only: nothing else on the device is waited for
+  *width = s->dbg.w;
+  *height = s->dbg.h;
+  if (!out) return VO_OK;
+  if (out_stride < 3 * s->dbg.w) VO_FAIL(c, VO_ERR_INVALID, "out_stride %d is below 3 x width = %d", out_stride, 3 * s->dbg.w);
+  for (int y = 0; y < s->dbg.h; ++y) memcpy(out + (size_t)y * out_stride, s->dbg.buf.h_img + (size_t)y * 3 * s->dbg.w, (size_t)3 * s->dbg.w);
+  return VO_OK;
+}
 
 extern "C" int vo_svo_enqueue(vo_svo *s, const void *left, const void *right, int stride, int on_device, double timestamp) {
   if (!s || !left || !right) return VO_ERR_INVALID;
@@ -437,6 +488,7 @@ extern "C" int vo_svo_enqueue(vo_svo *s, const void *left, const void *right, in
   if (rc < 0) return undo(rc);
   s->pending = true;
   s->pending_first = false;
+  if (s->dbg.on) RC(svo_draw(s));
   if (g_trace) s->ht.acc[1] += svo_now() - t_in;
   return VO_OK;
 }
@@ -567,6 +619,8 @@ extern "C" int vo_svo_result(vo_svo *s, vo_svo_frame_info *info) {
     }
   }
 #endif
+  // (a frame that was issued again after a device-side join time-out left its track set behind a second time: so is its picture)
+  if (s->dbg.on && s->dbg.recoveries != c->frame_recoveries) RC(svo_draw(s));
   const SvoHdr h = *s->h_hdr;
   if (h.overflow) VO_FAIL(c, VO_ERR_CAPACITY, "the next track set (%d) exceeds vo_config.max_points=%d", h.n_next, s->cap);
   I.n_tracks_in = s->n;

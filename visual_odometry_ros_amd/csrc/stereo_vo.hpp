@@ -4,6 +4,7 @@
 
 #include "svo_device.hpp"
 #include "vo_internal.hpp"
+#include "vo_kernels.hpp"
 
 // Keyframe-centric storage of what the reference keeps per landmark (getObservationsOnKeyframes / getRelatedKeyframePtr):
 // a keyframe holds its related landmarks' ids and both pixels. The ids of a track set are ASCENDING and dense (survivors
@@ -40,6 +41,13 @@ struct vo_svo {
   int n_keyframes = 0, n_kf_lms = 0;
   // landmark table, keyframe ring, window scratch and the solver's arena, all on the device (stereo_vo_lba.hip)
   struct vo_svo_lba *lba = nullptr;
+  // vo_svo_set_debug_image: img_debug_ of the reference (stereo_vo.cpp:685-688), drawn on the side stream behind every frame
+  struct {
+    bool on = false, have = false;  // switched on; a picture has been enqueued (dbg.done says when it is there)
+    vo_draw_buffers buf = {};
+    hipEvent_t fork = nullptr, done = nullptr;
+    int w = 0, h = 0, recoveries = 0;
+  } dbg;
   int mono = 0;  // the keyframe storage serves a MonoVO (mono_vo.hip): one observation per keyframe entry, bundled flags
   // all_stkeyframes_ (stats_keyframe): every keyframe's current pose (host) and where its related landmarks' ids are kept
   // on the device (a pool that only grows)

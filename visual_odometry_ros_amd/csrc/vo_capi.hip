@@ -131,6 +131,7 @@ extern "C" int vo_create(const vo_config *cfg, vo_ctx **out) {
   c->h_stage_bytes = (size_t)cfg->max_width * cfg->max_height + 64 * N + 4096;
   VO_CHECK_HIP(c, vo_host_malloc(c, (void **)&c->h_stage, c->h_stage_bytes, hipHostMallocDefault));
   VO_CHECK_HIP(c, vo_dev_malloc(c, (void **)&c->d_img_stage, (size_t)cfg->max_width * cfg->max_height));
+  c->stage_bpp = 1;
   VO_CHECK_HIP(c, hipStreamSynchronize(c->stream));
   return VO_OK;
 }
@@ -143,6 +144,7 @@ extern "C" void vo_destroy(vo_ctx *c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   vo_frame_free(c);
   vo_rectify_free(c);
+  vo_draw_free(c);
   vo_sba_free(c);
   vo_orb_describe_free(c);
   vo_orb_free(c);
@@ -303,12 +305,14 @@ extern "C" int vo_pyramid_levels(int width, int height, int win, int max_level) 
 
 extern "C" int vo_set_image_device(vo_ctx *c, int slot, const void *dev, int width, int height, int stride) {
   if (!c || !dev) return VO_ERR_INVALID;
+  VO_NEED_MONO8(c, "vo_set_image_device");
   VO_CHECK_HIP(c, hipSetDevice(c->device));
   return vo_pyramid_build(c, slot, (const uint8_t *)dev, width, height, stride);
 }
 
 extern "C" int vo_set_image(vo_ctx *c, int slot, const uint8_t *host, int width, int height, int stride) {
   if (!c || !host) return VO_ERR_INVALID;
+  VO_NEED_MONO8(c, "vo_set_image");
   if (width <= 0 || height <= 0 || width > c->cfg.max_width || height > c->cfg.max_height)
     VO_FAIL(c, VO_ERR_CAPACITY, "image %dx%d exceeds vo_config %dx%d", width, height, c->cfg.max_width,
             c->cfg.max_height);
@@ -327,6 +331,7 @@ extern "C" int vo_set_image(vo_ctx *c, int slot, const uint8_t *host, int width,
 extern "C" int vo_set_stereo_pair_device(vo_ctx *c, int slot_l, const void *dev_l, int slot_r, const void *dev_r,
                                          int width, int height, int stride) {
   if (!c || !dev_l || !dev_r) return VO_ERR_INVALID;
+  VO_NEED_MONO8(c, "vo_set_stereo_pair_device");
   VO_CHECK_HIP(c, hipSetDevice(c->device));
   return vo_pyramid_build_pair(c, slot_l, (const uint8_t *)dev_l, slot_r, (const uint8_t *)dev_r, width, height,
                                stride);
@@ -343,6 +348,7 @@ extern "C" int vo_set_ingest_side_stream(vo_ctx *c, int on) {
 extern "C" int vo_set_stereo_pair_host_async(vo_ctx *c, int slot_l, const uint8_t *host_l, int slot_r,
                                              const uint8_t *host_r, int width, int height, int stride) {
   if (!c || !host_l || !host_r) return VO_ERR_INVALID;
+  VO_NEED_MONO8(c, "vo_set_stereo_pair_host_async");
   if (slot_l < 0 || slot_l >= c->cfg.n_slots || slot_r < 0 || slot_r >= c->cfg.n_slots || slot_l == slot_r)
     VO_FAIL(c, VO_ERR_INVALID, "slot out of range");
   if (width <= 0 || height <= 0 || width > c->cfg.max_width || height > c->cfg.max_height || stride < width)
@@ -378,6 +384,7 @@ extern "C" int vo_set_stereo_pair_host_async(vo_ctx *c, int slot_l, const uint8_
 // slot's staging plane and the pyramid chain on the ingest stream; consumers wait for the slot's event on the device.
 int vo_set_image_host_async(vo_ctx *c, int slot, const uint8_t *host, int width, int height, int stride) {
   if (!c || !host) return VO_ERR_INVALID;
+  VO_NEED_MONO8(c, "vo_set_image (asynchronous form)");
   if (slot < 0 || slot >= c->cfg.n_slots) VO_FAIL(c, VO_ERR_INVALID, "slot out of range");
   if (width <= 0 || height <= 0 || width > c->cfg.max_width || height > c->cfg.max_height || stride < width)
     VO_FAIL(c, VO_ERR_CAPACITY, "image %dx%d exceeds vo_config %dx%d", width, height, c->cfg.max_width, c->cfg.max_height);

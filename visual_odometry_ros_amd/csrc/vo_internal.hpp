@@ -68,6 +68,9 @@ struct vo_ctx {
   uint8_t *h_stage;
   size_t h_stage_bytes;
   uint8_t *d_img_stage;    // device staging for host images
+  // vo_set_input_format (rectify.hip): what the rectifying entry points take; both staging buffers hold stage_bpp bytes per pixel
+  int input_format;        // VO_PIX_*, 0 = VO_PIX_MONO8
+  int stage_bpp;
   // hamming
   uint8_t *d_desc_a, *d_desc_b;
   uint16_t *d_dist;
@@ -97,6 +100,7 @@ struct vo_ctx {
   struct vo_sba_state *sba;  // device arena of the sparse local BA (sba.hip)
   struct vo_orb_state *orb;  // pyramid, score planes and candidate lists of the keypoint detector (orb_detect.hip)
   struct vo_orb_desc_state *orb_desc;  // pattern table, resident descriptor sets (orb_describe.hip)
+  struct vo_draw_state *draw;          // index plane and picture of the debug image (draw.hip), allocated on first use
   // every device / pinned allocation made on behalf of this context (vo_dev_malloc / vo_host_malloc): what
   // vo_debug_allocation_count reports, so that a test can assert that a steady-state frame allocates nothing
   long long n_allocs;
@@ -127,6 +131,15 @@ static inline hipError_t vo_host_malloc(vo_ctx *c, void **p, size_t bytes, unsig
   do {                                                         \
     snprintf((ctx)->err, sizeof((ctx)->err), __VA_ARGS__);     \
     return (code);                                             \
+  } while (0)
+
+// The entry points without a remap take u8 planes only (vo_set_input_format).
+#define VO_NEED_MONO8(ctx, name)                                                                                      \
+  do {                                                                                                               \
+    if ((ctx)->input_format != VO_PIX_MONO8)                                                                          \
+      VO_FAIL(ctx, VO_ERR_INVALID,                                                                                   \
+              name ": the context's input format is not VO_PIX_MONO8 and this entry point does not convert; use the " \
+                   "rectifying entry points (identity maps via vo_rectify_set_maps for undistorted data)");          \
   } while (0)
 
 // A call needs pyramid levels 0..eff of a slot. Fewer were built when vo_config.max_level is below the call's

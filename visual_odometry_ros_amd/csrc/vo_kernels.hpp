@@ -66,6 +66,22 @@ int vo_pyramid_build_pair_rectified(vo_ctx *c, int slot_l, const uint8_t *d_l, i
 // rectify.hip
 void vo_rectify_free(vo_ctx *c);
 
+// frame_pipeline.hip
+bool vo_frame_in_flight(const vo_ctx *c);
+
+// draw.hip
+void vo_draw_free(vo_ctx *c);
+struct vo_draw_buffers {  // what one picture needs: the index plane, the picture on the device and its pinned copy
+  uint32_t *idx;
+  uint8_t *img, *h_img;
+  size_t img_bytes;
+};
+int vo_draw_buffers_alloc(vo_ctx *c, vo_draw_buffers *b);  // sized by vo_config.max_width x max_height
+void vo_draw_buffers_free(vo_draw_buffers *b);
+// The drivers' form of showTrackingBA(level 0 of `slot`, {}, d_pts_proj[0 .. min(*d_n, cap))): both launches and the copy into
+// b->h_img on stream `st`. Points and count are DEVICE memory — the count need not be known to the host when this is enqueued.
+int vo_draw_ba_enqueue(vo_ctx *c, hipStream_t st, int slot, const float *d_pts_proj, const int *d_n, int cap, vo_draw_buffers *b);
+
 // sba.hip
 void vo_sba_free(vo_ctx *c);
 
