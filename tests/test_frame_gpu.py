@@ -14,18 +14,22 @@ def rel_frob(A, B):
     return np.linalg.norm(np.asarray(A, np.float64) - np.asarray(B, np.float64)) / np.linalg.norm(B)
 
 
-def _run_stream(ctx, oracle, stream, n_frames, strict, win=21, max_level=6, sanity=True, untri=None):
+def _run_stream(ctx, oracle, stream, n_frames, strict, win=21, max_level=6, sanity=True, untri=None, min_inlier_frac=None):
     """untri: fraction of the track set whose landmark is NOT triangulated (stereo_vo.cpp:490, :515-519, :599);
-    None = no flag array at all (every landmark triangulated)."""
-    prm_g = make_stereo_params(stream.width, stream.height, win, max_level, 80.0, 0.5, 3.0, stream.K, stream.K,
+    None = no flag array at all (every landmark triangulated). The right intrinsics are the stream's .Kr where it has one
+    (util.RigStream), its .K otherwise. min_inlier_frac: every frame must keep more than that share of its features as BA
+    inliers (for streams too small for the pose-against-truth bar of `sanity`). Returns the largest relative Frobenius
+    deviation of dT from the oracle's, (against SUM_TREE, against SUM_SEQ)."""
+    Kr = getattr(stream, "Kr", stream.K)
+    prm_g = make_stereo_params(stream.width, stream.height, win, max_level, 80.0, 0.5, 3.0, stream.K, Kr,
                                stream.T_lr)
     prm_o = oracle.make_stereo_params(stream.width, stream.height, win, max_level, 80.0, 0.5, 3.0, stream.K,
-                                      stream.K, stream.T_lr)
+                                      Kr, stream.T_lr)
     pipe = StereoFramePipeline(ctx, prm_g, strict_border=strict)
     poses = stream.poses(n_frames)
     Lp, Rp, _ = stream.render_pair(poses[0])
     ctx.set_image(0, Lp)
-    worst = 0.0
+    worst = worst_s = 0.0
     for k in range(1, n_frames):
         L, R, _ = stream.render_pair(poses[k])
         ts = stream.track_set(k - 1, poses[k - 1], poses[k])
@@ -71,8 +75,11 @@ def _run_stream(ctx, oracle, stream, n_frames, strict, win=21, max_level=6, sani
         os_ = oracle.stereo_frame(prm_o, Lp, L, R, ts["pts_l0"], ts["pts_r0"], ts["Xp"], ts["dT_prior"],
                                   ts["pts_new"], oracle.SUM_SEQ, 0,
                                   oracle.IC_REFERENCE if strict else oracle.IC_MASKED, 8, lm_flags=fl)
+        worst_s = max(worst_s, rel_frob(g["dT"], os_["dT"]))
         assert rel_frob(g["dT"], os_["dT"]) < 1e-4
         assert np.array_equal(g["stage"], os_["stage"])
+        if min_inlier_frac is not None:
+            assert g["counts"].n_inlier > min_inlier_frac * n
         # and the estimate is a sane odometry result
         if sanity and n_tri > 0.5 * n:
             assert rel_frob(g["dT"], ts["dT_true"]) < 5e-3
@@ -81,7 +88,7 @@ def _run_stream(ctx, oracle, stream, n_frames, strict, win=21, max_level=6, sani
             assert g["counts"].n_ba == 0 and np.allclose(g["dT"], ts["dT_prior"], atol=1e-6)
         ctx.swap_slots(0, 1)  # current left becomes previous left
         Lp = L
-    return worst
+    return worst, worst_s
 
 
 @pytest.mark.parametrize("strict", [False, True, 3, 5])

@@ -13,16 +13,15 @@ def rel_frob(A, B):
     return np.linalg.norm(np.asarray(A, np.float64) - np.asarray(B, np.float64)) / np.linalg.norm(B)
 
 
-@pytest.mark.parametrize("n,seed", [(500, 1), (1500, 2), (37, 3), (3000, 4), (1, 5)])
-def test_stereo_gn_parity(ctx, vo, oracle, n, seed):
-    d = S.two_view_points(n=n, seed=seed)
+def stereo_gn_parity(ctx, vo, oracle, d, Kr, T0):
+    """The parity assertions of the stereo pose-only BA on one input (d: a two-view dict, Kr: right intrinsics, T0: initial
+    pose). Returns the relative Frobenius deviation of the pose from oracle(SUM_SEQ)."""
     me = vo.MotionEstimator(ctx, True, d["T_lr"])
-    T0 = np.eye(4, dtype=np.float32)
-    ok, T, mask, info = me.poseOnlyBundleAdjustment_Stereo(d["X"], d["pts_l"], d["pts_r"], d["K"], d["K"],
+    ok, T, mask, info = me.poseOnlyBundleAdjustment_Stereo(d["X"], d["pts_l"], d["pts_r"], d["K"], Kr,
                                                           d["T_lr"], 3.0, T0)
-    rc_t, T_t, mask_t, info_t = oracle.gn_pose_stereo(d["X"], d["pts_l"], d["pts_r"], d["K"], d["K"],
+    rc_t, T_t, mask_t, info_t = oracle.gn_pose_stereo(d["X"], d["pts_l"], d["pts_r"], d["K"], Kr,
                                                       d["T_lr"], 3.0, T0, oracle.SUM_TREE, GN_T)
-    rc_s, T_s, mask_s, info_s = oracle.gn_pose_stereo(d["X"], d["pts_l"], d["pts_r"], d["K"], d["K"],
+    rc_s, T_s, mask_s, info_s = oracle.gn_pose_stereo(d["X"], d["pts_l"], d["pts_r"], d["K"], Kr,
                                                       d["T_lr"], 3.0, T0, oracle.SUM_SEQ, 0)
     assert ok == bool(rc_t) == bool(rc_s)
     # same summation tree: iteration count and inlier mask identical, pose to float rounding
@@ -35,14 +34,19 @@ def test_stereo_gn_parity(ctx, vo, oracle, n, seed):
     assert rel_frob(T, T_s) < 1e-4
     assert np.array_equal(mask, mask_s)
     assert info.cnt_invalid == info_s.cnt_invalid
+    return rel_frob(T, T_s)
 
 
-@pytest.mark.parametrize("variant", [0, 1])
-@pytest.mark.parametrize("n,seed", [(500, 1), (1000, 7)])
-def test_mono_gn_parity(ctx, vo, oracle, n, seed, variant):
+@pytest.mark.parametrize("n,seed", [(500, 1), (1500, 2), (37, 3), (3000, 4), (1, 5)])
+def test_stereo_gn_parity(ctx, vo, oracle, n, seed):
     d = S.two_view_points(n=n, seed=seed)
+    stereo_gn_parity(ctx, vo, oracle, d, d["K"], np.eye(4, dtype=np.float32))
+
+
+def mono_gn_parity(ctx, vo, oracle, d, R0, t0, variant):
+    """The parity assertions of the mono pose-only BA on one input. Returns the relative Frobenius deviation of the pose
+    from oracle(SUM_SEQ)."""
     me = vo.MotionEstimator(ctx)
-    R0, t0 = np.eye(3, dtype=np.float32), np.zeros(3, np.float32)
     ok, R, t, mask, info = me.poseOnlyBundleAdjustment(d["X"], d["pts_l"], d["K"], 3, R0, t0, variant)
     rc_t, R_t, t_t, mask_t, info_t = oracle.gn_pose_mono(d["X"], d["pts_l"], d["K"], 3, R0, t0, variant,
                                                          oracle.SUM_TREE, GN_T)
@@ -58,6 +62,14 @@ def test_mono_gn_parity(ctx, vo, oracle, n, seed, variant):
     assert np.array_equal(np.asarray(t).view(np.uint32), t_t.view(np.uint32))
     assert rel_frob(T, Ts) < 1e-4
     assert np.array_equal(mask, mask_s)
+    return rel_frob(T, Ts)
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+@pytest.mark.parametrize("n,seed", [(500, 1), (1000, 7)])
+def test_mono_gn_parity(ctx, vo, oracle, n, seed, variant):
+    d = S.two_view_points(n=n, seed=seed)
+    mono_gn_parity(ctx, vo, oracle, d, np.eye(3, dtype=np.float32), np.zeros(3, np.float32), variant)
 
 
 def test_se3_exp_device_unit(ctx, vo, oracle):

@@ -56,7 +56,14 @@ def test_compaction_indices(ctx, oracle, n):
     assert compact_indices(ctx, np.zeros(n, bool)).size == 0
 
 
-def test_calc_prior(ctx, vo, oracle):
+# the camera these tests always had (fx == fy) and one with fx != fy whose principal point is neither centred (1241 x 376)
+# nor the same in x and y: a swap of fx / fy or cx / cy, or fx used for both, shows in the second only
+CAMERAS = [(718.856, 718.856, 607.19, 185.2), (707.09, 731.4, 583.62, 201.37)]
+CAMERA_IDS = ["fx_eq_fy", "fx_ne_fy"]
+
+
+@pytest.mark.parametrize("cam", CAMERAS, ids=CAMERA_IDS)
+def test_calc_prior(ctx, vo, oracle, cam):
     rng = np.random.default_rng(2)
     n = 700
     pts0 = rng.uniform(0, 1000, (n, 2)).astype(np.float32)
@@ -64,18 +71,19 @@ def test_calc_prior(ctx, vo, oracle):
     Xw[:, 2] = np.abs(Xw[:, 2]) + 2
     Tw1 = S.se3_exp([0.3, -0.1, 1.2, 0.02, -0.03, 0.01]).astype(np.float32)
     Xw[10] = Tw1[:3, 3]  # exactly at the camera centre: ||X|| == 0 -> keeps pts0
-    K = np.array([[718.856, 0, 607.19], [0, 718.856, 185.2], [0, 0, 1]], np.float32)
+    K = np.array([[cam[0], 0, cam[2]], [0, cam[1], cam[3]], [0, 0, 1]], np.float32)
     ft = vo.FeatureTracker(ctx)
     out = ft.calcPrior(pts0, Xw, Tw1, K)
     ref = oracle.calc_prior(pts0, Xw, Tw1, K)
     assert np.array_equal(out.view(np.uint32), ref.view(np.uint32))
 
 
-@pytest.mark.parametrize("n", [1, 255, 256, 1500, 8000])
-def test_epipolar_distances_bit_exact(ctx, vo, oracle, n):
+@pytest.mark.parametrize("n,cam", [pytest.param(n, cam, id=str(n) if i == 0 else f"{n}-{CAMERA_IDS[i]}")
+                                   for i, cam in enumerate(CAMERAS) for n in (1, 255, 256, 1500, 8000)])
+def test_epipolar_distances_bit_exact(ctx, vo, oracle, n, cam):
     """calcSampsonDistance / calcSymmetricEpipolarDistance (motion_estimator.cpp:538-653) vs the oracle."""
     rng = np.random.default_rng(n)
-    K = np.array([718.856, 718.856, 607.19, 185.2], np.float32)
+    K = np.array(cam, np.float32)
     ang = 0.015
     R10 = np.array([[np.cos(ang), 0, np.sin(ang)], [0, 1, 0], [-np.sin(ang), 0, np.cos(ang)]], np.float32)
     t10 = np.array([0.05, -0.02, -0.8], np.float32)

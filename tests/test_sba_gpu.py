@@ -7,6 +7,7 @@ import pytest
 
 from visual_odometry_ros_amd import synthetic as S
 from visual_odometry_ros_amd.api import SparseBundleAdjustmentSolver
+from util import RIG_KITTI, sba_converged
 from util import sba_run as _run  # device next to oracle.sba_solve at the bar of the docstring above
 
 pytestmark = pytest.mark.gpu
@@ -42,6 +43,12 @@ def test_sba_quirks_and_edges(ctx, oracle, vo):
     T_lr[:3, 3] = [0.537, 0.004, -0.003]
     p = S.ba_window(n_kf=6, n_points=400, stereo=True, seed=2, T_lr=T_lr)
     _run(ctx, oracle, p)
+    # the same rig with two different cameras (fx != fy in both): right observations projected with K_r, which the
+    # solver is given as well — K_l read for K_r, or fx for fy, leaves several pixels of error and fails both checks
+    p = S.ba_window(n_kf=6, n_points=400, stereo=True, seed=2, T_lr=T_lr, K=RIG_KITTI["K_l"], Kr=RIG_KITTI["K_r"])
+    assert not np.array_equal(p["Kr"], p["K"])
+    ok, T, X, err = _run(ctx, oracle, p, label="rotated rig, K_r != K_l")
+    assert ok and sba_converged(err)
     # landmarks seen only in the right image of some keyframes (skipped by the Schur loops)
     p = S.ba_window(n_kf=6, n_points=400, stereo=True, seed=3, right_only_frac=0.3)
     _run(ctx, oracle, p)

@@ -45,17 +45,20 @@ def test_triangulate_dlt_bit_exact(vo, oracle, ctx):
 
 
 def _run_both(vo, oracle, W, H, K, nu, nv, frames, win, lvl, n_frames, lba, strict, seed=5, speed=0.5, prefetch=False,
-              kf_trans=10.0, kf_overlap=0.6, id_offset=0, id_jump=None):
+              kf_trans=10.0, kf_overlap=0.6, id_offset=0, id_jump=None, K_r=None, T_lr=None):
+    """K_r, T_lr: the right camera's intrinsics and pose where the rig is not the stream's plain one (K, st.T_lr)."""
     from oracle.stereo_vo import StereoVORef
     st, imgs = frames
-    ref = StereoVORef(W, H, K, K, st.T_lr, nu, nv, thres_fast=15, win=win, max_level=lvl, kf_trans=kf_trans, kf_overlap=kf_overlap,
+    K_r = K if K_r is None else K_r
+    T_lr = st.T_lr if T_lr is None else T_lr
+    ref = StereoVORef(W, H, K, K_r, T_lr, nu, nv, thres_fast=15, win=win, max_level=lvl, kf_trans=kf_trans, kf_overlap=kf_overlap,
                       lba=lba, sum_mode=oracle.SUM_TREE, tree_width=512, ic_border=oracle.IC_REFERENCE if strict else oracle.IC_MASKED,
                       n_threads=8)
     c = vo.Context(device=0, max_width=W, max_height=H, max_points=4096, n_slots=5, max_level=lvl)
     try:
         if id_offset:
             vo.TrackIds(c).reset(id_offset, 0)  # the stream's landmark counter starts here (the CPU loop's at 0)
-        svo = vo.StereoVO(c, W, H, K, K, st.T_lr, nu, nv, thres_fastscore=15, window_size=win, max_level=lvl, strict_border=strict,
+        svo = vo.StereoVO(c, W, H, K, K_r, T_lr, nu, nv, thres_fastscore=15, window_size=win, max_level=lvl, strict_border=strict,
                           local_ba=lba, thres_trans=kf_trans, thres_alive_ratio=kf_overlap)
         log = []
         for k in range(n_frames):

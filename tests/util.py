@@ -240,3 +240,147 @@ def sba_ulp_perturbed(p, seed):
         a = p[name]
         q[name] = np.where(rng.random(a.shape) < 0.5, np.nextafter(a, np.inf), np.nextafter(a, -np.inf))
     return q
+
+
+# ---- general stereo rig (test_rig_inputs.py, test_rig_gpu.py) ------------------------------------------------------------
+# Right intrinsics 1-3 % off the left ones, fx != fy in both cameras, and a right camera that is rotated by ~0.016 rad and
+# shifted in y and z as well: no two of K_l / K_r, R_lr / R_lr^T, T_lr / inverse(T_lr), fx / fy can be exchanged, and
+# t_y, t_z cannot be dropped, without the result changing (test_rig_inputs.py shows that for every input built from these).
+# Small enough that left -> right tracking still finds its features.
+RIG_XI = (0.537, 0.011, -0.007, 0.012, -0.009, 0.004)
+RIG_KITTI = dict(K_l=(718.856, 726.1, 607.1928, 185.2157), K_r=(709.4, 704.3, 615.9, 180.4))  # two-view point sets, BA windows
+RIG_320 = dict(width=320, height=200, K_l=(300.0, 303.5, 160.0, 100.0), K_r=(296.0, 294.5, 166.0, 96.5))
+RIG_640 = dict(width=640, height=240, K_l=(400.0, 404.0, 320.0, 120.0), K_r=(395.0, 392.5, 327.0, 116.0))
+RIG_MUTANTS = ("K_l <-> K_r", "R_lr transposed", "T_lr inverted", "t_y = t_z = 0", "fx <-> fy right")
+RIG_PLAIN_NOOPS = ("K_l <-> K_r", "R_lr transposed", "t_y = t_z = 0")  # what leaves K_r = K_l, R = I, t = (b, 0, 0) as it is
+# pose-only BA point counts: one point, less than a wavefront's worth, around one workgroup (512), around the 2048 points
+# gn_pose_kernel keeps in registers (the rest is reloaded each iteration), and well past it
+RIG_GN_COUNTS = (1, 37, 511, 512, 513, 2047, 2048, 2049, 3000)
+RIG_GN_SEED = {n: 100 + n for n in RIG_GN_COUNTS}  # seeds at which the TREE and SEQ inlier masks are equal (test_rig_inputs.py)
+MONO_K = (458.654, 457.296, 367.215, 248.375)  # fx != fy
+MONO_GN_COUNTS = (2047, 2048, 2049, 3000)     # around and past the points kept in registers: the mono reload loop
+MONO_GN_SEED = {n: 200 + n for n in MONO_GN_COUNTS}
+RIG_GN_T0_XI = (0.02, -0.015, 0.017, 0.003, -0.002, 0.0017)  # |v| = 0.030 m, |w| = 0.004 rad off the truth
+
+
+def rig_T_lr():
+    """float64 pose of the right camera in the left one's frame."""
+    from visual_odometry_ros_amd import synthetic as S
+    return S.se3_exp(RIG_XI)
+
+
+def plain_T_lr(baseline=None):
+    """float64 T_lr of the plain rig: its float32 cast is synthetic.stereo_T_lr(baseline)."""
+    from visual_odometry_ros_amd import synthetic as S
+    T = np.eye(4)
+    T[0, 3] = S.KITTI_BASELINE if baseline is None else baseline
+    return T
+
+
+def se3_inverse64(T):
+    T = np.asarray(T, np.float64)
+    Ti = np.eye(4)
+    Ti[:3, :3] = T[:3, :3].T
+    Ti[:3, 3] = -(T[:3, :3].T @ T[:3, 3])
+    return Ti
+
+
+def project64(X, T, K):
+    """Pixels of the points X (n x 3, float64) in the camera K = (fx, fy, cx, cy) whose frame T maps them to."""
+    Xc = X @ T[:3, :3].T + T[:3, 3]
+    fx, fy, cx, cy = K
+    return np.stack([fx * Xc[:, 0] / Xc[:, 2] + cx, fy * Xc[:, 1] / Xc[:, 2] + cy], 1)
+
+
+def rig_mutants(K_l, K_r, T_lr):
+    """The rig as a kernel would see it after each of the mistakes of RIG_MUTANTS: name -> (K_l, K_r, T_lr)."""
+    K_l, K_r, T = tuple(K_l), tuple(K_r), np.asarray(T_lr, np.float64)
+    R_t, t_x = T.copy(), T.copy()
+    R_t[:3, :3] = T[:3, :3].T
+    t_x[1:3, 3] = 0.0
+    rigs = ((K_r, K_l, T), (K_l, K_r, R_t), (K_l, K_r, se3_inverse64(T)), (K_l, K_r, t_x),
+            (K_l, (K_r[1], K_r[0], K_r[2], K_r[3]), T))
+    return dict(zip(RIG_MUTANTS, rigs))
+
+
+def rig_two_view(n=500, seed=1, K_l=None, K_r=None, T_lr=None, noise_px=0.3, outlier_frac=0.10,
+                 xi_true=(0.05, -0.02, 0.8, 0.004, -0.01, 0.002)):
+    """synthetic.two_view_points for a rig of two different cameras: the same draws in the same order, the right pixels
+    projected in float64 through inverse(T_lr) and K_r. Defaults: RIG_KITTI and rig_T_lr(). Returns K (left), Kr and the
+    float32 T_lr the operators take."""
+    from visual_odometry_ros_amd import synthetic as S
+    K_l = RIG_KITTI["K_l"] if K_l is None else K_l
+    K_r = RIG_KITTI["K_r"] if K_r is None else K_r
+    T_lr = rig_T_lr() if T_lr is None else np.asarray(T_lr, np.float64)
+    rng = np.random.default_rng(seed)
+    X = np.stack([rng.uniform(-10, 10, n), rng.uniform(-4, 4, n), rng.uniform(4, 40, n)], 1)
+    T01 = S.se3_exp(xi_true)
+    T10 = np.linalg.inv(T01)
+    X1 = X @ T10[:3, :3].T + T10[:3, 3]
+    pl = project64(X1, np.eye(4), K_l)
+    pr = project64(X1, se3_inverse64(T_lr), K_r)
+    pl += rng.normal(0, noise_px, pl.shape)
+    pr += rng.normal(0, noise_px, pr.shape)
+    n_out = int(round(outlier_frac * n))
+    out_idx = rng.choice(n, n_out, replace=False)
+    pl[out_idx] += rng.uniform(-20, 20, (n_out, 2))
+    pr[out_idx] += rng.uniform(-20, 20, (n_out, 2))
+    is_outlier = np.zeros(n, bool)
+    is_outlier[out_idx] = True
+    return dict(X=X.astype(np.float32), pts_l=pl.astype(np.float32), pts_r=pr.astype(np.float32), T01_true=T01,
+                K=np.asarray(K_l, np.float32), Kr=np.asarray(K_r, np.float32), T_lr=T_lr.astype(np.float32),
+                is_outlier=is_outlier)
+
+
+def rig_gn_T0(d, identity):
+    """The initial pose of a pose-only BA test: the identity, or the truth moved by RIG_GN_T0_XI, rounded to float32 (a
+    rotation that is orthonormal to float32 rounding only)."""
+    from visual_odometry_ros_amd import synthetic as S
+    if identity:
+        return np.eye(4, dtype=np.float32)
+    return (d["T01_true"] @ S.se3_exp(RIG_GN_T0_XI)).astype(np.float32)
+
+
+class RigStream:
+    """synthetic.StereoStream with two different cameras (a wrapper: scene, poses and every attribute it does not define
+    are the wrapped stream's). The left image is rendered with K_l (.K), the right one with K_r (.Kr) at T_wc @ T_lr; the
+    track set's right pixels are the float64 projection of the cast points through inverse(T_lr) and K_r. T_lr is given in
+    float64; .T_lr is its float32 cast, which is what the operators take and (as in StereoStream) what the right image is
+    rendered at. Every other array of the track set is StereoStream's."""
+
+    def __init__(self, K_l, K_r, T_lr, **kw):
+        from visual_odometry_ros_amd import synthetic as S
+        self._T_lr64 = np.asarray(T_lr, np.float64)
+        self._plain = S.StereoStream(K=K_l, baseline=float(self._T_lr64[0, 3]), **kw)
+        self.Kr = K_r
+        self.T_lr = self._T_lr64.astype(np.float32)
+
+    def __getattr__(self, name):
+        return getattr(self._plain, name)
+
+    def render_pair(self, T_wc):
+        L, depth = self.scene.render(T_wc, self.K, self.width, self.height)
+        R, _ = self.scene.render(T_wc @ self.T_lr.astype(np.float64), self.Kr, self.width, self.height)
+        return L, R, depth
+
+    def track_set(self, k, T_wc_prev, T_wc_cur):
+        from visual_odometry_ros_amd import synthetic as S
+        ts = self._plain.track_set(k, T_wc_prev, T_wc_cur)
+        rng = np.random.default_rng(self.seed * 7919 + k)  # the left pixels again, before their cast to float32
+        pts = S.bucket_points(self.width, self.height, self.n_u, self.n_v, rng, self.margin)
+        fx, fy, cx, cy = self.K
+        z, _, _ = self.scene.cast(T_wc_prev, self.K, self.width, self.height, pix=pts)
+        X = np.stack([(pts[:, 0] - cx) / fx * z, (pts[:, 1] - cy) / fy * z, z], 1)
+        ts["pts_r0"] = project64(X, se3_inverse64(self._T_lr64), self.Kr).astype(np.float32)
+        return ts
+
+
+def rig_stream(rig, T_lr=None, **kw):
+    """RigStream of one of the named rigs (RIG_320, RIG_640)."""
+    return RigStream(rig["K_l"], rig["K_r"], rig_T_lr() if T_lr is None else T_lr, width=rig["width"], height=rig["height"], **kw)
+
+
+def rig_ba_window(**kw):
+    """synthetic.ba_window on RIG_KITTI with rig_T_lr(): right observations projected with K_r."""
+    from visual_odometry_ros_amd import synthetic as S
+    return S.ba_window(K=RIG_KITTI["K_l"], Kr=RIG_KITTI["K_r"], T_lr=rig_T_lr(), **kw)

@@ -255,14 +255,15 @@ class StereoStream:
 
 def ba_window(n_kf=8, n_points=600, stereo=True, seed=0, K=KITTI_K, baseline=0.537, n_fix=2, px_noise=0.3,
               pose_noise=(0.02, 0.004), point_noise=0.05, width=1241, height=376, scale=0.1, right_only_frac=0.0,
-              T_lr=None):
+              T_lr=None, Kr=None):
     """A local-BA window as SparseBAParameters hands it to the solver (sparse_ba_parameters.h:283-420):
     keyframe poses T_jw relative to the first keyframe with translations scaled by 1/pose_scale (0.1), the
     first n_fix poses fixed, landmarks in that frame and scale, per-landmark observation lists in keyframe
     order (left observation, then the right one of the same stereo keyframe). Returns a dict with the
-    perturbed problem (T_jw, X), the ground truth and the CSR observation arrays."""
+    perturbed problem (T_jw, X), the ground truth and the CSR observation arrays. Kr: intrinsics of the right camera
+    (right observations are projected with them; the dict then carries "Kr"); None = the right camera is K as well."""
     rng = np.random.default_rng(seed)
-    fx, fy, cx, cy = K
+    cams = (K, K if Kr is None else Kr)
     # forward-moving rig with small rotations; keyframe 0 is the reference frame
     T_wj = [np.eye(4)]
     for _ in range(1, n_kf):
@@ -289,6 +290,7 @@ def ba_window(n_kf=8, n_points=600, stereo=True, seed=0, K=KITTI_K, baseline=0.5
                 Xr = T_rl @ Xc if right else Xc
                 if Xr[2] < 0.5:
                     continue
+                fx, fy, cx, cy = cams[right]
                 u, v = fx * Xr[0] / Xr[2] + cx, fy * Xr[1] / Xr[2] + cy
                 if not (5 < u < width - 5 and 5 < v < height - 5):
                     continue
@@ -322,7 +324,10 @@ def ba_window(n_kf=8, n_points=600, stereo=True, seed=0, K=KITTI_K, baseline=0.5
     opt_index = np.array([-1] * n_fix + list(range(n_kf - n_fix)), np.int32)
     T_lr_s = T_lr.copy()
     T_lr_s[:3, 3] *= scale
-    return dict(T_jw=T_jw, X=X, T_jw_true=T_jw_true, X_true=X_true, opt_index=opt_index,
-                obs_ptr=np.array(obs_ptr, np.int32), obs_frame=np.array(obs_frame, np.int32),
-                obs_right=np.array(obs_right, np.uint8), obs_px=np.array(obs_px, np.float64), K=np.array(K, np.float64),
-                T_lr=T_lr_s, stereo=stereo)
+    out = dict(T_jw=T_jw, X=X, T_jw_true=T_jw_true, X_true=X_true, opt_index=opt_index,
+               obs_ptr=np.array(obs_ptr, np.int32), obs_frame=np.array(obs_frame, np.int32),
+               obs_right=np.array(obs_right, np.uint8), obs_px=np.array(obs_px, np.float64), K=np.array(K, np.float64),
+               T_lr=T_lr_s, stereo=stereo)
+    if Kr is not None:
+        out["Kr"] = np.array(Kr, np.float64)
+    return out
