@@ -1,5 +1,5 @@
 """Kernel-by-kernel GPU timeline of a few consecutive frames from a rocprofv3 --kernel-trace CSV (frame = from one frame
-kernel's start to the next one's): start, duration, queue.  usage: python tools/tools_trace_frames.py <csv> [first] [count] [all]
+kernel's start on the main queue to the next one's): start, duration, queue.  usage: python tools/tools_trace_frames.py <csv> [first] [count] [all]
        python tools/tools_trace_frames.py <csv> busy [tail_ms]   how full the device is over the last tail_ms of the trace (S streams
                                                                   on one GPU: what overlaps, what each queue does, who holds the time)"""
 import csv
@@ -56,7 +56,10 @@ def main():
             rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"].split("(")[0].replace("void ", ""),
                          r.get("Queue_Id", "?")))
     rows.sort()
-    tracks = [i for i, r in enumerate(rows) if "frame_track" in r[2] or "mono_track" in r[2]]
+    # a frame starts with the frame kernel on the BA launch's queue; the look-ahead loop's candidates-only launch of the NEXT
+    # pair (the same kernel, side stream's queue) is a line inside the frame, marked by its queue
+    main_q = {r[3] for r in rows if "gn_pose" in r[2]}
+    tracks = [i for i, r in enumerate(rows) if ("frame_track" in r[2] and (not main_q or r[3] in main_q)) or "mono_track" in r[2]]
     for fi in range(first, min(first + count, len(tracks) - 1)):
         a, b = tracks[fi], tracks[fi + 1]
         t0 = rows[a][0]

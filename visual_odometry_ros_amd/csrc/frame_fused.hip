@@ -121,18 +121,32 @@ template <int WIN, bool ORD>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(FRAME_WAVES_PER_EU, FRAME_WAVES_PER_EU))) void frame_track_kernel(FrameArgs a) {
   __shared__ FrameShared<WIN> sh;
   if ((int)blockIdx.x + a.wg_off >= a.n + a.n_new) return;
-  // Issue priority of the two roles (measured, -DFRAME_PRIO_FEAT / _CAND / -DFRAME_WAVES_PER_EU sweeps, 400 frames each,
-  // run-to-run noise ~1.5 %): candidates one step above the features 162-165 us per launch, equal 169-171 us, features
-  // above 170 us — the candidates are dispatched last (3150 workgroups, 2048 resident at 211 VGPRs) and the launch ends
-  // when the last of them does. Capping the kernel at 168 VGPRs (3 wavefronts per SIMD, everything resident at once)
-  // costs 38 spilled VGPRs: 159-166 us with the features above, 177-182 us otherwise — no better than this.
+  // Issue priority of the roles. The look-ahead loop (the headline) launches the two roles apart: the frame's launch holds
+  // the features only (about 1870 workgroups at BASELINE configs[1], 2048 wavefronts resident at 211 VGPRs: all of it is
+  // resident from the start, 106-119 us per launch in the trace against 132-160 us for the combined one), and the candidates
+  // of the NEXT pair run on the side stream behind that pair's detection (1500 workgroups, 81-84 us), under the BA launch
+  // of the frame in flight and the start of the next frame kernel. Nobody waits for that launch yet, so it issues at the
+  // features' priority: FRAME_PRIO_CAND_AHEAD 0 against 1 measured 2631 against 2624 frames/s (medians of three 400-frame
+  // runs, run-to-run spread 20) — no difference, and 0 is the value that cannot hold up the BA launch's one workgroup.
+  // FRAME_PRIO_FEAT / _CAND govern the COMBINED launch, which remains for everything that is not a prefetched pair (the
+  // operator-level closed frame, a re-issued synchronous frame): there the candidates are dispatched last (3150 workgroups,
+  // 2048 resident) and the launch ends when the last of them does — candidates one step above the features 162-165 us per
+  // launch, equal 169-171 us, features above 170 us (-DFRAME_PRIO_FEAT / _CAND / -DFRAME_WAVES_PER_EU sweeps, 400 frames
+  // each, noise ~1.5 %). Capping the kernel at 168 VGPRs (3 wavefronts per SIMD) costs 38 spilled VGPRs: 159-166 us with
+  // the features above, 177-182 us otherwise — no better.
 #ifndef FRAME_PRIO_FEAT
 #define FRAME_PRIO_FEAT 0
 #define FRAME_PRIO_CAND 1
 #endif
-  if ((int)blockIdx.x + a.wg_off >= a.n)
-    __builtin_amdgcn_s_setprio(FRAME_PRIO_CAND);
-  else
+#ifndef FRAME_PRIO_CAND_AHEAD
+#define FRAME_PRIO_CAND_AHEAD 0
+#endif
+  if ((int)blockIdx.x + a.wg_off >= a.n) {
+    if (a.n == 0)  // tracked ahead of its frame (vo_frame_fused_candidates_enqueue): nobody waits for this launch yet
+      __builtin_amdgcn_s_setprio(FRAME_PRIO_CAND_AHEAD);
+    else
+      __builtin_amdgcn_s_setprio(FRAME_PRIO_CAND);
+  } else
     __builtin_amdgcn_s_setprio(FRAME_PRIO_FEAT);
   // Feature i is workgroup i: consecutive features (bucket order, i.e. image neighbours) go round-robin
   // over the 8 XCDs. The XCD-aware alternative — XCD x takes the x-th eighth of the list, a horizontal
@@ -654,6 +668,65 @@ int vo_frame_fused_enqueue(vo_ctx *c, const vo_stereo_params *prm, int slot_l0, 
 #undef VO_FRAME_LAUNCH
     default: VO_FAIL(c, VO_ERR_INVALID, "fused frame kernel not instantiated for window %d", prm->win);
   }
+  VO_CHECK_HIP(c, hipGetLastError());
+  return VO_OK;
+}
+
+// The candidate role of frame_track_kernel for a pair that is not a frame yet (the look-ahead loop: frame_pipeline.hip,
+// vo_frame_candidates_enqueue). No features: n = wg_off = 0, so workgroup b is candidate b; only L1 / R1, the window, the
+// levels and the two thresholds are read on that path.
+int vo_frame_fused_candidates_enqueue(vo_ctx *c, const vo_stereo_params *prm, int slot_l, int slot_r, const float *d_xy,
+                                      const uint8_t *d_has, int n_bins, float *new_r, uint8_t *m_new, int *cand_done) {
+  if (n_bins <= 0 || !d_xy || !d_has || !new_r || !m_new || !cand_done) return VO_ERR_INVALID;
+  for (int s : {slot_l, slot_r})
+    if (s < 0 || s >= c->cfg.n_slots || c->slots[s].n_levels <= 0) VO_FAIL(c, VO_ERR_INVALID, "slot holds no image");
+  const vo_pyramid &P1 = c->slots[slot_l], &P2 = c->slots[slot_r];
+  if (P1.w != P2.w || P1.h != P2.h) VO_FAIL(c, VO_ERR_SIZE, "image size mismatch");
+  if (prm->max_level < 1 || prm->win <= 2) VO_FAIL(c, VO_ERR_INVALID, "trackBidirection needs max_level >= 1 && winSize > 2");
+  FrameArgs a;
+  memset(&a, 0, sizeof(a));
+  const int eff = vo_pyr_levels_host(P1.w, P1.h, prm->win, prm->max_level);
+  for (const vo_pyramid *P : {&P1, &P2}) VO_NEED_LEVELS(c, *P, eff);
+  for (int s : {slot_l, slot_r})
+    if (vo_slot_acquire(c, s) < 0) return VO_ERR_HIP;
+  for (int l = 0; l <= eff; ++l) {
+    a.L0[l] = P1.lv[l];  // (never read: no workgroup is a feature)
+    a.L1[l] = P1.lv[l];
+    a.R1[l] = P2.lv[l];
+  }
+  a.max_level = eff;
+  const int effb = vo_pyr_levels_host(P1.w, P1.h, prm->win, prm->max_level - 1);
+  a.max_level_bwd = effb < eff ? effb : eff;
+  a.n = 0;
+  a.wg_off = 0;
+  a.n_new = n_bins;
+  a.pts_new = d_xy;
+  a.cand_has = d_has;
+  a.new_r = new_r;
+  a.m_new = m_new;
+  a.cand_done = cand_done;
+  a.thres_bidir = prm->thres_bidirection;
+  a.W = prm->width;
+  a.H = prm->height;
+  a.thres_err = prm->thres_err;
+  const bool ord = c->sum_order != 0;  // (the candidates run no IC sum: the instantiation the frame itself will launch)
+  vo_prof_begin(c, VO_K_KLT);  // the key of the frame kernel: its bytes count the candidates, so does its time
+  switch (prm->win) {
+#define VO_CAND_LAUNCH(W)                                                                                              \
+  case W:                                                                                                              \
+    if (ord)                                                                                                           \
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(frame_track_kernel<W, true>), dim3(n_bins), dim3(64), 0, c->stream, a);       \
+    else                                                                                                               \
+      hipLaunchKernelGGL(HIP_KERNEL_NAME(frame_track_kernel<W, false>), dim3(n_bins), dim3(64), 0, c->stream, a);      \
+    break;
+    VO_CAND_LAUNCH(13)
+    VO_CAND_LAUNCH(15)
+    VO_CAND_LAUNCH(21)
+    VO_CAND_LAUNCH(31)
+#undef VO_CAND_LAUNCH
+    default: c->prof_open = 0; VO_FAIL(c, VO_ERR_INVALID, "fused frame kernel not instantiated for window %d", prm->win);
+  }
+  vo_prof_end(c);
   VO_CHECK_HIP(c, hipGetLastError());
   return VO_OK;
 }

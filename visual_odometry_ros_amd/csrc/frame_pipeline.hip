@@ -134,6 +134,73 @@ int vo_frame_set_deferred_detection(vo_ctx *c, int issued) {
   return VO_OK;
 }
 
+// StereoVO's look-ahead loop (stereo_vo.hip: vo_svo_prefetch): the pair in slot_l / slot_r is known a frame early, and its
+// new-point candidates depend on its two pyramids and its detector table only. They are tracked HERE — the candidate role of
+// the frame kernel as a launch of its own, on the side stream right behind the table's detection, where the chip is close to
+// empty under the previous frame's BA launch — instead of as the last-dispatched workgroups of the pair's frame kernel, which
+// ends when the last of them does. The results live with the table; the frame finds them there (vo_frame_enqueue_body) when
+// the table says it was tracked for exactly that frame's pair and parameters, and tracks the candidates itself otherwise.
+// Nothing of the per-frame state is touched: a frame may be in flight. The launch counts its workgroups in the same
+// cumulative word as the synchronous call's (cand_done); the side stream runs one such launch behind the other, so the
+// word has passed a launch's own target only when every workgroup of that launch has counted — however far a later
+// launch has got by then.
+int vo_frame_candidates_enqueue(vo_ctx *c, const vo_stereo_params *prm, int slot_l, int slot_r, const vo_bin_params *bp, int table) {
+  if (!c || !prm || !bp) return VO_ERR_INVALID;
+  // only where the pair's frame will take the fused path with the concurrent arrangements still on
+  if (!vo_frame_fused_supported(prm->win) || prm->max_level < 1 || !c->ingest_side || c->frame_conc_off || c->dbg[VO_DBG_CANDS_IN_FRAME])
+    return VO_OK;
+  vo_cand_table *T = vo_orb_cand_table_mut(c, table);
+  if (!T || T->n_bins != bp->n_bins_u * bp->n_bins_v || T->n_bins > c->cfg.max_points) return VO_OK;  // (the frame will say why)
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  RC(vo_frame_init(c));
+  vo_frame_state *f = c->frame;
+  T->tracked = 0;
+  // ... and only where the frame kernel leaves room next to it: one of many times the chip's resident wavefronts is
+  // throughput-bound to its end, and a launch beside it takes from it what it saves the next one (BASELINE configs[4],
+  // 8000 features + 8000 bins: 1145 -> 870 frames/s with the candidates tracked ahead). The same bound, by the same
+  // reasoning, as the concurrent replay's; the frame in flight stands for the one this pair will be.
+  if (f->n + T->n_bins > VO_CONC_MAX_WORKGROUPS) return VO_OK;
+  hipStream_t keep = c->stream;
+  c->stream = c->stream2;  // (launcher, slot events and the event bracket follow c->stream)
+  const unsigned gen_l = c->slots[slot_l].gen, gen_r = c->slots[slot_r].gen;
+  const int rc = vo_frame_fused_candidates_enqueue(c, prm, slot_l, slot_r, T->xy, T->has, T->n_bins, T->new_r, T->m_new, f->cand_done);
+  c->stream = keep;
+  if (rc < 0) return rc;
+  vo_wrap_add(f->cand_total, T->n_bins);  // (the launch went out: it counts, whatever becomes of the table)
+  VO_CHECK_HIP(c, hipEventRecord(T->tracked_ev, c->stream2));
+  T->trk.slot_l = slot_l;
+  T->trk.slot_r = slot_r;
+  T->trk.gen_l = gen_l;
+  T->trk.gen_r = gen_r;
+  T->trk.win = prm->win;
+  T->trk.max_level = prm->max_level;
+  T->trk.width = prm->width;
+  T->trk.height = prm->height;
+  T->trk.thres_err = prm->thres_err;
+  T->trk.thres_bidir = prm->thres_bidirection;
+  T->trk.sum_order = c->sum_order;
+  T->trk.target = f->cand_total;
+  T->tracked = 1;
+  return VO_OK;
+}
+
+int vo_frame_candidates_abandon(vo_ctx *c, int table) {
+  vo_cand_table *T = c ? vo_orb_cand_table_mut(c, table) : nullptr;
+  if (!T || !T->tracked) return VO_OK;
+  T->tracked = 0;
+  VO_CHECK_HIP(c, hipStreamWaitEvent(c->stream_main, T->tracked_ev, 0));
+  return VO_OK;
+}
+
+// the table's candidates were tracked ahead for exactly this frame: the same kernel on the same inputs
+static bool vo_frame_table_tracked_for(const vo_ctx *c, const vo_cand_table *T, const vo_stereo_params *prm, int slot_l1, int slot_r1) {
+  if (!T || !T->tracked || c->dbg[VO_DBG_CANDS_IN_FRAME]) return false;
+  const auto &k = T->trk;
+  return k.slot_l == slot_l1 && k.slot_r == slot_r1 && k.gen_l == c->slots[slot_l1].gen && k.gen_r == c->slots[slot_r1].gen &&
+         k.win == prm->win && k.max_level == prm->max_level && k.width == prm->width && k.height == prm->height &&
+         k.thres_err == prm->thres_err && k.thres_bidir == prm->thres_bidirection && k.sum_order == c->sum_order;
+}
+
 extern "C" int vo_stereo_frame_set_strict_border(vo_ctx *c, int strict) {
   if (!c) return VO_ERR_INVALID;
   c->frame_strict_ic = (strict >= 2 && strict <= 5) ? strict : (strict ? 1 : 0);
@@ -231,7 +298,19 @@ static int vo_frame_enqueue_body(vo_ctx *c, const vo_stereo_params *prm, int slo
   // launch, on the side stream itself, reads it)
   const bool split = tab && c->frame->defer_detect && vo_frame_fused_supported(prm->win) && n > 0 && c->ingest_side && !c->frame_conc_off;
   if (tab && c->frame->defer_detect == 1 && !split) RC(vo_new_point_candidates_enqueue(c, slot_l1, bp, table));  // (cannot overlap: now)
-  if (tab && !split) VO_CHECK_HIP(c, hipStreamWaitEvent(s, tab->ready, 0));
+  // The look-ahead loop: the candidates of this very pair were tracked on the side stream a frame ago (vo_frame_candidates_
+  // enqueue). The frame kernel then holds the features only, and the BA launch joins the candidates' launch on the device as
+  // it joins the synchronous call's — in ordinary frames that launch has long finished. Nothing on the main stream reads the
+  // table in front of that join (the BA launch reads it past the caches, behind the join; the host reads its flags behind
+  // the frame's result), so the main stream waits for no event of the side stream here, not even the table's `ready`.
+  // With the concurrent arrangements off (a join timed out before: this may be the re-issue) stream order does it, through
+  // the event recorded behind the candidates' launch.
+  const bool tracked = tab && !c->frame->defer_detect && n > 0 && vo_frame_table_tracked_for(c, tab, prm, slot_l1, slot_r1);
+  const bool tracked_join = tracked && c->ingest_side && !c->frame_conc_off;
+  if (tracked && !tracked_join)
+    VO_CHECK_HIP(c, hipStreamWaitEvent(s, tab->tracked_ev, 0));
+  else if (tab && !split && !tracked)
+    VO_CHECK_HIP(c, hipStreamWaitEvent(s, tab->ready, 0));
   // ---- carve the packed result block for this frame ----
   f->n = n;
   f->n_new = n_new;
@@ -294,6 +373,7 @@ static int vo_frame_enqueue_body(vo_ctx *c, const vo_stereo_params *prm, int slo
 
   if (n_new > 0 && !fused) VO_CHECK_HIP(c, hipEventRecord(c->ev_fork, s));  // the new pyramids are enqueued before this point
   bool cand_joined = false;  // the candidates went out as a launch of their own on the side stream: the BA launch joins them
+  int cand_target = 0;
 
   if (fused) {
     // steps [3] .. [5] of a feature are one wavefront of ONE launch (frame_fused.hip)
@@ -323,7 +403,7 @@ static int vo_frame_enqueue_body(vo_ctx *c, const vo_stereo_params *prm, int slo
     b.new_r = tab ? f->bin_r : f->new_r;   // closed: per-bin scratch, compacted into the block by the BA launch
     b.m_new = tab ? f->bin_m : f->mNew;
     b.cand_has = tab ? tab->has : nullptr;
-    b.split_cands = split ? 1 : 0;
+    b.split_cands = (split || tracked) ? 1 : 0;  // (tracked: there is no phase 2 — that launch went out with the prefetch)
     b.cand_done = split ? f->cand_done : nullptr;
     // what vo_stereo_frame_result needs to issue this frame again (device pointers only)
     f->again.prm = *prm;
@@ -368,6 +448,7 @@ static int vo_frame_enqueue_body(vo_ctx *c, const vo_stereo_params *prm, int slo
         if (rcf >= 0) {
           cand_joined = true;
           vo_wrap_add(f->cand_total, n_new);  // (cumulative, like the word the candidate workgroups count in)
+          cand_target = f->cand_total;
         }
       }
     }
@@ -375,6 +456,10 @@ static int vo_frame_enqueue_body(vo_ctx *c, const vo_stereo_params *prm, int slo
       f->sync_p1_target = p1_before;
       f->sync_done_target = done_before;
       return rcf;
+    }
+    if (tracked_join) {  // the table's own target: later launches of the side stream may be counting already
+      cand_joined = true;
+      cand_target = tab->trk.target;
     }
     VO_TT("phase1");
   } else if (n > 0) {
@@ -519,8 +604,8 @@ static int vo_frame_enqueue_body(vo_ctx *c, const vo_stereo_params *prm, int slo
       gf.np_v_step = bp->v_step;
       gf.np_has = tab->has;
       gf.np_xy = tab->xy;
-      gf.np_bin_r = f->bin_r;
-      gf.np_bin_m = f->bin_m;
+      gf.np_bin_r = tracked ? tab->new_r : f->bin_r;
+      gf.np_bin_m = tracked ? tab->m_new : f->bin_m;
       gf.np_out_l = (float *)(f->res_dev + f->off_newl);
       gf.np_out_r = f->new_r;
       gf.np_out_m = f->mNew;
@@ -529,7 +614,7 @@ static int vo_frame_enqueue_body(vo_ctx *c, const vo_stereo_params *prm, int slo
       gf.np_host_m = f->res_host + f->off_mnew;
       if (cand_joined) {
         gf.np_cand_done = f->cand_done;
-        gf.np_cand_target = f->cand_total;
+        gf.np_cand_target = cand_target;
         if (c->dbg[VO_DBG_FAIL_JOIN]) gf.np_cand_target += 1 << 20;  // tests: a join that cannot be met
       }
     }
@@ -663,7 +748,8 @@ extern "C" int vo_stereo_frame_result(vo_ctx *c, float *pts_l1, float *pts_r1, u
     VO_CHECK_HIP(c, hipStreamSynchronize(c->stream2));
     VO_CHECK_HIP(c, hipStreamSynchronize(c->stream_main));
     VO_CHECK_HIP(c, hipMemsetAsync(f->cand_done, 0, 64, c->stream_main));
-    f->cand_total = 0;
+    f->cand_total = 0;  // (a tracked table's own target is void with it — and never read again: with the concurrent
+                        //  arrangements off its results, complete by now, are taken in stream order, and nothing tracks ahead)
     VO_CHECK_HIP(c, hipMemsetAsync(f->sync, 0, 128 + 64 * 128, c->stream_main));
     VO_CHECK_HIP(c, hipMemsetAsync(f->ctl, 0, vo_ic_ctl_bytes(), c->stream_main));
     f->sync_p1_target = f->sync_done_target = 0;

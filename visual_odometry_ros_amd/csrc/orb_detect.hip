@@ -362,6 +362,9 @@ void vo_orb_free(vo_ctx *c) {
       if (t.has) (void)hipFree(t.has);
       if (t.ready) (void)hipEventDestroy(t.ready);
       if (t.h_flags) (void)hipHostFree(t.h_flags);
+      if (t.new_r) (void)hipFree(t.new_r);
+      if (t.m_new) (void)hipFree(t.m_new);
+      if (t.tracked_ev) (void)hipEventDestroy(t.tracked_ev);
     }
     delete c->orb;
     c->orb = nullptr;
@@ -883,6 +886,7 @@ const vo_cand_table *vo_orb_cand_table(vo_ctx *c, int table) {
   if (!c->orb || table < 0 || table > 1 || c->orb->tab[table].n_bins <= 0) return nullptr;
   return &c->orb->tab[table];
 }
+vo_cand_table *vo_orb_cand_table_mut(vo_ctx *c, int table) { return const_cast<vo_cand_table *>(vo_orb_cand_table(c, table)); }
 
 static int cand_table_enqueue(vo_ctx *c, int slot, const vo_bin_params *bp, int table, const uint8_t *src, int src_stride, int src_w,
                               int src_h);
@@ -904,14 +908,24 @@ static int cand_table_enqueue(vo_ctx *c, int slot, const vo_bin_params *bp, int 
   vo_cand_table &T = S->tab[table];
   if (c->frame && c->frame->pending && c->frame->table == &T)
     VO_FAIL(c, VO_ERR_INVALID, "candidate table %d is read by the closed frame in flight: collect its result first", table);
+  // whatever was tracked ahead from this table's keypoints (vo_frame_candidates_enqueue) is void from here on — also when
+  // this call fails half-way
+  T.tracked = 0;
   if (T.n_bins != total) {
     if (T.xy) (void)hipFree(T.xy);
     if (T.has) (void)hipFree(T.has);
+    if (T.new_r) (void)hipFree(T.new_r);
+    if (T.m_new) (void)hipFree(T.m_new);
     T.xy = nullptr;
     T.has = nullptr;
+    T.new_r = nullptr;
+    T.m_new = nullptr;
     T.n_bins = 0;
     VO_CHECK_HIP(c, vo_dev_malloc(c, (void **)&T.xy, sizeof(float) * 2 * (size_t)total));
     VO_CHECK_HIP(c, vo_dev_malloc(c, (void **)&T.has, (size_t)total));
+    VO_CHECK_HIP(c, vo_dev_malloc(c, (void **)&T.new_r, sizeof(float) * 2 * (size_t)total));
+    VO_CHECK_HIP(c, vo_dev_malloc(c, (void **)&T.m_new, (size_t)total));
+    if (!T.tracked_ev) VO_CHECK_HIP(c, hipEventCreateWithFlags(&T.tracked_ev, hipEventDisableTiming));
     if (!T.ready) VO_CHECK_HIP(c, hipEventCreateWithFlags(&T.ready, hipEventDisableTiming));
     if (!T.h_flags) VO_CHECK_HIP(c, vo_host_malloc(c, (void **)&T.h_flags, 64, hipHostMallocDefault));
     T.n_bins = total;

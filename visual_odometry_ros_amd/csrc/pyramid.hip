@@ -161,6 +161,7 @@ static int build(vo_ctx *c, int slot_l, const uint8_t *d_l, int slot_r, const ui
     VO_CHECK_HIP(c, hipEventRecord(P[i]->ready, c->stream));
     P[i]->seen[k] = 1;
     P[i]->seen[1 - k] = 0;
+    ++P[i]->gen;
   }
   return VO_OK;
 }

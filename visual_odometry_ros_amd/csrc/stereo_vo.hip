@@ -36,6 +36,7 @@ int vo_frame_enqueue_impl(vo_ctx *c, const vo_stereo_params *prm, int slot_l0, i
                           const vo_bin_params *bp, int table, const float *T_pw, const float *T_cw_prior);
 int vo_frame_set_advance(vo_ctx *c, const VoAdvArgs *adv);          // frame_pipeline.hip
 int vo_frame_set_deferred_detection(vo_ctx *c, int issued);
+// (vo_frame_candidates_enqueue / _abandon: vo_kernels.hpp)
 
 #define RC(x)                \
   do {                       \
@@ -283,7 +284,9 @@ static const bool g_trace = getenv("VO_SVO_TRACE") != nullptr;  // (read once, n
 
 // the pair into the "next" slots + its candidate table (side stream); detect = false: the images and pyramids only (the
 // synchronous call defers the detection to the frame's enqueue, where it runs next to the features' tracking)
-static int svo_ingest(vo_svo *s, const void *left, const void *right, int stride, int on_device, bool detect = true) {
+// ahead = true (a pair handed over early): its candidates are tracked right behind its detection, on the side stream, so that
+// its frame kernel holds the features only (frame_pipeline.hip: vo_frame_candidates_enqueue)
+static int svo_ingest(vo_svo *s, const void *left, const void *right, int stride, int on_device, bool detect = true, bool ahead = false) {
   vo_ctx *c = s->c;
   const int W = s->prm.frame.width, H = s->prm.frame.height;
   // A pair that comes WITH its frame (no look-ahead: detect == false) is ingested on the main stream: the frame kernel, which
@@ -311,6 +314,9 @@ static int svo_ingest(vo_svo *s, const void *left, const void *right, int stride
     RC(vo_set_stereo_pair_host_async(c, s->slot[S_NL], (const uint8_t *)left, s->slot[S_NR], (const uint8_t *)right, W, H, stride));
   }
   if (detect) RC(vo_new_point_candidates_enqueue(c, s->slot[S_NL], &s->prm.bins, s->tab_next));
+  // (not with flagDoUndistortion; not for the stream's first pair, whose candidates the first frame chooses on the host)
+  if (detect && ahead && !s->prm.rectify && !s->first)
+    RC(vo_frame_candidates_enqueue(c, &s->prm.frame, s->slot[S_NL], s->slot[S_NR], &s->prm.bins, s->tab_next));
   return VO_OK;
 }
 
@@ -318,7 +324,8 @@ extern "C" int vo_svo_prefetch(vo_svo *s, const void *left, const void *right, i
   if (!s || !left || !right) return VO_ERR_INVALID;
   const double t_in = g_trace ? svo_now() : 0.0;
   VO_CHECK_HIP(s->c, hipSetDevice(s->c->device));
-  RC(svo_ingest(s, left, right, stride, on_device));
+  s->prefetched = false;  // (whatever was handed over before is overwritten from here on, also if this fails half-way)
+  RC(svo_ingest(s, left, right, stride, on_device, true, true));
   if (g_trace) s->ht.acc[2] += svo_now() - t_in;
   s->pre_l = left;
   s->pre_r = right;
@@ -391,6 +398,9 @@ extern "C" int vo_svo_enqueue(vo_svo *s, const void *left, const void *right, in
   // and the candidates follow as a launch of their own (frame_pipeline.hip: vo_frame_set_deferred_detection)
   bool deferred = false, issued = false;
   if (!(s->prefetched && s->pre_l == left && s->pre_r == right)) {
+    // a pair handed over early that is not this one: its candidates' launch may still read the slots this pair goes into, and
+    // the synchronous call builds its pyramids on the MAIN stream — behind that launch, then (one event; nothing in the loop)
+    RC(vo_frame_candidates_abandon(c, s->tab_next));
     deferred = !s->first && s->c->ingest_side;
     if (deferred && !s->prm.rectify && s->n > 0 && vo_orb_cand_table(c, s->tab_next)) {
       // the detector needs the left IMAGE, not its pyramid: it starts now, on the side stream — from the caller's device image at

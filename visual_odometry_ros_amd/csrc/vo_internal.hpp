@@ -25,6 +25,7 @@ struct vo_pyramid {
   // that built it; a consumer on the other stream waits for it once (vo_slot_acquire)
   hipEvent_t ready;
   uint8_t seen[2];  // [0] main stream / [1] side stream is already ordered behind the last build
+  unsigned gen;     // counts the builds of this slot: what was computed from a slot names the build it read
   uint8_t *stage;  // device staging for an image that arrives from the host asynchronously (allocated on demand)
 };
 

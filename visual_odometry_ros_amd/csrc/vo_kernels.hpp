@@ -153,6 +153,10 @@ int vo_frame_fused_enqueue(vo_ctx *c, const vo_stereo_params *prm, int slot_l0, 
                            const float T_cp[16],
                            const float T_rl[16], const float *d_new, int n_new, const vo_frame_fused_bufs &b,
                            int phase, const float *T_pw = nullptr);
+// the candidate role alone, n_bins workgroups on c->stream: L1 / R1 from the two slots, results written through to
+// new_r / m_new, every workgroup counts itself in cand_done
+int vo_frame_fused_candidates_enqueue(vo_ctx *c, const vo_stereo_params *prm, int slot_l, int slot_r, const float *d_xy,
+                                      const uint8_t *d_has, int n_bins, float *new_r, uint8_t *m_new, int *cand_done);
 
 // misc_kernels.hip
 int vo_hamming_enqueue(vo_ctx *c, const uint8_t *d_a, int na, const uint8_t *d_b, int nb, uint16_t *d_dist);
@@ -216,8 +220,23 @@ struct vo_cand_table {
   hipEvent_t ready; // recorded on the side stream behind the table's kernels and the copy of its flags
   int *h_flags;     // pinned: the detector's capacity flags of this table's detection
   int dbg_filled;   // (VO_DBG_SKIP_DETECT only)
+  // The look-ahead loop tracks the table's candidates AHEAD of the frame that will use them (vo_frame_candidates_enqueue:
+  // the candidate role of the frame kernel as a launch of its own on the side stream, behind the table's detection). The
+  // results live with the table — the BA launch of the frame before reads the OTHER table's while these are written.
+  float *new_r;     // [n_bins][2] forward result of the bin's candidate
+  uint8_t *m_new;   // [n_bins]    its trackBidirection mask
+  hipEvent_t tracked_ev;  // recorded on the side stream behind that launch (the stream-ordered consumers: re-issue, abandonment)
+  int tracked;      // new_r / m_new hold the results described by `trk`; cleared by every detection into this table
+  struct {
+    int slot_l, slot_r;           // the pair's two slots and the builds of them that were read (vo_pyramid::gen)
+    unsigned gen_l, gen_r;
+    int win, max_level, width, height, sum_order;
+    float thres_err, thres_bidir;
+    int target;                   // what vo_frame_state::cand_done reads when that launch has finished (cumulative)
+  } trk;
 };
 const vo_cand_table *vo_orb_cand_table(vo_ctx *c, int table);
+vo_cand_table *vo_orb_cand_table_mut(vo_ctx *c, int table);
 // the table of an image that is not (yet) a pyramid slot: `dev_img` is the image itself (device memory, `stride` bytes per row), read by
 // the tile kernels on the side stream with NO wait for anything — the caller orders the side stream behind whatever fills the
 // image. Returns 1 (nothing enqueued) where the tile kernels do not apply: the caller detects from the slot as usual.
@@ -226,3 +245,9 @@ int vo_new_point_candidates_enqueue_image(vo_ctx *c, const uint8_t *dev_img, int
 
 // frame_pipeline.hip
 void vo_frame_free(vo_ctx *c);
+// the candidates of table `table` (detected from slot_l) tracked slot_l -> slot_r -> slot_l on the side stream, for a pair that
+// is not a frame yet; touches no per-frame state. VO_OK with nothing enqueued where the frame would not use it.
+int vo_frame_candidates_enqueue(vo_ctx *c, const vo_stereo_params *prm, int slot_l, int slot_r, const vo_bin_params *bp, int table);
+// the pair the table was tracked for is not going to be that table's frame: the main stream is ordered behind the launch
+// (it may rebuild the slots that launch reads) and the table is no longer `tracked`
+int vo_frame_candidates_abandon(vo_ctx *c, int table);
