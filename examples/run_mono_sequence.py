@@ -4,11 +4,14 @@ initialisation and of the 5-point fallback is the library's own (FivePointRansac
 
     python examples/run_mono_sequence.py --config config/mono/kitti_00.yaml \
         --images /data/kitti/sequences/00/image_0 --trajectory frame_poses.txt [--keyframes keyframes.txt] [--max-frames N]
+        [--debug-images DIR]
 
 Images: 8-bit grey PNG / PGM / JPEG ... (whatever PIL opens; colour is converted), in sorted file-name order. The next image
 is handed over while the current one is tracked (vo_mvo_prefetch). Output: the reference's trajectory format (`id` + the 12
 numbers of [R|t], `%.4f`), one line per frame; optionally every keyframe's current pose after the last frame. Monocular
-poses carry the scale of the first motion (unit length)."""
+poses carry the scale of the first motion (unit length). --debug-images DIR: the reference's img_debug_ (showTracking /
+showTrackingBA, drawn on the device) of every frame as DIR/debug_<frame>.ppm, a binary PPM in the channel order the node
+publishes (bgr8), written without an image library; a frame that draws nothing repeats the previous picture."""
 import argparse
 import os
 import sys
@@ -27,6 +30,13 @@ def load_grey(path):
     return np.ascontiguousarray(np.asarray(im, dtype=np.uint8))
 
 
+def write_ppm(path, img):
+    """(H, W, 3) uint8 as a binary PPM (P6): header, then the bytes as they are"""
+    with open(path, "wb") as f:
+        f.write(b"P6\n%d %d\n255\n" % (img.shape[1], img.shape[0]))
+        f.write(np.ascontiguousarray(img, np.uint8).tobytes())
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", required=True, help="a config/mono/*.yaml file of the reference")
@@ -37,13 +47,17 @@ def main():
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--strict-border", type=int, default=4, help="see vo_stereo_frame_set_strict_border (0: masked border taps)")
     ap.add_argument("--no-local-ba", action="store_true")
+    ap.add_argument("--debug-images", default=None, metavar="DIR", help="write the debug image of every frame there (binary PPM)")
     args = ap.parse_args()
     import visual_odometry_ros_amd as V
     names = sorted(os.listdir(args.images))
     n = len(names) if not args.max_frames else min(len(names), args.max_frames)
     if n == 0:
         raise SystemExit("no images found")
-    mvo = V.MonoVO.from_yaml(args.config, device=args.device, strict_border=args.strict_border, local_ba=not args.no_local_ba)
+    mvo = V.MonoVO.from_yaml(args.config, device=args.device, strict_border=args.strict_border, local_ba=not args.no_local_ba,
+                             debug_image=bool(args.debug_images))
+    if args.debug_images:
+        os.makedirs(args.debug_images, exist_ok=True)
     image = lambda k: load_grey(os.path.join(args.images, names[k]))  # noqa: E731
     ids, poses, n_kf, n_5p = [], [], 0, 0
     cur = image(0)
@@ -58,6 +72,8 @@ def main():
         poses.append(np.array(info.T_wc, np.float32).reshape(4, 4))
         n_kf += int(info.is_keyframe)
         n_5p += int(info.used_five_point)
+        if args.debug_images:
+            write_ppm(os.path.join(args.debug_images, f"debug_{k:06d}.ppm"), mvo.getDebugImage())
         if k % 100 == 0 or k == n - 1:
             t = poses[-1][:3, 3]
             print(f"frame {k:6d}: {info.n_tracks_out:5d} tracks, {n_kf:4d} keyframes, {n_5p:4d} 5-point poses, "

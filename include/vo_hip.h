@@ -604,7 +604,7 @@ int vo_svo_device_bytes(const vo_svo *svo, size_t *bytes);
  * vo_svo_get_debug_image waits for the last picture only and copies it into `out` (height x width x 3 bytes, row pitch
  * out_stride >= 3 * width; NULL: the size only). A frame that does not draw (the first pair of a stream) keeps the previous
  * picture; before the first one *width = *height = 0 and the call returns VO_OK.
- * MonoVO has no such option yet: its getDebugImage stays empty. */
+ * MonoVO's form of the option is vo_mvo_set_debug_image / vo_mvo_get_debug_image (below). */
 int vo_svo_set_debug_image(vo_svo *svo, int on);
 int vo_svo_get_debug_image(vo_svo *svo, uint8_t *out, int out_stride, int *width, int *height);
 
@@ -831,6 +831,42 @@ int vo_mvo_get_tracks(vo_mvo *mvo, int32_t *ids, float *pts, float *Xw, uint8_t 
 /* stats_keyframe (mono_vo.cpp:1130-1155), as vo_svo_keyframe_count / vo_svo_get_keyframes */
 int vo_mvo_keyframe_count(vo_mvo *mvo, int *n_keyframes);
 int vo_mvo_get_keyframes(vo_mvo *mvo, float *T_wc, int32_t *n_points, float *mappoints, size_t cap_points, size_t *total_points);
+/* img_debug_ of the reference's MonoVO: with the option on, every frame draws what trackImage draws, on level 0 of the
+ * current image slot (with rectify the undistorted image, which is what the reference draws on):
+ *   first image      mono_vo.cpp:555  showTracking(I1, lmtrack_curr.pts1, {}, {}) = vo_draw_tracking with pts0 = the new
+ *                    landmarks' pixels in landmark order, n1 = n_new = 0                                            (kind 1)
+ *   initialisation   :627  showTracking(I1, lmtrack_final.pts0, lmtrack_final.pts1, pts1_new): the survivors of the 5-point
+ *                    mask and the Sampson gate, in order, previous and current pixels; pts_new = EVERY candidate of the
+ *                    bucketed extraction of :624, accepted by the back-tracking gate of :634 or not                 (kind 1)
+ *   steady state     :904  showTrackingBA(I1, pts1_ba, pts1_proj_ba) = vo_draw_tracking_ba when the pose-only BA gave the
+ *                    pose. index_ba (:799-826) = the features i with stage >= 2 and the BA class and Xp(2) > 0.1, in index
+ *                    order (Xp = Rcw_prev X + tcw_prev, the frame kernel's own value). pts1_ba[i] = the refined pixel
+ *                    pts1[i], also for features the BA or the Sampson gate reject afterwards. pts1_proj_ba[i] =
+ *                    projectToPixel(dR10 Xp + dt10) (:893-897, camera.cpp:208-213) with dT10 = inverseSE3_f(dT01) of the
+ *                    pose the frame returns, in float, every operation rounded on its own:
+ *                      Xc_r = ((R[r][0]*Xp0 + R[r][1]*Xp1) + R[r][2]*Xp2) + t_r;  invz = 1.0f / Xc_2;
+ *                      u = (fx * Xc_0) * invz + cx;  v = (fy * Xc_1) * invz + cy
+ *                    (a depth Xc_2 <= 0 gives negative, infinite or NaN pixels: the drawing rules skip or clip them) (kind 2)
+ *   steady state, 5-point fallback (too few BA points, or a failed BA): nothing, as in the reference — the picture, its size,
+ *                    its kind and its points stay as they were.
+ * Off by default; with it off no launch, allocation or result differs from a driver without the option.
+ * vo_mvo_set_debug_image(mvo, 1) makes the option's only allocations, five of them: an index plane, the picture on the device,
+ * a pinned host picture, and a device and a pinned block for the point sets. VO_ERR_INVALID while a frame is in flight.
+ * The steady-state sets are gathered on the device by one small launch on the main stream behind the frame's last launch —
+ * the frame's arrays are the next frame's to overwrite — and whether the frame draws is decided there, from the frame's
+ * need_five_point word. Coverage, resolve and the copies to the host follow on the context's side stream. At most one picture
+ * is in flight: vo_mvo_result waits for the PREVIOUS frame's picture before it enqueues its own, never for its own. Poses,
+ * ids, pixels, flags, keyframe decisions and the local BA are the same bits with the option on and off.
+ * vo_mvo_get_debug_image waits for the last picture only and copies it into `out` (height x width x 3 bytes, row pitch
+ * out_stride >= 3 * width, VO_ERR_INVALID otherwise; NULL: the size only). Before the first picture *width = *height = 0 and
+ * the call returns VO_OK.
+ * vo_mvo_get_debug_points is a test / inspection hook: what the last picture was drawn from. *kind = 0 (none yet), 1
+ * (showTracking), 2 (showTrackingBA). kind 1: set0 = pts0, set1 = pts1, set2 = pts_new. kind 2: set0 = pts1_ba, set1 =
+ * pts1_proj_ba (both compacted, index order), n[2] = 0. x y pairs; any pointer may be NULL; VO_ERR_CAPACITY when a requested
+ * set exceeds cap. */
+int vo_mvo_set_debug_image(vo_mvo *mvo, int on);
+int vo_mvo_get_debug_image(vo_mvo *mvo, uint8_t *out, int out_stride, int *width, int *height);
+int vo_mvo_get_debug_points(vo_mvo *mvo, int *kind, float *set0, float *set1, float *set2, int n[3], int cap);
 
 /* ---- 5-point RANSAC pose: MotionEstimator::calcPose5PointsAlgorithm ------------------------------------------------
  * motion_estimator.cpp:21-123 + findCorrectRT (:205-263): cv::findEssentialMat(pts0, pts1, K, RANSAC, confidence, thres_px)

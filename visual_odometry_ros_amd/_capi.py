@@ -134,7 +134,7 @@ SYMBOLS = [
     "vo_stereo_frame_enqueue_closed_world", "vo_stereo_frame_recoveries", "vo_svo_create", "vo_svo_destroy", "vo_svo_track", "vo_svo_run", "vo_svo_enqueue",
     "vo_svo_prefetch", "vo_svo_result", "vo_svo_get_tracks", "vo_svo_get_new_points", "vo_svo_keyframe_count", "vo_svo_get_keyframe", "vo_svo_get_keyframes", "vo_triangulate_dlt", "vo_batch_create", "vo_batch_destroy",
     "vo_mvo_create", "vo_mvo_destroy", "vo_mvo_track", "vo_mvo_run", "vo_mvo_enqueue", "vo_mvo_prefetch", "vo_mvo_result", "vo_mvo_get_tracks",
-    "vo_mvo_keyframe_count", "vo_mvo_get_keyframes",
+    "vo_mvo_keyframe_count", "vo_mvo_get_keyframes", "vo_mvo_set_debug_image", "vo_mvo_get_debug_image", "vo_mvo_get_debug_points",
     "vo_batch_last_error", "vo_batch_run", "vo_debug_set", "vo_batch_debug_set", "vo_batch_strict_border", "vo_debug_allocation_count", "vo_svo_device_bytes",
     "vo_se3_exp", "vo_ids_reset", "vo_ids_peek", "vo_ids_new_frames", "vo_ids_new_landmarks", "vo_compact_tracks",
     "vo_set_sum_order", "vo_get_sum_order",
@@ -215,6 +215,9 @@ def load():
     lib.vo_draw_tracking_ba.argtypes = [vp, ci, vp, ci, vp, ci, vp, ci]
     lib.vo_svo_set_debug_image.argtypes = [vp, ci]
     lib.vo_svo_get_debug_image.argtypes = [vp, vp, ci, vp, vp]
+    lib.vo_mvo_set_debug_image.argtypes = [vp, ci]
+    lib.vo_mvo_get_debug_image.argtypes = [vp, vp, ci, vp, vp]
+    lib.vo_mvo_get_debug_points.argtypes = [vp, vp, vp, vp, vp, vp, ci]
     lib.vo_get_sum_order.argtypes = [vp]
     lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_five_point_destroy.argtypes = [vp]

@@ -1543,7 +1543,8 @@ class MonoVO:
     def __init__(self, ctx, width, height, K, n_bins_u, n_bins_v, five_point=None, thres_fastscore=15, window_size=15, max_level=5,
                  thres_error=20.0, thres_bidirection=1.0, thres_poseba_error=5, thres_sampson=1.0, thres_parallax=1.0,
                  thres_overlap_ratio=0.7, thres_rotation=3.0, thres_translation=3.0, n_max_keyframes_in_window=9, strict_border=4,
-                 local_ba=True, rectify=False, thres_5p_error=2.0):
+                 local_ba=True, rectify=False, thres_5p_error=2.0, debug_image=False):
+        """debug_image=True: every frame draws the reference's img_debug_ on the device (getDebugImage, getDebugPoints)."""
         self.ctx, self.lib = ctx, ctx.lib
         self._own_fp = None
         if five_point is None:
@@ -1590,6 +1591,8 @@ class MonoVO:
                 self._own_fp.close()
             raise
         ctx._children.add(self)
+        if debug_image:
+            ctx.check(self.lib.vo_mvo_set_debug_image(self._h, 1))
         self._info = MvoFrameInfo()
         self.stats_frame = []
 
@@ -1599,8 +1602,8 @@ class MonoVO:
         configured by one of its config/mono/*.yaml files, with the library's 5-point solver at motion_estimator.
         thres_5p_error. The context is created here (sized by the file) and closed with the object. With flagDoUndistortion
         the images go through the camera's undistortion map (mono_vo.cpp:509-513). `overrides`: keyword arguments of the
-        constructor (five_point, strict_border, local_ba, ...). `max_points`: capacity of a track set (default 2 * bins +
-        1024, as StereoVO.from_yaml). `input_format`: the images' pixel format (Context.set_input_format); anything but
+        constructor (five_point, strict_border, local_ba, debug_image, ...). `max_points`: capacity of a track set (default
+        2 * bins + 1024, as StereoVO.from_yaml). `input_format`: the images' pixel format (Context.set_input_format); anything but
         "mono8" needs flagDoUndistortion in the file."""
         from . import config as _config
         cfg = _config.load_mono_config(path)
@@ -1737,6 +1740,28 @@ class MonoVO:
         for i in out:
             self.stats_frame.append(np.array(i.T_wc, np.float32).reshape(4, 4))
         return out, stamps[:m]
+
+    def getDebugImage(self):
+        """img_debug_ of the last frame that drew one (debug_image=True): an (H, W, 3) uint8 array — published as bgr8 by the
+        reference's node — or an empty (0, 0, 3) array before the first one and with the option off. A steady-state frame
+        that took the 5-point fallback draws nothing, as in the reference: the previous picture stays."""
+        w, h = C.c_int(), C.c_int()
+        self.ctx.check(self.lib.vo_mvo_get_debug_image(self._h, None, 0, C.addressof(w), C.addressof(h)))
+        out = np.zeros((h.value, w.value, 3), np.uint8)
+        if out.size:
+            self.ctx.check(self.lib.vo_mvo_get_debug_image(self._h, out.ctypes.data, out.strides[0], C.addressof(w), C.addressof(h)))
+        return out
+
+    def getDebugPoints(self):
+        """What the last picture was drawn from (vo_mvo_get_debug_points): (kind, set0, set1, set2), (n, 2) float32 arrays.
+        kind 0: none yet; 1: showTracking (pts0, pts1, pts_new); 2: showTrackingBA (pts1_ba, pts1_proj_ba, empty)."""
+        kind, n = C.c_int(), (C.c_int * 3)()
+        self.ctx.check(self.lib.vo_mvo_get_debug_points(self._h, C.addressof(kind), None, None, None, n, 0))
+        cap = max(max(n), 1)
+        sets = [np.zeros((cap, 2), np.float32) for _ in range(3)]
+        self.ctx.check(self.lib.vo_mvo_get_debug_points(self._h, C.addressof(kind), sets[0].ctypes.data, sets[1].ctypes.data,
+                                                        sets[2].ctypes.data, n, cap))
+        return (kind.value,) + tuple(a[:n[k]].copy() for k, a in enumerate(sets))
 
     def getTracks(self):
         """frame_prev_'s related landmarks: dict(ids, pts, Xw, flags, age, cos_parallax)."""

@@ -223,6 +223,18 @@ class MonoVO {
     }
   }
   const vo_mvo_frame_info &lastFrameInfo() const { return last_; }
+  // img_debug_ of the reference (mono_vo.cpp:555, :627 showTracking; :904 showTrackingBA), drawn on the device
+  // (vo_mvo_set_debug_image): off by default
+  void setDebugImage(bool on) { ctx_->check(vo_mvo_set_debug_image(mvo_, on ? 1 : 0)); }
+  // the last picture: rows of width x 3 bytes (cv::Scalar component k in channel k: published as bgr8, (0,255,0) is green);
+  // returns false and leaves `rgb` empty before the first drawn frame. A frame that took the 5-point fallback keeps the previous one.
+  bool getDebugImage(std::vector<std::uint8_t> &rgb, int &width, int &height) {
+    ctx_->check(vo_mvo_get_debug_image(mvo_, nullptr, 0, &width, &height));
+    rgb.assign((size_t)width * (size_t)height * 3, 0);
+    if (rgb.empty()) return false;
+    ctx_->check(vo_mvo_get_debug_image(mvo_, rgb.data(), 3 * width, &width, &height));
+    return true;
+  }
 
  private:
   static int trampoline(void *user, const float *p0, const float *p1, int n, const float K[4], float R10[9], float t10[3], std::uint8_t *mask) {

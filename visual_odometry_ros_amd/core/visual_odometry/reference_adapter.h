@@ -467,7 +467,10 @@ class StereoVO {
 // reference's signatures; the loop runs in libvo_hip.so (vo::MonoVO, mono_vo.h next to this file). The 5-point pose is the
 // one piece the library does not contain (OpenCV calib3d): bind MonoVO::setFivePointSolver to the reference's
 // own MotionEstimator::calcPose5PointsAlgorithm (motion_estimator.cpp:21-203 + findCorrectRT, kept from the reference tree)
-// before the first trackImage — INTEGRATION.md shows the three lines. getDebugImage() returns an empty image.
+// before the first trackImage — INTEGRATION.md shows the three lines. getDebugImage(): after setDebugImage(true) — NOT in the
+// reference, where the image is always drawn — the CV_8UC3 picture of the last frame that drew one, drawn on the device as
+// mono_vo.cpp:555, :627 and :904 draw it (vo_mvo_set_debug_image; a frame that took the 5-point fallback keeps the previous
+// picture, as in the reference); empty otherwise.
 class MonoVO {
  public:
   struct AlgorithmStatistics {  // the members the ROS node reads (ros1/visual_odometry/mono_vo_ros1.cpp:123-190)
@@ -525,7 +528,17 @@ class MonoVO {
     }
   }
   const AlgorithmStatistics &getStatistics() const { return stat_; }
-  const cv::Mat &getDebugImage() { return img_debug_; }
+  void setDebugImage(bool on) {
+    impl_.setDebugImage(on);
+    debug_on_ = on;
+    if (!on) img_debug_ = cv::Mat();
+  }
+  const cv::Mat &getDebugImage() {
+    int w = 0, h = 0;
+    if (debug_on_ && impl_.getDebugImage(debug_rgb_, w, h))
+      img_debug_ = cv::Mat(h, w, CV_8UC3, debug_rgb_.data(), (size_t)3 * (size_t)w);  // (a header over debug_rgb_, valid until the next call)
+    return img_debug_;
+  }
   vo::MonoVO &device() { return impl_; }
 
  private:
@@ -559,9 +572,10 @@ class MonoVO {
   }
   vo::ContextPtr ctx_;
   vo::MonoVO impl_;
-  bool undistort_ = false, format_is_set_ = false;
+  bool undistort_ = false, format_is_set_ = false, debug_on_ = false;
   FivePointSolver solver_;
   AlgorithmStatistics stat_;
+  std::vector<std::uint8_t> debug_rgb_;
   cv::Mat img_debug_;
 };
 

@@ -6,6 +6,7 @@
 //                           part of its major axis that lies inside the image, so no loop is longer than max(W, H) / 64.
 //   2. draw_resolve_kernel  four pixels per lane: level 0 of the slot replicated into three channels (CV_GRAY2RGB) or the
 //                           colour of the pixel's highest primitive; 12 bytes = three dword stores.
+// A driver's job may leave the sizes of its point sets, and whether it is drawn at all, to words in device memory (DrawDev).
 // The rules themselves (numbering, coverage, colours) are csrc/draw_device.hpp; include/vo_hip.h states them.
 #include "vo_internal.hpp"
 #include "vo_kernels.hpp"
@@ -17,26 +18,40 @@ struct vo_draw_state {
 };
 
 #define DRAW_WAVES 4
-// n_dev != nullptr (tracking_ba with pts empty): the number of pts_proj is read from the device, at most n_prims
-__global__ __launch_bounds__(64 * DRAW_WAVES) void draw_cover_kernel(DrawJob j, int n_prims, const int *__restrict__ n_dev,
-                                                                    uint32_t *__restrict__ idx) {
-  const int prim = blockIdx.x * DRAW_WAVES + (threadIdx.x >> 6);
-  if (n_dev) {
-    const int n = *n_dev;
-    n_prims = n < 0 ? 0 : (n < n_prims ? n : n_prims);
-    j.n1 = n_prims;
+// What a driver's job leaves to the device (any pointer may be null: the host's value holds). n0 / n1: the sizes of p0 / p1 of a
+// tracking_ba job, clamped to [0, cap] (the grid is sized for them). go: *go == 0 skips the job as a whole — no pixel of the
+// picture is written, so the device picture stays the previous one.
+struct DrawDev {
+  const int *n0, *n1, *go;
+  int cap;
+};
+__device__ __forceinline__ bool draw_dev_apply(DrawJob &j, const DrawDev &d) {
+  if (d.go && *d.go == 0) return false;
+  if (d.n0) {
+    const int n = *d.n0;
+    j.n0 = n < 0 ? 0 : (n < d.cap ? n : d.cap);
   }
-  if (prim >= n_prims) return;
+  if (d.n1) {
+    const int n = *d.n1;
+    j.n1 = n < 0 ? 0 : (n < d.cap ? n : d.cap);
+  }
+  return true;
+}
+__global__ __launch_bounds__(64 * DRAW_WAVES) void draw_cover_kernel(DrawJob j, DrawDev d, uint32_t *__restrict__ idx) {
+  const int prim = blockIdx.x * DRAW_WAVES + (threadIdx.x >> 6);
+  if (!draw_dev_apply(j, d)) return;
+  if (prim >= draw_prim_count(j)) return;
   const uint32_t tag = (uint32_t)prim + 1u;
   draw_cover(j, prim, threadIdx.x & 63, 64, [&](int x, int y) { atomicMax(idx + (size_t)y * j.w + x, tag); });
 }
 
-__global__ __launch_bounds__(256) void draw_resolve_kernel(DrawJob j, const uint32_t *__restrict__ idx,
+__global__ __launch_bounds__(256) void draw_resolve_kernel(DrawJob j, DrawDev d, const uint32_t *__restrict__ idx,
                                                            const uint8_t *__restrict__ lv0, int lstride,
                                                            uint32_t *__restrict__ out) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x, total = j.w * j.h;
   const int i = 4 * g;
   if (i >= total) return;
+  if (!draw_dev_apply(j, d)) return;
   int y = i / j.w, x = i - y * j.w;
   uint32_t c[4];
 #pragma unroll
@@ -93,18 +108,22 @@ static int draw_ensure(vo_ctx *c) {
 }
 
 // the two launches on `st`: j's point sets are DEVICE pointers, the picture goes to s->img and, behind it, to s->h_img.
-// d_n: see draw_cover_kernel (the grid is then sized for `cap` primitives).
-static int draw_enqueue(vo_ctx *c, hipStream_t st, int slot, DrawJob j, vo_draw_buffers *s, const int *d_n = nullptr, int cap = 0) {
+// d: see DrawDev (with a device-side count the grid is sized for d.cap points per such set). A job skipped by *d.go leaves
+// s->img as it was; the copy behind it then moves the same bytes into s->h_img again.
+static int draw_enqueue(vo_ctx *c, hipStream_t st, int slot, DrawJob j, vo_draw_buffers *s, DrawDev d = DrawDev{nullptr, nullptr, nullptr, 0}) {
   const vo_level &L = c->slots[slot].lv[0];
   j.w = L.w;
   j.h = L.h;
   const size_t px = (size_t)L.w * L.h;
   VO_CHECK_HIP(c, hipMemsetAsync(s->idx, 0, px * sizeof(uint32_t), st));
-  const int n_prims = d_n ? cap : draw_prim_count(j);
+  DrawJob most = j;  // (the largest job the device may make of it)
+  if (d.n0) most.n0 = d.cap;
+  if (d.n1) most.n1 = d.cap;
+  const int n_prims = draw_prim_count(most);
   if (n_prims > 0)
-    hipLaunchKernelGGL(draw_cover_kernel, dim3((n_prims + DRAW_WAVES - 1) / DRAW_WAVES), dim3(64 * DRAW_WAVES), 0, st, j, n_prims, d_n, s->idx);
+    hipLaunchKernelGGL(draw_cover_kernel, dim3((n_prims + DRAW_WAVES - 1) / DRAW_WAVES), dim3(64 * DRAW_WAVES), 0, st, j, d, s->idx);
   const int lanes = (int)((px + 3) / 4);
-  hipLaunchKernelGGL(draw_resolve_kernel, dim3((lanes + 255) / 256), dim3(256), 0, st, j, s->idx, L.origin(), L.stride, (uint32_t *)s->img);
+  hipLaunchKernelGGL(draw_resolve_kernel, dim3((lanes + 255) / 256), dim3(256), 0, st, j, d, s->idx, L.origin(), L.stride, (uint32_t *)s->img);
   VO_CHECK_HIP(c, hipGetLastError());
   VO_CHECK_HIP(c, hipMemcpyAsync(s->h_img, s->img, px * 3, hipMemcpyDeviceToHost, st));
   return VO_OK;
@@ -115,7 +134,31 @@ int vo_draw_ba_enqueue(vo_ctx *c, hipStream_t st, int slot, const float *d_pts_p
   memset(&j, 0, sizeof(j));
   j.mode = 1;
   j.p1 = d_pts_proj;
-  return draw_enqueue(c, st, slot, j, b, d_n, cap);
+  return draw_enqueue(c, st, slot, j, b, DrawDev{nullptr, d_n, nullptr, cap});
+}
+
+int vo_draw_ba_sets_enqueue(vo_ctx *c, hipStream_t st, int slot, const float *d_pts, const float *d_pts_proj, const int *d_n, int cap,
+                            const int *d_go, vo_draw_buffers *b) {
+  DrawJob j;
+  memset(&j, 0, sizeof(j));
+  j.mode = 1;
+  j.p0 = d_pts;
+  j.p1 = d_pts_proj;
+  return draw_enqueue(c, st, slot, j, b, DrawDev{d_n, d_n, d_go, cap});
+}
+
+int vo_draw_tracking_enqueue(vo_ctx *c, hipStream_t st, int slot, const float *d_pts0, int n0, const float *d_pts1, int n1,
+                             const float *d_pts_new, int n_new, vo_draw_buffers *b) {
+  DrawJob j;
+  memset(&j, 0, sizeof(j));
+  j.mode = 0;
+  j.n0 = n0;
+  j.n1 = n1;
+  j.n2 = n_new;
+  j.p0 = d_pts0;
+  j.p1 = d_pts1;
+  j.p2 = d_pts_new;
+  return draw_enqueue(c, st, slot, j, b);
 }
 
 static int draw_host(vo_ctx *c, int slot, DrawJob j, const float *const sets[3], const int n[3], uint8_t *out, int out_stride) {

@@ -34,6 +34,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "mono_debug_device.hpp"
 #include "mvo_device.hpp"
 #include "stereo_vo.hpp"
 
@@ -242,7 +243,29 @@ __global__ void mvo_pose_put_kernel(MvoPoseArgs a, float *frameT) {
   if (j < a.n && t < 32) frameT[(size_t)(a.f[j] & (MVO_FRAME_RING - 1)) * 32 + t] = a.T[j][t];
 }
 
+// vo_mvo_set_debug_image, steady state: what showTrackingBA is drawn from (mono_debug_device.hpp), one lane per feature. Runs
+// on the main stream behind the frame's last launch: the arrays it reads are the next frame kernel's to overwrite.
+__global__ __launch_bounds__(256) void mvo_debug_gather_kernel(MonoDbgArgs a) { mono_dbg_gather(a, (int)(blockIdx.x * blockDim.x + threadIdx.x)); }
+
 // ---- host -------------------------------------------------------------------------------------------------------------
+// img_debug_ (vo_mvo_set_debug_image). At most one picture is in flight: `done` of the previous one is waited for before the
+// next is enqueued, which is also what lets the image slot it reads be reused (vo_mvo_enqueue rotates three slots: the current
+// image of frame k is written again by the ingestion that follows vo_mvo_result(k + 1) at the earliest, and that call has waited
+// for picture k). What the host knows of a picture — kind, size, compacted points — is taken over when its `done` is seen.
+struct MvoDebug {
+  bool on = false, have = false, settled = true;  // switched on; a job has been enqueued; its outcome has been taken over
+  vo_draw_buffers buf = {};
+  hipEvent_t fork = nullptr, done = nullptr;
+  uint8_t *d_blk = nullptr, *h_blk = nullptr;  // control words | 3 point sets of cap x y pairs | cap validity bytes, device and pinned
+  size_t off_set[3] = {0, 0, 0}, off_valid = 0, blk_bytes = 0;
+  // the job in flight
+  int job_kind = 0, job_w = 0, job_h = 0;
+  std::vector<float> job_set[3];  // kind 1: the sets as the host has them
+  // the last picture
+  int kind = 0, w = 0, h = 0;
+  std::vector<float> set[3];
+};
+
 struct vo_mvo {
   vo_ctx *c = nullptr;
   vo_mvo_params prm;
@@ -270,6 +293,7 @@ struct vo_mvo {
   std::vector<int> kf_frame;  // frame index of every window keyframe (parallel to core.keyframes)
   float cos_thres = -2.0f;
   vo_mvo_frame_info info;
+  MvoDebug dbg;
 };
 
 extern void svo_mul44(const float A[16], const float B[16], float C[16]);
@@ -347,6 +371,12 @@ extern "C" void vo_mvo_destroy(vo_mvo *s) {
   if (!s) return;
   if (s->c) (void)hipSetDevice(s->c->device);
   if (s->c) (void)hipStreamSynchronize(s->c->stream);
+  if (s->dbg.have) (void)hipEventSynchronize(s->dbg.done);
+  vo_draw_buffers_free(&s->dbg.buf);
+  if (s->dbg.fork) (void)hipEventDestroy(s->dbg.fork);
+  if (s->dbg.done) (void)hipEventDestroy(s->dbg.done);
+  if (s->dbg.d_blk) (void)hipFree(s->dbg.d_blk);
+  if (s->dbg.h_blk) (void)hipHostFree(s->dbg.h_blk);
   for (int k = 0; k < 2; ++k) mvo_free_set(&s->ts[k]);
   void *b[] = {s->d_frameT, s->d_hdr, s->d_nrec, s->d_pos, s->d_stage, s->d_mnew, s->d_pts1, s->d_cand1, s->d_cand0};
   for (void *p : b)
@@ -627,9 +657,171 @@ static int mvo_finish_frame(vo_mvo *s, const MvoHdr &h, float T_wc[16], vo_mvo_f
   return VO_OK;
 }
 
+// ---- img_debug_ ---------------------------------------------------------------------------------------------------------
+// the outcome of the job in flight: waits for it (that picture only) and takes over kind, size and points
+static int mvo_debug_settle(vo_mvo *s) {
+  MvoDebug &d = s->dbg;
+  if (!d.have || d.settled) return VO_OK;
+  VO_CHECK_HIP(s->c, hipEventSynchronize(d.done));
+  d.settled = true;
+  if (d.job_kind == 1) {
+    for (int k = 0; k < 3; ++k) d.set[k].swap(d.job_set[k]);
+  } else {
+    const int *ctl = (const int *)d.h_blk;
+    if (!ctl[MVO_DBG_GO]) return VO_OK;  // the 5-point fallback: picture, size, kind and points stay
+    const int n = ctl[MVO_DBG_N] < 0 ? 0 : (ctl[MVO_DBG_N] < s->cap ? ctl[MVO_DBG_N] : s->cap);
+    const float *p0 = (const float *)(d.h_blk + d.off_set[0]), *p1 = (const float *)(d.h_blk + d.off_set[1]);
+    const uint8_t *valid = d.h_blk + d.off_valid;
+    for (int k = 0; k < 3; ++k) d.set[k].clear();
+    for (int i = 0; i < n; ++i)
+      if (valid[i]) {
+        d.set[0].insert(d.set[0].end(), {p0[2 * i], p0[2 * i + 1]});
+        d.set[1].insert(d.set[1].end(), {p1[2 * i], p1[2 * i + 1]});
+      }
+  }
+  d.kind = d.job_kind;
+  d.w = d.job_w;
+  d.h = d.job_h;
+  return VO_OK;
+}
+// in front of a job: the previous picture is there, and the side stream is ordered behind what the main stream holds
+static int mvo_debug_fork(vo_mvo *s) {
+  vo_ctx *c = s->c;
+  VO_CHECK_HIP(c, hipEventRecord(s->dbg.fork, c->stream_main));
+  VO_CHECK_HIP(c, hipStreamWaitEvent(c->stream2, s->dbg.fork, 0));
+  return VO_OK;
+}
+static void mvo_debug_enqueued(vo_mvo *s, int kind) {
+  MvoDebug &d = s->dbg;
+  d.have = true;
+  d.settled = false;
+  d.job_kind = kind;
+  d.job_w = s->prm.frame.width;
+  d.job_h = s->prm.frame.height;
+}
+// the first image and the initialisation (mono_vo.cpp:555, :627): showTracking of sets the host has, not waited for
+static int mvo_debug_tracking(vo_mvo *s, const std::vector<float> &pts0, const std::vector<float> &pts1, const std::vector<float> &pts_new) {
+  vo_ctx *c = s->c;
+  MvoDebug &d = s->dbg;
+  RC(mvo_debug_settle(s));
+  const std::vector<float> *src[3] = {&pts0, &pts1, &pts_new};
+  int n[3];
+  for (int k = 0; k < 3; ++k) {
+    n[k] = (int)(src[k]->size() / 2);
+    if (n[k] > s->cap) VO_FAIL(c, VO_ERR_CAPACITY, "debug image: a set of %d points exceeds vo_config.max_points=%d", n[k], s->cap);
+    d.job_set[k] = *src[k];  // (kept: the copy below reads it, vo_mvo_get_debug_points returns it)
+  }
+  RC(mvo_debug_fork(s));
+  for (int k = 0; k < 3; ++k)
+    if (n[k] > 0)
+      VO_CHECK_HIP(c, hipMemcpyAsync(d.d_blk + d.off_set[k], d.job_set[k].data(), sizeof(float) * 2 * (size_t)n[k], hipMemcpyHostToDevice, c->stream2));
+  RC(vo_draw_tracking_enqueue(c, c->stream2, s->slot[1], (const float *)(d.d_blk + d.off_set[0]), n[0], (const float *)(d.d_blk + d.off_set[1]), n[1],
+                              (const float *)(d.d_blk + d.off_set[2]), n[2], &d.buf));
+  VO_CHECK_HIP(c, hipEventRecord(d.done, c->stream2));
+  mvo_debug_enqueued(s, 1);
+  return VO_OK;
+}
+// the steady state (mono_vo.cpp:904): the gather on the main stream, in front of everything that follows the frame; cover,
+// resolve and the two copies to the host on the side stream. Whether anything is drawn is the device's decision.
+static int mvo_debug_ba(vo_mvo *s) {
+  vo_ctx *c = s->c;
+  MvoDebug &d = s->dbg;
+  vo_frame_state *f = c->frame;
+  RC(mvo_debug_settle(s));
+  MonoDbgArgs a;
+  memset(&a, 0, sizeof(a));
+  a.n = f->n;
+  a.stage = f->stage;
+  a.ba_ok = f->m3;
+  a.pts1 = f->F_pl1;
+  a.Xp = f->A_X;
+  a.dT01 = f->hdr->dT;
+  a.need_five_point = &f->hdr->cnt[5];
+  memcpy(a.K, s->prm.frame.K, sizeof(a.K));
+  a.ctl = (int *)d.d_blk;
+  a.pts_ba = (float *)(d.d_blk + d.off_set[0]);
+  a.pts_proj = (float *)(d.d_blk + d.off_set[1]);
+  a.valid = d.d_blk + d.off_valid;
+  const int lanes = a.n > 0 ? a.n : 1;
+  hipLaunchKernelGGL(mvo_debug_gather_kernel, dim3((lanes + 255) / 256), dim3(256), 0, c->stream_main, a);
+  VO_CHECK_HIP(c, hipGetLastError());
+  RC(mvo_debug_fork(s));
+  RC(vo_draw_ba_sets_enqueue(c, c->stream2, s->slot[1], a.pts_ba, a.pts_proj, a.ctl + MVO_DBG_N, s->cap, a.ctl + MVO_DBG_GO, &d.buf));
+  VO_CHECK_HIP(c, hipMemcpyAsync(d.h_blk, d.d_blk, d.blk_bytes, hipMemcpyDeviceToHost, c->stream2));
+  VO_CHECK_HIP(c, hipEventRecord(d.done, c->stream2));
+  mvo_debug_enqueued(s, 2);
+  return VO_OK;
+}
+
+extern "C" int vo_mvo_set_debug_image(vo_mvo *s, int on) {
+  if (!s) return VO_ERR_INVALID;
+  vo_ctx *c = s->c;
+  if (s->pending) VO_FAIL(c, VO_ERR_INVALID, "vo_mvo_set_debug_image: a frame is in flight");
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  MvoDebug &d = s->dbg;
+  if (on && !d.buf.idx) {  // the option's only allocations, five: index plane, device and pinned picture, device and pinned block
+    RC(vo_draw_buffers_alloc(c, &d.buf));
+    const size_t set_bytes = sizeof(float) * 2 * (size_t)s->cap;
+    size_t off = sizeof(int) * MVO_DBG_WORDS;
+    for (int k = 0; k < 3; ++k) {
+      d.off_set[k] = off;
+      off += set_bytes;
+    }
+    d.off_valid = off;
+    d.blk_bytes = off + (size_t)s->cap;
+    VO_CHECK_HIP(c, vo_dev_malloc(c, (void **)&d.d_blk, d.blk_bytes));
+    VO_CHECK_HIP(c, vo_host_malloc(c, (void **)&d.h_blk, d.blk_bytes, hipHostMallocDefault));
+    VO_CHECK_HIP(c, hipMemset(d.d_blk, 0, d.blk_bytes));
+    memset(d.h_blk, 0, d.blk_bytes);
+    VO_CHECK_HIP(c, hipEventCreateWithFlags(&d.fork, hipEventDisableTiming));
+    VO_CHECK_HIP(c, hipEventCreateWithFlags(&d.done, hipEventDisableTiming));
+  }
+  d.on = on != 0;
+  return VO_OK;
+}
+
+extern "C" int vo_mvo_get_debug_image(vo_mvo *s, uint8_t *out, int out_stride, int *width, int *height) {
+  if (!s || !width || !height) return VO_ERR_INVALID;
+  vo_ctx *c = s->c;
+  *width = *height = 0;
+  MvoDebug &d = s->dbg;
+  if (!d.have) return VO_OK;  // no frame has drawn yet
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  RC(mvo_debug_settle(s));  // that picture only: nothing else on the device is waited for
+  if (d.kind == 0) return VO_OK;
+  *width = d.w;
+  *height = d.h;
+  if (!out) return VO_OK;
+  if (out_stride < 3 * d.w) VO_FAIL(c, VO_ERR_INVALID, "out_stride %d is below 3 x width = %d", out_stride, 3 * d.w);
+  for (int y = 0; y < d.h; ++y) memcpy(out + (size_t)y * out_stride, d.buf.h_img + (size_t)y * 3 * d.w, (size_t)3 * d.w);
+  return VO_OK;
+}
+
+extern "C" int vo_mvo_get_debug_points(vo_mvo *s, int *kind, float *set0, float *set1, float *set2, int n[3], int cap) {
+  if (!s) return VO_ERR_INVALID;
+  vo_ctx *c = s->c;
+  MvoDebug &d = s->dbg;
+  if (kind) *kind = 0;
+  if (n) n[0] = n[1] = n[2] = 0;
+  if (!d.have) return VO_OK;
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  RC(mvo_debug_settle(s));
+  if (kind) *kind = d.kind;
+  float *out[3] = {set0, set1, set2};
+  for (int k = 0; k < 3; ++k) {
+    const int m = (int)(d.set[k].size() / 2);
+    if (n) n[k] = m;
+    if (out[k] && m > cap) VO_FAIL(c, VO_ERR_CAPACITY, "debug point set %d holds %d points, room for %d", k, m, cap);
+  }
+  for (int k = 0; k < 3; ++k)
+    if (out[k] && !d.set[k].empty()) memcpy(out[k], d.set[k].data(), sizeof(float) * d.set[k].size());
+  return VO_OK;
+}
+
 // new points driven from the host (initialisation, 5-point fallback): updateWeightBin(final pixels), the table's best keypoint
-// of every bin left empty, trackBidirection(I1, I0) — uploaded for the advance kernel. Returns the number of candidates.
-static int mvo_host_new_points(vo_mvo *s, const std::vector<float> &final_px, int *m_out) {
+// of every bin left empty, trackBidirection(I1, I0) — uploaded for the advance kernel. Returns the number of candidates
+// (cand_out: their pixels, every one of them, as extractORBwithBinning_fast returned them).
+static int mvo_host_new_points(vo_mvo *s, const std::vector<float> &final_px, int *m_out, std::vector<float> *cand_out = nullptr) {
   vo_ctx *c = s->c;
   const vo_bin_params &b = s->prm.bins;
   const int bins = b.n_bins_u * b.n_bins_v;
@@ -648,6 +840,7 @@ static int mvo_host_new_points(vo_mvo *s, const std::vector<float> &final_px, in
     }
   const int nc = (int)(cand.size() / 2);
   *m_out = nc;
+  if (cand_out) *cand_out = cand;
   if (nc == 0) return VO_OK;
   p0.assign(2 * (size_t)nc, 0.f);
   m.assign((size_t)nc, 1);
@@ -708,6 +901,7 @@ static int mvo_first_image(vo_mvo *s, vo_mvo_frame_info *I) {
     VO_CHECK_HIP(c, hipGetLastError());
   }
   s->n = n;
+  if (s->dbg.on) RC(mvo_debug_tracking(s, pts, {}, {}));  // showTracking(I1, lmtrack_curr.pts1, {}, {}), :555
   // frame_curr->setPose(Identity); setPoseDiff10(T_init), T_init.t = (0, 0, -1) -> dT01_ = inverseSE3_f(T_init)
   float T_init[16];
   mvo_eye(T_init);
@@ -748,14 +942,14 @@ static int mvo_second_image(vo_mvo *s, vo_mvo_frame_info *I) {
     VO_FAIL(c, VO_ERR_GN_FAILED, "calcPose5PointsAlgorithm() is failed.");
   float F[9];
   mvo_fundamental(p.K, R10, t10, F);
-  std::vector<float> dist((size_t)std::max(nk, 1)), fin;
+  std::vector<float> dist((size_t)std::max(nk, 1)), fin, fin0;
   if (nk > 0) RC(vo_sampson_distance(c, p0k.data(), p1k.data(), nk, F, dist.data()));
 
   for (int q = 0; q < nk; ++q)
     if (m5[q] && dist[q] < p.thres_sampson) {
       stage[idx[q]] = 4;
       fin.insert(fin.end(), {p1k[2 * q], p1k[2 * q + 1]});
-
+      if (s->dbg.on) fin0.insert(fin0.end(), {p0k[2 * q], p0k[2 * q + 1]});
     }
   // dt10 = dt10 / dt10.norm() * 1.0f; dT10; dT01 = inverseSE3_f(dT10); pose = Twc_prev * dT01 (:606-612)
   const float nrm = sqrtf(t10[0] * t10[0] + (t10[1] * t10[1] + t10[2] * t10[2]));
@@ -770,7 +964,9 @@ static int mvo_second_image(vo_mvo *s, vo_mvo_frame_info *I) {
   svo_mul44(s->T_wp, dT01, T_wc);
   svo_inv_se3(dT10, s->dT01);  // setPoseDiff10(dT10)
   int m = 0;
-  RC(mvo_host_new_points(s, fin, &m));
+  std::vector<float> cand_all;
+  RC(mvo_host_new_points(s, fin, &m, s->dbg.on ? &cand_all : nullptr));
+  if (s->dbg.on) RC(mvo_debug_tracking(s, fin0, fin, cand_all));  // showTracking(I1, lmtrack_final.pts0, .pts1, pts1_new), :627
   VO_CHECK_HIP(c, hipMemcpyAsync(s->d_stage, stage.data(), (size_t)n, hipMemcpyHostToDevice, st));
   VO_CHECK_HIP(c, hipMemcpyAsync(s->d_pts1, pts1.data(), sizeof(float) * 2 * n, hipMemcpyHostToDevice, st));
   VO_CHECK_HIP(c, hipStreamSynchronize(st));
@@ -1004,6 +1200,10 @@ extern "C" int vo_mvo_result(vo_mvo *s, vo_mvo_frame_info *info) {
     if (rc < 0) return rc;
     vo_frame_state *f = c->frame;
     const vo_frame_hdr *fh = (const vo_frame_hdr *)f->res_host;
+    if (s->dbg.on) {  // showTrackingBA(I1, pts1_ba, pts1_proj_ba), :904 — or nothing, as the frame's own count word says
+      rc = mvo_debug_ba(s);
+      if (rc < 0) return rc;
+    }
     I.n_tracks_in = s->n;
     const uint8_t *stage = f->res_dev + f->off_stage, *mnew = f->res_dev + f->off_mnew;
     const float *pts1 = (const float *)(f->res_dev + f->off_pl1);

@@ -81,6 +81,13 @@ void vo_draw_buffers_free(vo_draw_buffers *b);
 // The drivers' form of showTrackingBA(level 0 of `slot`, {}, d_pts_proj[0 .. min(*d_n, cap))): both launches and the copy into
 // b->h_img on stream `st`. Points and count are DEVICE memory — the count need not be known to the host when this is enqueued.
 int vo_draw_ba_enqueue(vo_ctx *c, hipStream_t st, int slot, const float *d_pts_proj, const int *d_n, int cap, vo_draw_buffers *b);
+// showTrackingBA(level 0 of `slot`, d_pts[0 .. n), d_pts_proj[0 .. n)) with n = min(*d_n, cap) read on the device, drawn only
+// when *d_go != 0: a skipped job writes no pixel of b->img, and the copy behind it leaves b->h_img with the bytes it had.
+int vo_draw_ba_sets_enqueue(vo_ctx *c, hipStream_t st, int slot, const float *d_pts, const float *d_pts_proj, const int *d_n, int cap,
+                            const int *d_go, vo_draw_buffers *b);
+// showTracking(level 0 of `slot`, pts0, pts1, pts_new) from DEVICE point sets whose sizes the host knows (n1 <= n0)
+int vo_draw_tracking_enqueue(vo_ctx *c, hipStream_t st, int slot, const float *d_pts0, int n0, const float *d_pts1, int n1,
+                             const float *d_pts_new, int n_new, vo_draw_buffers *b);
 
 // sba.hip
 void vo_sba_free(vo_ctx *c);
