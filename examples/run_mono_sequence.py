@@ -4,14 +4,17 @@ initialisation and of the 5-point fallback is the library's own (FivePointRansac
 
     python examples/run_mono_sequence.py --config config/mono/kitti_00.yaml \
         --images /data/kitti/sequences/00/image_0 --trajectory frame_poses.txt [--keyframes keyframes.txt] [--max-frames N]
-        [--debug-images DIR]
+        [--debug-images DIR] [--covariance cov.txt]
 
 Images: 8-bit grey PNG / PGM / JPEG ... (whatever PIL opens; colour is converted), in sorted file-name order. The next image
 is handed over while the current one is tracked (vo_mvo_prefetch). Output: the reference's trajectory format (`id` + the 12
 numbers of [R|t], `%.4f`), one line per frame; optionally every keyframe's current pose after the last frame. Monocular
 poses carry the scale of the first motion (unit length). --debug-images DIR: the reference's img_debug_ (showTracking /
 showTrackingBA, drawn on the device) of every frame as DIR/debug_<frame>.ppm, a binary PPM in the channel order the node
-publishes (bgr8), written without an image library; a frame that draws nothing repeats the previous picture."""
+publishes (bgr8), written without an image library; a frame that draws nothing repeats the previous picture. --covariance FILE:
+the pose's covariance as a node would put it into nav_msgs::Odometry::pose.covariance, in map units (up to the stream's scale),
+one line per frame: the id, the 36 values (row-major; x, y, z, rot x, rot y, rot z), `valid` and `n_unknown_steps` (frames whose
+pose did not come from the pose-only BA: the first image, the initialisation, 5-point fallbacks)."""
 import argparse
 import os
 import sys
@@ -44,6 +47,7 @@ def main():
     ap.add_argument("--trajectory", default="frame_poses.txt")
     ap.add_argument("--keyframes", default=None, help="also write the keyframes' current poses there")
     ap.add_argument("--max-frames", type=int, default=0)
+    ap.add_argument("--covariance", default=None, metavar="FILE", help="also write every frame's pose covariance (ROS form) there")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--strict-border", type=int, default=4, help="see vo_stereo_frame_set_strict_border (0: masked border taps)")
     ap.add_argument("--no-local-ba", action="store_true")
@@ -55,7 +59,8 @@ def main():
     if n == 0:
         raise SystemExit("no images found")
     mvo = V.MonoVO.from_yaml(args.config, device=args.device, strict_border=args.strict_border, local_ba=not args.no_local_ba,
-                             debug_image=bool(args.debug_images))
+                             debug_image=bool(args.debug_images), pose_covariance=bool(args.covariance))
+    cov_file = open(args.covariance, "w") if args.covariance else None
     if args.debug_images:
         os.makedirs(args.debug_images, exist_ok=True)
     image = lambda k: load_grey(os.path.join(args.images, names[k]))  # noqa: E731
@@ -71,6 +76,10 @@ def main():
         ids.append(info.frame_id)
         poses.append(np.array(info.T_wc, np.float32).reshape(4, 4))
         n_kf += int(info.is_keyframe)
+        if cov_file:
+            cov = mvo.getPoseCovariance()
+            ros = V.pose_covariance_ros(cov.P, poses[-1])
+            cov_file.write(f"{info.frame_id} " + " ".join(f"{v:.9e}" for v in ros) + f" {int(cov.valid)} {cov.n_unknown_steps}\n")
         n_5p += int(info.used_five_point)
         if args.debug_images:
             write_ppm(os.path.join(args.debug_images, f"debug_{k:06d}.ppm"), mvo.getDebugImage())
@@ -84,6 +93,8 @@ def main():
     if args.keyframes:
         kfs = mvo.getKeyframes()
         V.write_trajectory(args.keyframes, list(range(len(kfs))), np.stack([T for T, _ in kfs]) if kfs else np.zeros((0, 4, 4), np.float32))
+    if cov_file:
+        cov_file.close()
     mvo.close()
     print(f"{n} frames in {dt:.2f} s ({n / dt:.1f} frames/s incl. image decoding); trajectory -> {args.trajectory}")
 

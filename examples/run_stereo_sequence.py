@@ -3,12 +3,15 @@
 
     python examples/run_stereo_sequence.py --config config/stereo/kitti_00_stereo.yaml \
         --left  /data/kitti/sequences/00/image_0 --right /data/kitti/sequences/00/image_1 \
-        --trajectory frame_poses.txt [--keyframes keyframes.txt] [--max-frames N]
+        --trajectory frame_poses.txt [--keyframes keyframes.txt] [--max-frames N] [--covariance cov.txt]
 
 Images: 8-bit grey PNG / PGM / JPEG ... (whatever PIL opens; colour is converted), paired by sorted file name. The next pair
 is handed over while the current one is tracked (vo_svo_prefetch: upload, pyramids and keypoint detection run under the
 frame in flight). Output: the reference's trajectory format (`id` + the 12 numbers of [R|t], `%.4f`,
-stereo_vo.cpp:62-80), one line per frame; optionally every keyframe's current pose after the last frame."""
+stereo_vo.cpp:62-80), one line per frame; optionally every keyframe's current pose after the last frame. --covariance FILE: the
+pose's covariance as a node would put it into nav_msgs::Odometry::pose.covariance (chained on the device behind every frame's
+pose-only BA), one line per frame: the id, the 36 values (row-major; x, y, z, rot x, rot y, rot z), `valid` and
+`n_unknown_steps` (frames whose pose did not come from the BA)."""
 import argparse
 import os
 import sys
@@ -35,6 +38,7 @@ def main():
     ap.add_argument("--trajectory", default="frame_poses.txt")
     ap.add_argument("--keyframes", default=None, help="also write the keyframes' current poses there")
     ap.add_argument("--max-frames", type=int, default=0)
+    ap.add_argument("--covariance", default=None, metavar="FILE", help="also write every frame's pose covariance (ROS form) there")
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--strict-border", type=int, default=4, help="see vo_stereo_frame_set_strict_border (0: masked border taps)")
     ap.add_argument("--no-local-ba", action="store_true")
@@ -48,7 +52,9 @@ def main():
         n = min(n, args.max_frames)
     if n == 0:
         raise SystemExit("no image pairs found")
-    svo = V.StereoVO.from_yaml(args.config, device=args.device, strict_border=args.strict_border, local_ba=not args.no_local_ba)
+    svo = V.StereoVO.from_yaml(args.config, device=args.device, strict_border=args.strict_border, local_ba=not args.no_local_ba,
+                               pose_covariance=bool(args.covariance))
+    cov_file = open(args.covariance, "w") if args.covariance else None
     svo.ctx.sum_order = args.sum_order
     pair = lambda k: (load_grey(os.path.join(args.left, names_l[k])), load_grey(os.path.join(args.right, names_r[k])))  # noqa: E731
     ids, poses, n_kf = [], [], 0
@@ -63,6 +69,10 @@ def main():
         ids.append(info.frame_id)
         poses.append(np.array(info.T_wc, np.float32).reshape(4, 4))
         n_kf += int(info.is_keyframe)
+        if cov_file:
+            cov = svo.getPoseCovariance()
+            ros = V.pose_covariance_ros(cov.P, poses[-1])
+            cov_file.write(f"{info.frame_id} " + " ".join(f"{v:.9e}" for v in ros) + f" {int(cov.valid)} {cov.n_unknown_steps}\n")
         if k % 100 == 0 or k == n - 1:
             t = poses[-1][:3, 3]
             print(f"frame {k:6d}: {info.n_tracks_out:5d} tracks, {n_kf:4d} keyframes, position ({t[0]:9.3f} {t[1]:9.3f} {t[2]:9.3f})", flush=True)
@@ -72,6 +82,8 @@ def main():
     if args.keyframes:
         kfs = svo.getKeyframes()
         V.write_trajectory(args.keyframes, list(range(len(kfs))), np.stack([T for T, _ in kfs]) if kfs else np.zeros((0, 4, 4), np.float32))
+    if cov_file:
+        cov_file.close()
     svo.close()
     print(f"{n} frames in {dt:.2f} s ({n / dt:.1f} frames/s incl. image decoding); trajectory -> {args.trajectory}")
 

@@ -189,6 +189,27 @@ int vo_gn_pose_stereo(vo_ctx *ctx, const float *X, const float *pts_l1, const fl
                       float thres_reproj_outlier, float T01[16], uint8_t *mask_inlier,
                       vo_gn_info *info);
 
+/* Covariance of the pose a pose-only BA returned (the reference has no counterpart: it never fills
+ * nav_msgs::Odometry::pose.covariance). Inputs: the set the BA ran on and the T01 it returned. Everything is evaluated in
+ * f64 from the f32 inputs, with T10 = the SE(3) inverse of T01: the Jacobian rows of the projections under T10 <- exp(delta) T10,
+ * order xi = [rho; phi] — the reference's rows for the left / mono camera (motion_estimator.cpp:976-998, :755-789); for the right
+ * camera [a | Xl x a] with a = (d proj / d Xr) R_rl, the exact derivative (the reference's :1009-1031, the left-frame formula at
+ * Xr, is not: DESIGN.md §13) —, the estimator's own
+ * Huber weight w at that pose (a = 0.5 * sum |r| stereo, |rx| + |ry| mono; w = 1 if a < 0.5, else 0.5 / a), all n points.
+ *   H      = sum_i w_i sum_rows J J^T (row-major 6x6, no (1 + lambda) factor)
+ *   s2     = sum_i w_i |r_i|^2 / (rows * sum_i w_i - 6), rows = 4 stereo / 2 mono, px^2
+ *   Sigma  = s2 * H^-1, or sigma_px^2 * H^-1 when sigma_px > 0: T10_true ~ exp(eps) * T10_est, eps ~ N(0, Sigma)
+ *   valid  = 0 when n < 3, the denominator is <= 0, anything is non-finite or the diagonally scaled H = S H S,
+ *            S = diag(H)^-1/2, is not positive definite: a pivot of its Cholesky factorisation is <= 0 up to rounding
+ *            (<= 36 * 2^-53 / the smallest earlier pivot; the diagonal is 1). Sigma and s2 are then zero. The inverse is that factorisation's, unscaled.
+ * The summation order is fixed: two calls give the same bits. Returns VO_OK or an error. */
+int vo_gn_pose_information_stereo(vo_ctx *ctx, const float *X, const float *pts_l1, const float *pts_r1, int n,
+                                  const float Kl[4], const float Kr[4], const float T_lr[16], const float T01[16],
+                                  double sigma_px, double H[36], double Sigma[36], double *s2, int *valid);
+int vo_gn_pose_information_mono(vo_ctx *ctx, const float *X, const float *pts1, int n, const float K[4],
+                                const float R01[9], const float t01[3], double sigma_px, double H[36], double Sigma[36],
+                                double *s2, int *valid);
+
 /* geometry::se3Exp_f (core/util/geometry_library.cpp:386-440, incl. the theta < 1e-7 branch) and inverseSE3_f
  * (:554-560) exactly as the GN kernel evaluates them on the device, on their own: T = exp(xi), xi = (v, w);
  * Tinv (may be NULL) = inverseSE3_f(T). Row-major. A test hook: the estimator never needs the host to call it. */
@@ -607,6 +628,22 @@ int vo_svo_device_bytes(const vo_svo *svo, size_t *bytes);
  * MonoVO's form of the option is vo_mvo_set_debug_image / vo_mvo_get_debug_image (below). */
 int vo_svo_set_debug_image(vo_svo *svo, int on);
 int vo_svo_get_debug_image(vo_svo *svo, uint8_t *out, int out_stride, int *width, int *height);
+/* Covariance of StereoVO's pose, what a node puts into nav_msgs::Odometry::pose.covariance. Off by default;
+ * with it off no launch, allocation or result differs from a driver without the option. vo_svo_set_pose_covariance(svo, 1,
+ * sigma_px) makes the option's only allocations (two result blocks on the device, one in pinned host memory) and starts the
+ * chain at P = 0; VO_ERR_INVALID while a frame is in flight. sigma_px > 0 scales by sigma_px^2 instead of the a-posteriori s2.
+ * Behind every frame's BA launch, in stream order, one launch of the operator above (vo_gn_pose_information_stereo) reads the
+ * launch's compacted set and the T01 it wrote on the device, and chains
+ *   P_k = Ad(T10,k) P_k-1 Ad(T10,k)^T + Sigma_xi,k,   Ad(T) = [[R, [t]x R], [0, R]],   T_wc_true ~ T_wc_est exp(-e), e ~ N(0, P_k).
+ * A frame whose pose did not come from the BA (the first pair, a block that is not valid) only carries P with its T10 and counts
+ * in n_unknown_steps. The local BA moves T_wc at a keyframe and leaves P alone. vo_svo_result does not wait for the launch;
+ * vo_svo_get_pose_covariance does (any output may be NULL; VO_ERR_INVALID while a frame is in flight or with the option off). */
+int vo_svo_set_pose_covariance(vo_svo *svo, int on, double sigma_px);
+int vo_svo_get_pose_covariance(vo_svo *svo, double P[36], double Sigma_xi[36], double *s2, int *valid, int *n_points,
+                               int *n_unknown_steps);
+/* test hook: what the last frame's covariance launch read — the BA set (X in the previous left camera's frame, both pixel
+ * sets; cap entries of room, NULL: the count only) and the T01 the BA returned */
+int vo_svo_get_pose_covariance_inputs(vo_svo *svo, float *X, float *pts_l, float *pts_r, int cap, int *n, float T01[16]);
 
 /* ---- undistortion / stereo rectification in front of the trackers ----------
  * core/visual_odometry/camera.cpp. A context holds the maps of two cameras
@@ -867,6 +904,16 @@ int vo_mvo_get_keyframes(vo_mvo *mvo, float *T_wc, int32_t *n_points, float *map
 int vo_mvo_set_debug_image(vo_mvo *mvo, int on);
 int vo_mvo_get_debug_image(vo_mvo *mvo, uint8_t *out, int out_stride, int *width, int *height);
 int vo_mvo_get_debug_points(vo_mvo *mvo, int *kind, float *set0, float *set1, float *set2, int n[3], int cap);
+/* Covariance of MonoVO's pose, in map units (up to the stream's scale): vo_svo_set_pose_covariance's twin. The launch behind a
+ * steady-state frame's BA launch is vo_gn_pose_information_mono on the launch's compacted set and its R01, t01. The first
+ * image, the initialisation frame and a frame that took the 5-point fallback have no BA pose: they carry P with their own T10
+ * (for the fallback the step is issued again from vo_mvo_result, where that pose becomes known) and count in n_unknown_steps.
+ * The scale's own uncertainty is not part of P. */
+int vo_mvo_set_pose_covariance(vo_mvo *mvo, int on, double sigma_px);
+int vo_mvo_get_pose_covariance(vo_mvo *mvo, double P[36], double Sigma_xi[36], double *s2, int *valid, int *n_points,
+                               int *n_unknown_steps);
+/* test hook: the last steady-state frame's BA set (X in the previous camera's frame, pixels) and the R01, t01 the BA returned */
+int vo_mvo_get_pose_covariance_inputs(vo_mvo *mvo, float *X, float *pts, int cap, int *n, float R01[9], float t01[3]);
 
 /* ---- 5-point RANSAC pose: MotionEstimator::calcPose5PointsAlgorithm ------------------------------------------------
  * motion_estimator.cpp:21-123 + findCorrectRT (:205-263): cv::findEssentialMat(pts0, pts1, K, RANSAC, confidence, thres_px)

@@ -9,4 +9,5 @@ from ._capi import VoError, load, LIB_PATH  # noqa: F401
 from .api import (Context, FeatureTracker, MotionEstimator, FeatureExtractor,  # noqa: F401
                   StereoFramePipeline, MonoFramePipeline, Camera, StereoCamera,
                   SparseBundleAdjustmentSolver, TrackIds, se3Exp_f, write_trajectory, StereoVO, MonoVO, triangulateDLT, ImageSlots, StereoBatch,
-                  FivePointRansac)
+                  FivePointRansac, PoseInformation, PoseCovariance, propagate_pose_covariance, pose_covariance_ros,
+                  se3_adjoint)

@@ -142,6 +142,9 @@ SYMBOLS = [
     "vo_five_point_minimal", "vo_five_point_samples", "vo_five_point_counts",
     "vo_orb_default_pattern", "vo_orb_get_pattern", "vo_orb_set_pattern", "vo_orb_compute", "vo_orb_detect_and_compute",
     "vo_orb_match_sets",
+    "vo_gn_pose_information_stereo", "vo_gn_pose_information_mono",
+    "vo_svo_set_pose_covariance", "vo_svo_get_pose_covariance", "vo_svo_get_pose_covariance_inputs",
+    "vo_mvo_set_pose_covariance", "vo_mvo_get_pose_covariance", "vo_mvo_get_pose_covariance_inputs",
 ]
 
 _lib = None
@@ -219,6 +222,15 @@ def load():
     lib.vo_mvo_get_debug_image.argtypes = [vp, vp, ci, vp, vp]
     lib.vo_mvo_get_debug_points.argtypes = [vp, vp, vp, vp, vp, vp, ci]
     lib.vo_get_sum_order.argtypes = [vp]
+    cd = C.c_double
+    lib.vo_gn_pose_information_stereo.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, vp, cd, vp, vp, vp, vp]
+    lib.vo_gn_pose_information_mono.argtypes = [vp, vp, vp, ci, vp, vp, vp, cd, vp, vp, vp, vp]
+    lib.vo_svo_set_pose_covariance.argtypes = [vp, ci, cd]
+    lib.vo_svo_get_pose_covariance.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.vo_svo_get_pose_covariance_inputs.argtypes = [vp, vp, vp, vp, ci, vp, vp]
+    lib.vo_mvo_set_pose_covariance.argtypes = [vp, ci, cd]
+    lib.vo_mvo_get_pose_covariance.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    lib.vo_mvo_get_pose_covariance_inputs.argtypes = [vp, vp, vp, ci, vp, vp, vp]
     lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_five_point_destroy.argtypes = [vp]
     lib.vo_five_point_destroy.restype = None

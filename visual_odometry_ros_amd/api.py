@@ -9,6 +9,7 @@ MaskVec; matrices are row-major numpy arrays.
 
 Everything here calls libvo_hip.so. Nothing falls back to numpy or the oracle.
 """
+import collections
 import ctypes as C
 import os
 import weakref
@@ -372,6 +373,45 @@ class FeatureTracker:
         return pt, m[:n].astype(bool)
 
 
+PoseInformation = collections.namedtuple("PoseInformation", "H Sigma s2 valid")
+PoseCovariance = collections.namedtuple("PoseCovariance", "P Sigma_xi s2 valid n_points n_unknown_steps")
+
+
+def _hat(t):
+    return np.array([[0.0, -t[2], t[1]], [t[2], 0.0, -t[0]], [-t[1], t[0], 0.0]])
+
+
+def se3_adjoint(T):
+    """Ad(T) = [[R, [t]x R], [0, R]] for the order xi = [rho; phi] of se3Exp_f (float64)."""
+    T = np.asarray(T, np.float64).reshape(4, 4)
+    R, t = T[:3, :3], T[:3, 3]
+    A = np.zeros((6, 6))
+    A[:3, :3] = A[3:, 3:] = R
+    A[:3, 3:] = _hat(t) @ R
+    return A
+
+
+def propagate_pose_covariance(P, T10, Sigma=None):
+    """One step of the chain the drivers keep on the device, in numpy float64:
+    P_k = Ad(T10) P_k-1 Ad(T10)^T + Sigma, with T_wc,k = T_wc,k-1 T01 and T10 = T01^-1. P is the covariance of the right
+    (body-frame) perturbation: T_wc_true ~ T_wc_est exp(-e), e ~ N(0, P). Sigma=None: the step is only carried."""
+    A = se3_adjoint(T10)
+    Pn = A @ np.asarray(P, np.float64).reshape(6, 6) @ A.T
+    if Sigma is not None:
+        Pn = Pn + np.asarray(Sigma, np.float64).reshape(6, 6)
+    return 0.5 * (Pn + Pn.T)
+
+
+def pose_covariance_ros(P, T_wc):
+    """P in the form of nav_msgs::Odometry::pose.covariance: C = B P B^T, B = blkdiag(R_wc, R_wc) — position and world-axis
+    rotation, order (x, y, z, rot x, rot y, rot z) — as 36 doubles, row-major."""
+    R = np.asarray(T_wc, np.float64).reshape(4, 4)[:3, :3]
+    B = np.zeros((6, 6))
+    B[:3, :3] = B[3:, 3:] = R
+    Cm = B @ np.asarray(P, np.float64).reshape(6, 6) @ B.T
+    return (0.5 * (Cm + Cm.T)).reshape(36)
+
+
 class MotionEstimator:
     """Mirror of the reference MotionEstimator's pose-only BA entry points."""
 
@@ -415,6 +455,31 @@ class MotionEstimator:
             C.c_float(thres_reproj_outlier), _p(T), _p(mask, C.c_uint8), C.byref(info)))
         return bool(rc), T.reshape(4, 4), mask[:n].astype(bool), info
 
+    def poseInformation(self, X, pts1, K, R01, t01, sigma_px=0.0):
+        """Covariance of the pose poseOnlyBundleAdjustment returned (vo_gn_pose_information_mono): the set it ran on and its
+        R01, t01. Returns PoseInformation(H, Sigma, s2, valid); Sigma = s2 H^-1, or sigma_px^2 H^-1 with sigma_px > 0."""
+        X, pts1 = _f32(X).reshape(-1, 3), _f32(pts1).reshape(-1, 2)
+        if X.shape[0] != pts1.shape[0]:
+            raise VoError(-4, "In 'poseInformation()': X.size() != pts1.size().")
+        K, R, t = _f32(K), _f32(R01).reshape(9), _f32(t01).reshape(3)
+        H, S, s2, valid = np.zeros((6, 6)), np.zeros((6, 6)), C.c_double(), C.c_int()
+        self.ctx.check(self.lib.vo_gn_pose_information_mono(self.ctx.handle, _p(X), _p(pts1), X.shape[0], _p(K), _p(R), _p(t),
+                                                            float(sigma_px), H.ctypes.data, S.ctypes.data, C.addressof(s2),
+                                                            C.addressof(valid)))
+        return PoseInformation(H, S, s2.value, bool(valid.value))
+
+    def poseInformation_Stereo(self, X, pts_l1, pts_r1, Kl, Kr, T_lr, T01, sigma_px=0.0):
+        """The stereo form (vo_gn_pose_information_stereo), for the pose poseOnlyBundleAdjustment_Stereo returned."""
+        X = _f32(X).reshape(-1, 3)
+        pts_l1, pts_r1 = _f32(pts_l1).reshape(-1, 2), _f32(pts_r1).reshape(-1, 2)
+        if X.shape[0] != pts_l1.shape[0] or X.shape[0] != pts_r1.shape[0]:
+            raise VoError(-4, "In 'poseInformation_Stereo()': size mismatch")
+        Kl, Kr, T_lr, T = _f32(Kl), _f32(Kr), _f32(T_lr).reshape(16), _f32(T01).reshape(16)
+        H, S, s2, valid = np.zeros((6, 6)), np.zeros((6, 6)), C.c_double(), C.c_int()
+        self.ctx.check(self.lib.vo_gn_pose_information_stereo(self.ctx.handle, _p(X), _p(pts_l1), _p(pts_r1), X.shape[0], _p(Kl),
+                                                              _p(Kr), _p(T_lr), _p(T), float(sigma_px), H.ctypes.data,
+                                                              S.ctypes.data, C.addressof(s2), C.addressof(valid)))
+        return PoseInformation(H, S, s2.value, bool(valid.value))
 
     def setThres1p(self, thres_1p):  # motion_estimator.cpp:655-658 (consumed by the host-side 1-point RANSAC)
         self.thres_1p_ = float(thres_1p)
@@ -923,8 +988,10 @@ class StereoVO:
     def __init__(self, ctx, width, height, Kl, Kr, T_lr, n_bins_u, n_bins_v, thres_fastscore=15, window_size=21, max_level=6,
                  thres_error=80.0, thres_bidirection=0.5, thres_poseba_error=3.0, thres_alive_ratio=0.6, thres_rotation=15.0,
                  thres_trans=10.0, n_max_keyframes_in_window=9, strict_border=4, local_ba=True, rectify=False, thres_sampson=60.0,
-                 debug_image=False):
+                 debug_image=False, pose_covariance=False, sigma_px=0.0):
         """debug_image=True: every tracked frame draws the reference's img_debug_ on the device (getDebugImage).
+        pose_covariance=True: every frame chains the covariance of its pose on the device (getPoseCovariance); sigma_px > 0
+        scales by that pixel noise instead of the a-posteriori variance.
         rectify=True is system_flags_.flagDoUndistortion: the context's stereo rectification maps (StereoCamera.
         initStereoCameraToRectify on the same context) are applied to every incoming pair; Kl / Kr / T_lr are then the
         rectified camera and extrinsics (getRectifiedCamera / getRectifiedStereoPoseLeft2Right)."""
@@ -944,6 +1011,8 @@ class StereoVO:
         ctx._children.add(self)
         if debug_image:
             ctx.check(self.lib.vo_svo_set_debug_image(self._h, 1))
+        if pose_covariance:
+            ctx.check(self.lib.vo_svo_set_pose_covariance(self._h, 1, float(sigma_px)))
         self._info = SvoFrameInfo()
         self.stats_frame = []  # AlgorithmStatistics::FrameStatistics::Twc per frame (stereo_vo.cpp:979-980)
 
@@ -1108,6 +1177,34 @@ class StereoVO:
         if out.size:
             self.ctx.check(self.lib.vo_svo_get_debug_image(self._h, out.ctypes.data, out.strides[0], C.addressof(w), C.addressof(h)))
         return out
+
+    def setPoseCovariance(self, on, sigma_px=0.0):
+        """Switches the option (vo_svo_set_pose_covariance); switching it on starts the chain at P = 0."""
+        self.ctx.check(self.lib.vo_svo_set_pose_covariance(self._h, int(bool(on)), float(sigma_px)))
+
+    def getPoseCovariance(self):
+        """PoseCovariance(P, Sigma_xi, s2, valid, n_points, n_unknown_steps) of the last frame (pose_covariance=True): waits
+        for that frame's covariance launch only."""
+        P, S = np.zeros((6, 6)), np.zeros((6, 6))
+        s2, valid, n, unk = C.c_double(), C.c_int(), C.c_int(), C.c_int()
+        self.ctx.check(self.lib.vo_svo_get_pose_covariance(self._h, P.ctypes.data, S.ctypes.data, C.addressof(s2), C.addressof(valid),
+                                                           C.addressof(n), C.addressof(unk)))
+        return PoseCovariance(P, S, s2.value, bool(valid.value), n.value, unk.value)
+
+    def getPoseCovarianceRos(self):
+        """The 36 doubles of nav_msgs::Odometry::pose.covariance for the last frame's pose (pose_covariance_ros)."""
+        return pose_covariance_ros(self.getPoseCovariance().P, np.array(self._info.T_wc, np.float32).reshape(4, 4))
+
+    def getPoseCovarianceInputs(self):
+        """Test hook: what the last frame's covariance launch read: dict(X, pts_l, pts_r, T01)."""
+        n, T = C.c_int(), np.zeros(16, np.float32)
+        self.ctx.check(self.lib.vo_svo_get_pose_covariance_inputs(self._h, None, None, None, 0, C.addressof(n), T.ctypes.data))
+        m = max(n.value, 1)
+        X, pl, pr = np.zeros((m, 3), np.float32), np.zeros((m, 2), np.float32), np.zeros((m, 2), np.float32)
+        self.ctx.check(self.lib.vo_svo_get_pose_covariance_inputs(self._h, X.ctypes.data, pl.ctypes.data, pr.ctypes.data, m,
+                                                                  C.addressof(n), T.ctypes.data))
+        k = n.value
+        return dict(X=X[:k], pts_l=pl[:k], pts_r=pr[:k], T01=T.reshape(4, 4))
 
     def getTracks(self):
         """The track set the next frame starts from: dict(ids, pts_l, pts_r, Xw, flags)."""
@@ -1543,8 +1640,10 @@ class MonoVO:
     def __init__(self, ctx, width, height, K, n_bins_u, n_bins_v, five_point=None, thres_fastscore=15, window_size=15, max_level=5,
                  thres_error=20.0, thres_bidirection=1.0, thres_poseba_error=5, thres_sampson=1.0, thres_parallax=1.0,
                  thres_overlap_ratio=0.7, thres_rotation=3.0, thres_translation=3.0, n_max_keyframes_in_window=9, strict_border=4,
-                 local_ba=True, rectify=False, thres_5p_error=2.0, debug_image=False):
-        """debug_image=True: every frame draws the reference's img_debug_ on the device (getDebugImage, getDebugPoints)."""
+                 local_ba=True, rectify=False, thres_5p_error=2.0, debug_image=False, pose_covariance=False, sigma_px=0.0):
+        """debug_image=True: every frame draws the reference's img_debug_ on the device (getDebugImage, getDebugPoints).
+        pose_covariance=True: every frame chains the covariance of its pose on the device, in map units (getPoseCovariance);
+        sigma_px > 0 scales by that pixel noise instead of the a-posteriori variance."""
         self.ctx, self.lib = ctx, ctx.lib
         self._own_fp = None
         if five_point is None:
@@ -1593,6 +1692,8 @@ class MonoVO:
         ctx._children.add(self)
         if debug_image:
             ctx.check(self.lib.vo_mvo_set_debug_image(self._h, 1))
+        if pose_covariance:
+            ctx.check(self.lib.vo_mvo_set_pose_covariance(self._h, 1, float(sigma_px)))
         self._info = MvoFrameInfo()
         self.stats_frame = []
 
@@ -1702,6 +1803,34 @@ class MonoVO:
         if rc < 0:
             self.ctx.check(rc)
         return self._out()
+
+    def setPoseCovariance(self, on, sigma_px=0.0):
+        """Switches the option (vo_mvo_set_pose_covariance); switching it on starts the chain at P = 0."""
+        self.ctx.check(self.lib.vo_mvo_set_pose_covariance(self._h, int(bool(on)), float(sigma_px)))
+
+    def getPoseCovariance(self):
+        """PoseCovariance(P, Sigma_xi, s2, valid, n_points, n_unknown_steps) of the last frame (pose_covariance=True), in map
+        units: waits for that frame's covariance launch only."""
+        P, S = np.zeros((6, 6)), np.zeros((6, 6))
+        s2, valid, n, unk = C.c_double(), C.c_int(), C.c_int(), C.c_int()
+        self.ctx.check(self.lib.vo_mvo_get_pose_covariance(self._h, P.ctypes.data, S.ctypes.data, C.addressof(s2), C.addressof(valid),
+                                                           C.addressof(n), C.addressof(unk)))
+        return PoseCovariance(P, S, s2.value, bool(valid.value), n.value, unk.value)
+
+    def getPoseCovarianceRos(self):
+        """The 36 doubles of nav_msgs::Odometry::pose.covariance for the last frame's pose (pose_covariance_ros)."""
+        return pose_covariance_ros(self.getPoseCovariance().P, np.array(self._info.T_wc, np.float32).reshape(4, 4))
+
+    def getPoseCovarianceInputs(self):
+        """Test hook: what the last steady-state frame's covariance launch read: dict(X, pts, R01, t01)."""
+        n, R, t = C.c_int(), np.zeros(9, np.float32), np.zeros(3, np.float32)
+        self.ctx.check(self.lib.vo_mvo_get_pose_covariance_inputs(self._h, None, None, 0, C.addressof(n), R.ctypes.data, t.ctypes.data))
+        m = max(n.value, 1)
+        X, p = np.zeros((m, 3), np.float32), np.zeros((m, 2), np.float32)
+        self.ctx.check(self.lib.vo_mvo_get_pose_covariance_inputs(self._h, X.ctypes.data, p.ctypes.data, m, C.addressof(n),
+                                                                  R.ctypes.data, t.ctypes.data))
+        k = n.value
+        return dict(X=X[:k], pts=p[:k], R01=R.reshape(3, 3), t01=t)
 
     def runSequence(self, images, k_begin=0, k_end=None):
         """A recorded sequence of (device address, stride) images — or of numpy u8 images of one size and layout (host memory) —

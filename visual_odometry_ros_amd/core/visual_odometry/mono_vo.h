@@ -21,6 +21,7 @@
 #include "../defines/define_type.h"
 #include "trajectory_io.h"
 #include "vo_context.h"
+#include "pose_covariance.h"
 
 namespace vo {
 
@@ -223,6 +224,20 @@ class MonoVO {
     }
   }
   const vo_mvo_frame_info &lastFrameInfo() const { return last_; }
+  // NOT in the reference (which leaves nav_msgs::Odometry::pose.covariance empty): the covariance of the pose, chained on the
+  // device behind every frame's BA launch (vo_mvo_set_pose_covariance), in map units (up to the stream's scale) off by default. sigma_px > 0 scales by that pixel
+  // noise instead of the a-posteriori variance.
+  void setPoseCovariance(bool on, double sigma_px = 0.0) { ctx_->check(vo_mvo_set_pose_covariance(mvo_, on ? 1 : 0, sigma_px)); }
+  // of the last tracked frame: waits for that frame's covariance launch only
+  PoseCovariance getPoseCovariance() {
+    PoseCovariance c;
+    int valid = 0;
+    ctx_->check(vo_mvo_get_pose_covariance(mvo_, c.P.data(), c.Sigma_xi.data(), &c.s2, &valid, &c.n_points, &c.n_unknown_steps));
+    c.valid = valid != 0;
+    return c;
+  }
+  // the 36 doubles of pose.covariance for the last frame's pose: (x, y, z, rot x, rot y, rot z), row-major
+  std::array<double, 36> getPoseCovarianceRos() { return poseCovarianceRos(getPoseCovariance().P, last_.T_wc); }
   // img_debug_ of the reference (mono_vo.cpp:555, :627 showTracking; :904 showTrackingBA), drawn on the device
   // (vo_mvo_set_debug_image): off by default
   void setDebugImage(bool on) { ctx_->check(vo_mvo_set_debug_image(mvo_, on ? 1 : 0)); }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../defines/define_type.h"
+#include "pose_covariance.h"
 #include "vo_context.h"
 
 namespace vo {
@@ -59,6 +60,37 @@ class MotionEstimator {
     return rc == 1;
   }
 
+  // NOT in the reference: the covariance of the pose poseOnlyBundleAdjustment returned (vo_gn_pose_information_mono): the set
+  // it ran on and its R01, t01. sigma_px > 0 scales by that pixel noise instead of the a-posteriori variance.
+  const PoseInformation &poseInformation(const PointVec &X, const PixelVec &pts1, const Camera &cam, const Rot3 &R01, const Pos3 &t01,
+                                         double sigma_px = 0.0) {
+    if (X.size() != pts1.size()) throw std::runtime_error("In 'poseInformation()': X.size() != pts1.size().");
+    const int n = (int)X.size();
+    const float K[4] = {cam.fx, cam.fy, cam.cx, cam.cy};
+    int valid = 0;
+    ctx_->check(vo_gn_pose_information_mono(ctx_->get(), n ? &X.data()->x : zero_, n ? &pts1.data()->x : zero_, n, K, R01.data(),
+                                            t01.data(), sigma_px, last_cov_.H.data(), last_cov_.Sigma.data(), &last_cov_.s2, &valid));
+    last_cov_.valid = valid != 0;
+    return last_cov_;
+  }
+  // ... and of the pose poseOnlyBundleAdjustment_Stereo returned (vo_gn_pose_information_stereo)
+  const PoseInformation &poseInformation_Stereo(const PointVec &X, const PixelVec &pts_l1, const PixelVec &pts_r1, const Camera &cam_left,
+                                                const Camera &cam_right, const PoseSE3 &T_lr, const PoseSE3 &T01, double sigma_px = 0.0) {
+    if (X.size() != pts_l1.size() || X.size() != pts_r1.size())
+      throw std::runtime_error("In 'poseInformation_Stereo()': X.size() != pts_l1.size() || X.size() != pts_r1.size().");
+    const int n = (int)X.size();
+    const float Kl[4] = {cam_left.fx, cam_left.fy, cam_left.cx, cam_left.cy};
+    const float Kr[4] = {cam_right.fx, cam_right.fy, cam_right.cx, cam_right.cy};
+    int valid = 0;
+    ctx_->check(vo_gn_pose_information_stereo(ctx_->get(), n ? &X.data()->x : zero_, n ? &pts_l1.data()->x : zero_,
+                                              n ? &pts_r1.data()->x : zero_, n, Kl, Kr, T_lr.data(), T01.data(), sigma_px,
+                                              last_cov_.H.data(), last_cov_.Sigma.data(), &last_cov_.s2, &valid));
+    last_cov_.valid = valid != 0;
+    return last_cov_;
+  }
+  // the last poseInformation / poseInformation_Stereo result
+  const PoseInformation &getPoseCovariance() const { return last_cov_; }
+
   // motion_estimator.cpp:572-599 (F10 overload; F10 row-major here, see reference_adapter.h for Eigen types)
   void calcSampsonDistance(const PixelVec &pts0, const PixelVec &pts1, const Rot3 &F10, std::vector<float> &sampson_dist) {
     if (pts0.size() != pts1.size())
@@ -89,6 +121,7 @@ class MotionEstimator {
   bool is_stereo_mode_;
   PoseSE3 T_left2right_;
   vo_gn_info last_info_{};
+  PoseInformation last_cov_;
   float thres_1p_ = 0.f, thres_5p_ = 0.f;  // consumed by the host-side 1-point / 5-point RANSAC (out of scope)
   float zero_[4] = {0, 0, 0, 0};
 };

@@ -446,6 +446,10 @@ class StereoVO {
       img_debug_ = cv::Mat(h, w, CV_8UC3, debug_rgb_.data(), (size_t)3 * (size_t)w);  // (a header over debug_rgb_, valid until the next call)
     return img_debug_;
   }
+  // NOT in the reference: what a node puts into nav_msgs::Odometry::pose.covariance (vo::StereoVO::setPoseCovariance)
+  void setPoseCovariance(bool on, double sigma_px = 0.0) { impl_.setPoseCovariance(on, sigma_px); }
+  vo::PoseCovariance getPoseCovariance() { return impl_.getPoseCovariance(); }
+  std::array<double, 36> getPoseCovarianceRos() { return impl_.getPoseCovarianceRos(); }
   vo::StereoVO &device() { return impl_; }
 
  private:
@@ -539,6 +543,10 @@ class MonoVO {
       img_debug_ = cv::Mat(h, w, CV_8UC3, debug_rgb_.data(), (size_t)3 * (size_t)w);  // (a header over debug_rgb_, valid until the next call)
     return img_debug_;
   }
+  // NOT in the reference: what a node puts into nav_msgs::Odometry::pose.covariance (vo::MonoVO::setPoseCovariance)
+  void setPoseCovariance(bool on, double sigma_px = 0.0) { impl_.setPoseCovariance(on, sigma_px); }
+  vo::PoseCovariance getPoseCovariance() { return impl_.getPoseCovariance(); }
+  std::array<double, 36> getPoseCovarianceRos() { return impl_.getPoseCovarianceRos(); }
   vo::MonoVO &device() { return impl_; }
 
  private:

@@ -20,6 +20,7 @@
 #include "../defines/define_type.h"
 #include "trajectory_io.h"
 #include "vo_context.h"
+#include "pose_covariance.h"
 
 namespace vo {
 
@@ -220,6 +221,20 @@ class StereoVO {
     }
   }
   const vo_svo_frame_info &lastFrameInfo() const { return last_; }
+  // NOT in the reference (which leaves nav_msgs::Odometry::pose.covariance empty): the covariance of the pose, chained on the
+  // device behind every frame's BA launch (vo_svo_set_pose_covariance), off by default. sigma_px > 0 scales by that pixel
+  // noise instead of the a-posteriori variance.
+  void setPoseCovariance(bool on, double sigma_px = 0.0) { ctx_->check(vo_svo_set_pose_covariance(svo_, on ? 1 : 0, sigma_px)); }
+  // of the last tracked frame: waits for that frame's covariance launch only
+  PoseCovariance getPoseCovariance() {
+    PoseCovariance c;
+    int valid = 0;
+    ctx_->check(vo_svo_get_pose_covariance(svo_, c.P.data(), c.Sigma_xi.data(), &c.s2, &valid, &c.n_points, &c.n_unknown_steps));
+    c.valid = valid != 0;
+    return c;
+  }
+  // the 36 doubles of pose.covariance for the last frame's pose: (x, y, z, rot x, rot y, rot z), row-major
+  std::array<double, 36> getPoseCovarianceRos() { return poseCovarianceRos(getPoseCovariance().P, last_.T_wc); }
   // img_debug_ of the reference (stereo_vo.cpp:685-688), drawn on the device (vo_svo_set_debug_image): off by default
   void setDebugImage(bool on) { ctx_->check(vo_svo_set_debug_image(svo_, on ? 1 : 0)); }
   // the last picture: rows of width x 3 bytes (cv::Scalar component k in channel k: published as bgr8, (0,255,0) is green);

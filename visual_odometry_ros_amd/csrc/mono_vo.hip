@@ -382,6 +382,7 @@ extern "C" void vo_mvo_destroy(vo_mvo *s) {
   for (void *p : b)
     if (p) (void)hipFree(p);
   if (s->h_hdr) (void)hipHostFree(s->h_hdr);
+  vo_pose_cov_state_free(&s->core.cov);
   vo_svo_lba_free(&s->core);
   delete s;
 }
@@ -780,6 +781,42 @@ extern "C" int vo_mvo_set_debug_image(vo_mvo *s, int on) {
   return VO_OK;
 }
 
+// The covariance launch of a frame (vo_mvo_set_pose_covariance), on the main stream. carry_T01 == null: behind the steady-state
+// frame's BA launch, reading its set, its T01 and its "the BA gave nothing" word on the device. Otherwise the frame's pose is
+// carry_T01 and did not come from the BA (first image, initialisation, 5-point fallback): the chain is only carried.
+static int mvo_cov(vo_mvo *s, const float *carry_T01) {
+  vo_frame_state *f = s->c->frame;
+  const float *K = s->prm.frame.K;
+  return vo_pose_cov_state_step(s->c, &s->core.cov, false, K, K, nullptr, carry_T01, carry_T01 || !f ? nullptr : &f->hdr->cnt[5]);
+}
+
+extern "C" int vo_mvo_set_pose_covariance(vo_mvo *s, int on, double sigma_px) {
+  if (!s) return VO_ERR_INVALID;
+  if (s->pending) VO_FAIL(s->c, VO_ERR_INVALID, "vo_mvo_set_pose_covariance: a frame is in flight");
+  return vo_pose_cov_state_set(s->c, &s->core.cov, on, sigma_px);
+}
+
+extern "C" int vo_mvo_get_pose_covariance(vo_mvo *s, double P[36], double Sigma_xi[36], double *s2, int *valid, int *n_points,
+                                          int *n_unknown_steps) {
+  if (!s) return VO_ERR_INVALID;
+  if (s->pending) VO_FAIL(s->c, VO_ERR_INVALID, "call vo_mvo_result first");
+  return vo_pose_cov_state_get(s->c, &s->core.cov, P, Sigma_xi, s2, valid, n_points, n_unknown_steps);
+}
+
+extern "C" int vo_mvo_get_pose_covariance_inputs(vo_mvo *s, float *X, float *pts, int cap, int *n, float R01[9], float t01[3]) {
+  if (!s || !n) return VO_ERR_INVALID;
+  if (s->pending) VO_FAIL(s->c, VO_ERR_INVALID, "call vo_mvo_result first");
+  if (!s->init_done) VO_FAIL(s->c, VO_ERR_INVALID, "no steady-state frame has run yet");
+  float T01[16];
+  RC(vo_pose_cov_inputs(s->c, false, X, pts, nullptr, cap, n, T01));
+  for (int i = 0; i < 3; ++i) {
+    for (int j = 0; j < 3; ++j)
+      if (R01) R01[i * 3 + j] = T01[i * 4 + j];
+    if (t01) t01[i] = T01[i * 4 + 3];
+  }
+  return VO_OK;
+}
+
 extern "C" int vo_mvo_get_debug_image(vo_mvo *s, uint8_t *out, int out_stride, int *width, int *height) {
   if (!s || !width || !height) return VO_ERR_INVALID;
   vo_ctx *c = s->c;
@@ -1100,6 +1137,7 @@ extern "C" int vo_mvo_enqueue(vo_mvo *s, const void *img, int stride, int on_dev
   s->pend_kind = !s->got_first ? 0 : (!s->init_done ? 1 : 2);
   if (!s->init_done) s->chained = false;
   s->pending = true;
+  if (s->pend_kind == 2 && s->core.cov.on) RC(mvo_cov(s, nullptr));
   return VO_OK;
 }
 
@@ -1180,10 +1218,14 @@ extern "C" int vo_mvo_result(vo_mvo *s, vo_mvo_frame_info *info) {
   memset(&I, 0, sizeof(I));
   I.frame_id = s->frame_id;
   int rc = VO_OK;
-  if (s->pend_kind == 0) {
-    rc = mvo_first_image(s, &I);
-  } else if (s->pend_kind == 1) {
-    rc = mvo_second_image(s, &I);
+  if (s->pend_kind == 0 || s->pend_kind == 1) {
+    rc = s->pend_kind == 0 ? mvo_first_image(s, &I) : mvo_second_image(s, &I);
+    if (rc >= 0 && s->core.cov.on) {  // a pose that is not the BA's (identity; the 5-point pose): the chain is carried with it
+      float T01[16];
+      mvo_eye(T01);
+      rc = mvo_cov(s, s->pend_kind == 0 ? T01 : I.dT01);
+      vo_pose_cov_state_accept(&s->core.cov);
+    }
   } else {
     float dT01[16], dT10[16], T_wc[16];
     MvoHdr h;
@@ -1222,6 +1264,16 @@ extern "C" int vo_mvo_result(vo_mvo *s, vo_mvo_frame_info *info) {
     }
     svo_mul44(s->T_wp, dT01, T_wc);  // frame_curr->setPose(Twc_prev * dT01)
     svo_inv_se3(dT10, s->dT01);      // setPoseDiff10(dT10): dT01_ = inverseSE3_f(dT10)
+    if (s->core.cov.launched) {
+      // the fallback's pose is known only here: the step is issued again and only carries P with it; so is the step of a frame
+      // that was itself issued again after a join time-out (both from the same previous block)
+      if (I.counts.need_five_point)
+        rc = mvo_cov(s, dT01);
+      else if (s->core.cov.recoveries != c->frame_recoveries)
+        rc = mvo_cov(s, nullptr);
+      if (rc < 0) return rc;
+      vo_pose_cov_state_accept(&s->core.cov);
+    }
     if (!s->chained || h.pad) {
       rc = mvo_advance(s, stage, pts1, cand1, cand0, mnew, m, T_wc, T_wc, &h);
       if (rc < 0) return rc;

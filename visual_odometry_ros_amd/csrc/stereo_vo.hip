@@ -272,6 +272,7 @@ extern "C" void vo_svo_destroy(vo_svo *s) {
   vo_draw_buffers_free(&s->dbg.buf);
   if (s->dbg.fork) (void)hipEventDestroy(s->dbg.fork);
   if (s->dbg.done) (void)hipEventDestroy(s->dbg.done);
+  vo_pose_cov_state_free(&s->cov);
   vo_svo_lba_free(s);
   delete s;
 }
@@ -365,6 +366,35 @@ extern "C" int vo_svo_set_debug_image(vo_svo *s, int on) {
   }
   s->dbg.on = on != 0;
   return VO_OK;
+}
+
+// The covariance launch of the frame just enqueued (vo_svo_set_pose_covariance). first: the stream's first pair (pose = identity,
+// not from the BA): the chain is only carried.
+static int svo_cov(vo_svo *s, bool first) {
+  const vo_stereo_params &p = s->prm.frame;
+  float I[16];
+  for (int i = 0; i < 16; ++i) I[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+  vo_frame_state *f = s->c->frame;
+  return vo_pose_cov_state_step(s->c, &s->cov, true, p.Kl, p.Kr, p.T_lr, first ? I : nullptr, first || !f ? nullptr : &f->hdr->gn.is_nan);
+}
+
+extern "C" int vo_svo_set_pose_covariance(vo_svo *s, int on, double sigma_px) {
+  if (!s) return VO_ERR_INVALID;
+  if (s->pending) VO_FAIL(s->c, VO_ERR_INVALID, "call vo_svo_result first");
+  return vo_pose_cov_state_set(s->c, &s->cov, on, sigma_px);
+}
+
+extern "C" int vo_svo_get_pose_covariance(vo_svo *s, double P[36], double Sigma_xi[36], double *s2, int *valid, int *n_points,
+                                          int *n_unknown_steps) {
+  if (!s) return VO_ERR_INVALID;
+  if (s->pending) VO_FAIL(s->c, VO_ERR_INVALID, "call vo_svo_result first");
+  return vo_pose_cov_state_get(s->c, &s->cov, P, Sigma_xi, s2, valid, n_points, n_unknown_steps);
+}
+
+extern "C" int vo_svo_get_pose_covariance_inputs(vo_svo *s, float *X, float *pts_l, float *pts_r, int cap, int *n, float T01[16]) {
+  if (!s || !n) return VO_ERR_INVALID;
+  if (s->pending) VO_FAIL(s->c, VO_ERR_INVALID, "call vo_svo_result first");
+  return vo_pose_cov_inputs(s->c, true, X, pts_l, pts_r, cap, n, T01);
 }
 
 extern "C" int vo_svo_get_debug_image(vo_svo *s, uint8_t *out, int out_stride, int *width, int *height) {
@@ -469,6 +499,7 @@ extern "C" int vo_svo_enqueue(vo_svo *s, const void *left, const void *right, in
     if (rc < 0) return undo(rc);
     s->pending = true;
     s->pending_first = true;
+    if (s->cov.on) RC(svo_cov(s, true));
     return VO_OK;
   }
   // [2] T_wc_prior = T_wp * dT_pc_prev; T_cw_prior = inverseSE3_f(T_wc_prior); T_pw = getPoseInv() (stereo_vo.cpp:475-480)
@@ -499,6 +530,7 @@ extern "C" int vo_svo_enqueue(vo_svo *s, const void *left, const void *right, in
   s->pending = true;
   s->pending_first = false;
   if (s->dbg.on) RC(svo_draw(s));
+  if (s->cov.on) RC(svo_cov(s, false));
   if (g_trace) s->ht.acc[1] += svo_now() - t_in;
   return VO_OK;
 }
@@ -603,6 +635,7 @@ extern "C" int vo_svo_result(vo_svo *s, vo_svo_frame_info *info) {
     I.n_new_candidates = s->first_n_cand;
     memcpy(I.T_wc, s->T_wp, sizeof(I.T_wc));
     for (int i = 0; i < 16; ++i) I.dT[i] = (i % 5 == 0) ? 1.0f : 0.0f;
+    vo_pose_cov_state_accept(&s->cov);
     if (info) *info = I;
     return VO_OK;
   }
@@ -631,6 +664,10 @@ extern "C" int vo_svo_result(vo_svo *s, vo_svo_frame_info *info) {
 #endif
   // (a frame that was issued again after a device-side join time-out left its track set behind a second time: so is its picture)
   if (s->dbg.on && s->dbg.recoveries != c->frame_recoveries) RC(svo_draw(s));
+  if (s->cov.launched) {  // (issued again: the same step of the chain again, from the same previous block)
+    if (s->cov.recoveries != c->frame_recoveries) RC(svo_cov(s, false));
+    vo_pose_cov_state_accept(&s->cov);
+  }
   const SvoHdr h = *s->h_hdr;
   if (h.overflow) VO_FAIL(c, VO_ERR_CAPACITY, "the next track set (%d) exceeds vo_config.max_points=%d", h.n_next, s->cap);
   I.n_tracks_in = s->n;

@@ -2,6 +2,7 @@
 #pragma once
 #include <vector>
 
+#include "pose_covariance.hpp"
 #include "svo_device.hpp"
 #include "vo_internal.hpp"
 #include "vo_kernels.hpp"
@@ -48,6 +49,9 @@ struct vo_svo {
     hipEvent_t fork = nullptr, done = nullptr;
     int w = 0, h = 0, recoveries = 0;
   } dbg;
+  // vo_svo_set_pose_covariance (MonoVO: vo_mvo_set_pose_covariance): one launch of pose_covariance.hip behind every frame's BA
+  // launch, in stream order
+  VoPoseCovState cov;
   int mono = 0;  // the keyframe storage serves a MonoVO (mono_vo.hip): one observation per keyframe entry, bundled flags
   // all_stkeyframes_ (stats_keyframe): every keyframe's current pose (host) and where its related landmarks' ids are kept
   // on the device (a pool that only grows)
