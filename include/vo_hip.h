@@ -432,9 +432,14 @@ int vo_stereo_frame_recoveries(const vo_ctx *ctx);
  *                         frame's result, instead of chaining it behind the BA launch in vo_mvo_enqueue (measurement)
  *   VO_DBG_CANDS_IN_FRAME != 0: StereoVO's look-ahead loop keeps the new-point candidates of a prefetched pair inside that pair's
  *                         frame kernel instead of tracking them ahead, on the side stream, behind the pair's detection — the
- *                         same results, bit for bit (tests compare the two; the A/B lever of the measurement) */
+ *                         same results, bit for bit (tests compare the two; the A/B lever of the measurement)
+ *   VO_DBG_SBA_SPLIT      0: the local BA's steady-state iteration runs its dense solve inside the point-update launch (two
+ *                         launches per iteration); 1: three launches per iteration (solve and point update apart) — the same
+ *                         results, bit for bit (tests compare the two; the A/B lever of the measurement); >= 2: the fused launch
+ *                         with at most that many workgroups (tests: every workgroup strides over several landmark groups) */
 enum { VO_DBG_FAIL_JOIN = 0, VO_DBG_CONC_GRID = 1, VO_DBG_SBA_LDS_SOLVE = 2, VO_DBG_SKIP_DETECT = 3, VO_OPT_POLL_YIELD = 4,
-       VO_DBG_MVO_HOST_ADVANCE = 5, VO_DBG_STAGED_DETECT = 6, VO_DBG_CANDS_IN_FRAME = 7, VO_DBG_COUNT = 8 };
+       VO_DBG_MVO_HOST_ADVANCE = 5, VO_DBG_STAGED_DETECT = 6, VO_DBG_CANDS_IN_FRAME = 7, VO_DBG_SBA_SPLIT = 8,
+       VO_DBG_COUNT = 9 };
 int vo_debug_set(vo_ctx *ctx, int key, int value);
 /* Device and pinned-host allocations made on behalf of this context so far (vo_create included). A steady-state frame —
  * keyframes and their local BA included — makes none: tests/test_stereo_vo_gpu.py asserts it. */

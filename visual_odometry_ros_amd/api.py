@@ -65,13 +65,15 @@ class Context:
         self.debug_switches = {}
         if os.environ.get("VO_TEST_SWITCHES") == "1":
             for key, name in ((0, "VO_DEBUG_FAIL_JOIN"), (1, "VO_CONC_GRID"), (2, "VO_SBA_LDS_SOLVE"), (3, "VO_DEBUG_SKIP_DETECT"),
-                              (5, "VO_MVO_HOST_ADVANCE"), (6, "VO_STAGED_DETECT"), (7, "VO_CANDS_IN_FRAME")):
+                              (5, "VO_MVO_HOST_ADVANCE"), (6, "VO_STAGED_DETECT"), (7, "VO_CANDS_IN_FRAME"),
+                              (8, "VO_SBA_SPLIT")):
                 v = os.environ.get(name)
                 if v:
                     self.debug_set(key, int(v) if v.lstrip("-").isdigit() else 1)
                     self.debug_switches[name] = v
 
     DBG_FAIL_JOIN, DBG_CONC_GRID, DBG_SBA_LDS_SOLVE, DBG_SKIP_DETECT, OPT_POLL_YIELD, DBG_MVO_HOST_ADVANCE, DBG_STAGED_DETECT, DBG_CANDS_IN_FRAME = 0, 1, 2, 3, 4, 5, 6, 7
+    DBG_SBA_SPLIT = 8
 
     @property
     def sum_order(self):

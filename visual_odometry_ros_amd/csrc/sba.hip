@@ -17,13 +17,17 @@
 //   sba_solve_reg_kernel<42>  the steady-state window: reduced system assembled into LDS by 512 lanes, then one
 //                      wavefront: pivot order from the original diagonal, rows of the permuted matrix in registers,
 //                      Eigen-order LDLT, x; pose updates exp(log(exp(x) exp(log T))); average error (second wavefront)
+//   sba_solve_point_kernel<N>  the steady-state iteration: that solve by EVERY workgroup of the point update, which then
+//                      updates and re-linearises its landmark groups from x and the poses in its own LDS
 //   sba_assemble_kernel + sba_solve_kernel  the same for any other size (one lane per entry; matrix in LDS)
-// Three launches per iteration in the steady-state window (four otherwise), no host round trip inside the solve.
+// Two launches per iteration in the steady-state window (three behind VO_DBG_SBA_SPLIT, four with the general solve), no host
+// round trip inside the solve.
 // The quirks listed in oracle/oracle_sba.c (B assigned not accumulated, left-only Schur loops, symmetrisation
 // overwrite, calc_Qij_t_Qij_weight's zero entries) are reproduced.
 #include <stdlib.h>
 #include <time.h>
 
+#include <algorithm>
 #include <vector>
 
 #include "vo_internal.hpp"
@@ -742,111 +746,86 @@ __device__ __forceinline__ long long sba_stamp_after(double dep) {
   return t;
 }
 #define SBA_SOLVE_WG 512
+// ---- the reduced system out of the partial sums (what sba_assemble_kernel does for the general kernel), by all
+// eight wavefronts straight into LDS: entry t of the packed lower triangle, then the right-hand side. An entry is two
+// sums of eight partials; a thread's (at most two) entries issue all their loads before anything waits: one exposure
+// of the memory latency instead of four.
 template <int N>
-__global__ __launch_bounds__(SBA_SOLVE_WG) void sba_solve_reg_kernel(SbaDev d, int iter) {
-  __shared__ double sL[N * N + N];  // first the reduced system (lower triangle, G(i,j) at [i * N + j]; rhs behind), later L
-  __shared__ double s_dg[N];
-  __shared__ int s_sig[N];
-  __shared__ double s_Tpre[64 * 16];  // exp(log(T_f)) of the frames' poses, made by the third wavefront during the solve
-  const int tid = threadIdx.x, lane = tid & 63;
-  const long long t_0 = (long long)__builtin_amdgcn_s_memrealtime();
-  // ---- the reduced system out of the partial sums (what sba_assemble_kernel does for the general kernel), by all
-  // eight wavefronts straight into LDS: entry t of the packed lower triangle, then the right-hand side. An entry is two
-  // sums of eight partials; a thread's (at most two) entries issue all their loads before anything waits: one exposure
-  // of the memory latency instead of four.
-  {
-    constexpr int TRI = N * (N + 1) / 2, TOT = TRI + N, PER = (TOT + SBA_SOLVE_WG - 1) / SBA_SOLVE_WG;
-    const int No = d.n_opt;
-    const double *p0[PER], *p1[PER];
-    int s1[PER], mode[PER], dst[PER];  // mode 0: -(sum p0); 1: sum p1 - sum p0; 2: the same with the damped diagonal; 3: rhs
-    double v0[PER][SBA_SG], v1[PER][SBA_PG];
+__device__ __forceinline__ void sba_assemble_lds(const SbaDev &d, double *__restrict__ sL, int tid) {
+  constexpr int TRI = N * (N + 1) / 2, TOT = TRI + N, PER = (TOT + SBA_SOLVE_WG - 1) / SBA_SOLVE_WG;
+  const int No = d.n_opt;
+  const double *p0[PER], *p1[PER];
+  int s1[PER], mode[PER], dst[PER];  // mode 0: -(sum p0); 1: sum p1 - sum p0; 2: the same with the damped diagonal; 3: rhs
+  double v0[PER][SBA_SG], v1[PER][SBA_PG];
 #pragma unroll
-    for (int e = 0; e < PER; ++e) {
-      const int t = tid + e * SBA_SOLVE_WG;
-      mode[e] = -1;
-      p0[e] = p1[e] = d.S;
-      s1[e] = 0;
-      dst[e] = 0;
-      if (t < TRI) {
-        int row = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-        while (row * (row + 1) / 2 > t) --row;
-        while ((row + 1) * (row + 2) / 2 <= t) ++row;
-        const int col = t - row * (row + 1) / 2;
-        const int j = row / 6, r = row - 6 * j, u = col / 6, c = col - 6 * u;  // u <= j (sba_reduced_entry)
-        p0[e] = d.S + 36 * (((size_t)u * No + j) * SBA_SG) + (c * 6 + r);      // block (u,j), read transposed
-        p1[e] = d.Apart + 48 * ((size_t)j * SBA_PG) + (r * 6 + c);
-        s1[e] = 48;
-        mode[e] = j != u ? 0 : (r == c ? 2 : 1);
-        dst[e] = row * N + col;
-      } else if (t < TOT) {
-        const int q = t - TRI, j = q / 6, r = q - 6 * j;
-        p0[e] = d.Apart + 48 * ((size_t)j * SBA_PG) + 36 + r;  // a_j
-        p1[e] = d.Apart + 48 * ((size_t)j * SBA_PG) + 42 + r;  // (B C^-1 b)_j
-        s1[e] = 48;
-        mode[e] = 3;
-        dst[e] = N * N + q;
-      }
-    }
-#pragma unroll
-    for (int e = 0; e < PER; ++e) {
-      const int s0 = mode[e] == 3 ? 48 : 36;
-#pragma unroll
-      for (int g = 0; g < SBA_SG; ++g) v0[e][g] = p0[e][(size_t)s0 * g];
-#pragma unroll
-      for (int g = 0; g < SBA_PG; ++g) v1[e][g] = p1[e][(size_t)s1[e] * g];
-    }
-#pragma unroll
-    for (int e = 0; e < PER; ++e) {
-      double a = 0.0, b2 = 0.0;
-#pragma unroll
-      for (int g = 0; g < SBA_SG; ++g) a += v0[e][g];
-#pragma unroll
-      for (int g = 0; g < SBA_PG; ++g) b2 += v1[e][g];
-      if (mode[e] == 2) b2 += d.lambda * b2;  // :433-441
-      if (mode[e] >= 0) sL[dst[e]] = mode[e] == 0 ? -a : (mode[e] == 3 ? a - b2 : b2 - a);  // rhs: a - bcb (:508-509)
+  for (int e = 0; e < PER; ++e) {
+    const int t = tid + e * SBA_SOLVE_WG;
+    mode[e] = -1;
+    p0[e] = p1[e] = d.S;
+    s1[e] = 0;
+    dst[e] = 0;
+    if (t < TRI) {
+      int row = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
+      while (row * (row + 1) / 2 > t) --row;
+      while ((row + 1) * (row + 2) / 2 <= t) ++row;
+      const int col = t - row * (row + 1) / 2;
+      const int j = row / 6, r = row - 6 * j, u = col / 6, c = col - 6 * u;  // u <= j (sba_reduced_entry)
+      p0[e] = d.S + 36 * (((size_t)u * No + j) * SBA_SG) + (c * 6 + r);      // block (u,j), read transposed
+      p1[e] = d.Apart + 48 * ((size_t)j * SBA_PG) + (r * 6 + c);
+      s1[e] = 48;
+      mode[e] = j != u ? 0 : (r == c ? 2 : 1);
+      dst[e] = row * N + col;
+    } else if (t < TOT) {
+      const int q = t - TRI, j = q / 6, r = q - 6 * j;
+      p0[e] = d.Apart + 48 * ((size_t)j * SBA_PG) + 36 + r;  // a_j
+      p1[e] = d.Apart + 48 * ((size_t)j * SBA_PG) + 42 + r;  // (B C^-1 b)_j
+      s1[e] = 48;
+      mode[e] = 3;
+      dst[e] = N * N + q;
     }
   }
-  const long long t_a = sba_stamp_after(0.0);
-  __syncthreads();
-  const long long t_b = sba_stamp_after(0.0);
-  const bool pre_staged = d.n_frames <= 64;
-  const bool deliver = d.res_host && pre_staged && iter == d.max_iter - 1;  // (uniform: see SbaDev::res_host)
-  if (tid >= 192) return;
-  if (tid >= 128) {
-    // the third wavefront: the half of the pose update that does not need x — xi = log(T), exp(xi) (:563-566) — one
-    // frame per lane, next to the factorisation; wavefront 0 picks the results up from LDS behind its solve
-    if (pre_staged) {
-      const int f = lane;
-      if (f < d.n_frames && d.opt_index[f] >= 0) {
-        double Tjw[16];
-        sba_pose_pre(d.T + 16 * (size_t)f, Tjw);
 #pragma unroll
-        for (int q = 0; q < 16; ++q) s_Tpre[f * 16 + q] = Tjw[q];
-      }
-      __syncthreads();  // (with wavefront 0, below: the only two wavefronts that are left by then need not be — a
-    }                   //  wavefront that has ended does not hold a barrier up)
-    return;
+  for (int e = 0; e < PER; ++e) {
+    const int s0 = mode[e] == 3 ? 48 : 36;
+#pragma unroll
+    for (int g = 0; g < SBA_SG; ++g) v0[e][g] = p0[e][(size_t)s0 * g];
+#pragma unroll
+    for (int g = 0; g < SBA_PG; ++g) v1[e][g] = p1[e][(size_t)s1[e] * g];
   }
-  if (tid >= 64) {
-    // the second wavefront: average pixel error of this iteration's linearisation point (:594-601), next to the solve
-    double e = 0.0;
-    int i = lane;
-    for (; i + 7 * 64 < d.n_err; i += 8 * 64) {
-      double v[8];
 #pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = d.err_part[i + 64 * q];
+  for (int e = 0; e < PER; ++e) {
+    double a = 0.0, b2 = 0.0;
 #pragma unroll
-      for (int q = 0; q < 8; ++q) e += v[q];
-    }
-    for (; i < d.n_err; i += 64) e += d.err_part[i];
-    e = sba_wave_sum(e);
-    if (lane == 0) {
-      d.avg_err[iter] = sqrt(e / (double)(d.dyn ? d.dyn[1] : d.n_obs));
-      if (e != e) atomicOr(d.flags, 2);
-    }
-    if (deliver) __syncthreads();  // (the error and its flag are part of what wavefront 0 sends to the host behind this barrier)
-    return;
+    for (int g = 0; g < SBA_SG; ++g) a += v0[e][g];
+#pragma unroll
+    for (int g = 0; g < SBA_PG; ++g) b2 += v1[e][g];
+    if (mode[e] == 2) b2 += d.lambda * b2;  // :433-441
+    if (mode[e] >= 0) sL[dst[e]] = mode[e] == 0 ? -a : (mode[e] == 3 ? a - b2 : b2 - a);  // rhs: a - bcb (:508-509)
   }
+}
+// average pixel error of this iteration's linearisation point (:594-601): one wavefront
+__device__ __forceinline__ void sba_error_wave(const SbaDev &d, int iter, int lane) {
+  double e = 0.0;
+  int i = lane;
+  for (; i + 7 * 64 < d.n_err; i += 8 * 64) {
+    double v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = d.err_part[i + 64 * q];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) e += v[q];
+  }
+  for (; i < d.n_err; i += 64) e += d.err_part[i];
+  e = sba_wave_sum(e);
+  if (lane == 0) {
+    d.avg_err[iter] = sqrt(e / (double)(d.dyn ? d.dyn[1] : d.n_obs));
+    if (e != e) atomicOr(d.flags, 2);
+  }
+}
+// ---- the dense solve by ONE wavefront: pivot order, rows into registers, LDLT, the two sweeps, P^T. sL holds the reduced
+// system (sba_assemble_lds) and is overwritten with L; x is left in s_dg behind a wave-level synchronisation.
+template <int N>
+__device__ __forceinline__ void sba_reg_solve_wave(double *sL, double *s_dg, int *s_sig, int lane, long long &t_1,
+                                                   long long &t_f, long long &t_2) {
   // ---- pivot order (see sba_solve_kernel): descending |diagonal| unless two are exactly equal
   {
     const double v = lane < N ? fabs(sL[lane * N + lane]) : -1.0;
@@ -895,7 +874,7 @@ __global__ __launch_bounds__(SBA_SOLVE_WG) void sba_solve_reg_kernel(SbaDev d, i
   for (int j = 0; j < N; ++j) r[j] = (lane < N && j <= lane) ? r[j] : 0.0;
   double y = lane < N ? sL[N * N + my] : 0.0;
   SBA_WAVE_SYNC();  // (sL is written again below)
-  const long long t_1 = sba_stamp_after(r[0] + y);
+  t_1 = sba_stamp_after(r[0] + y);
   // ---- Eigen::LDLT (lower, in place), left-looking, fully unrolled. (temp[j] through LDS — one store by lane k, a
   // broadcast read by all — was measured slower than the lane broadcasts: 22 vs 17 us, two LDS round trips per step.)
   // Scheduled column by column: once column j is final its contribution L(i,j) * (D_j L(k,j)) goes into the accumulator of
@@ -919,7 +898,7 @@ __global__ __launch_bounds__(SBA_SOLVE_WG) void sba_solve_reg_kernel(SbaDev d, i
 #pragma unroll
     for (int k = j + 1; k < N; ++k) acc[k] += r[j] * sba_rl(wj, k);
   }
-  const long long t_f = sba_stamp_after(dgl + r[N - 1]);
+  t_f = sba_stamp_after(dgl + r[N - 1]);
   // ---- solve: x = P^T L^-T D^+ L^-1 (P rhs); the entry of lane i stays in a register
 #pragma unroll
   for (int j = 0; j < N; ++j) {
@@ -937,10 +916,49 @@ __global__ __launch_bounds__(SBA_SOLVE_WG) void sba_solve_reg_kernel(SbaDev d, i
     if (lane < q) y -= sL[q * N + lane] * yq;
   }
   // P^T: scatter back through sig
-  double *xs = s_dg;
-  if (lane < N) xs[my] = y;
+  if (lane < N) s_dg[my] = y;
   SBA_WAVE_SYNC();
-  const long long t_2 = sba_stamp_after(y);
+  t_2 = sba_stamp_after(y);
+}
+template <int N>
+__global__ __launch_bounds__(SBA_SOLVE_WG) void sba_solve_reg_kernel(SbaDev d, int iter) {
+  __shared__ double sL[N * N + N];  // first the reduced system (lower triangle, G(i,j) at [i * N + j]; rhs behind), later L
+  __shared__ double s_dg[N];
+  __shared__ int s_sig[N];
+  __shared__ double s_Tpre[64 * 16];  // exp(log(T_f)) of the frames' poses, made by the third wavefront during the solve
+  const int tid = threadIdx.x, lane = tid & 63;
+  const long long t_0 = (long long)__builtin_amdgcn_s_memrealtime();
+  sba_assemble_lds<N>(d, sL, tid);
+  const long long t_a = sba_stamp_after(0.0);
+  __syncthreads();
+  const long long t_b = sba_stamp_after(0.0);
+  const bool pre_staged = d.n_frames <= 64;
+  const bool deliver = d.res_host && pre_staged && iter == d.max_iter - 1;  // (uniform: see SbaDev::res_host)
+  if (tid >= 192) return;
+  if (tid >= 128) {
+    // the third wavefront: the half of the pose update that does not need x — xi = log(T), exp(xi) (:563-566) — one
+    // frame per lane, next to the factorisation; wavefront 0 picks the results up from LDS behind its solve
+    if (pre_staged) {
+      const int f = lane;
+      if (f < d.n_frames && d.opt_index[f] >= 0) {
+        double Tjw[16];
+        sba_pose_pre(d.T + 16 * (size_t)f, Tjw);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) s_Tpre[f * 16 + q] = Tjw[q];
+      }
+      __syncthreads();  // (with wavefront 0, below: the only two wavefronts that are left by then need not be — a
+    }                   //  wavefront that has ended does not hold a barrier up)
+    return;
+  }
+  if (tid >= 64) {
+    // the second wavefront: average pixel error of this iteration's linearisation point (:594-601), next to the solve
+    sba_error_wave(d, iter, lane);
+    if (deliver) __syncthreads();  // (the error and its flag are part of what wavefront 0 sends to the host behind this barrier)
+    return;
+  }
+  long long t_1, t_f, t_2;
+  sba_reg_solve_wave<N>(sL, s_dg, s_sig, lane, t_1, t_f, t_2);
+  double *xs = s_dg;
   if (lane < N) d.x[lane] = xs[lane];
   // pose updates (:560-576)
   if (pre_staged) {
@@ -982,74 +1000,81 @@ __global__ __launch_bounds__(SBA_SOLVE_WG) void sba_solve_reg_kernel(SbaDev d, i
 // poses the solve of iteration k left): one launch instead of two. update != 0: X_i += y_i first; point != 0: then
 // C_i, b_i (sums over the observations), damping, Eigen-order 3x3 LDLT inverse, C^-1 b, and per slot B_ji (Qij^T Rij of
 // the LAST observation of landmark i in keyframe j, :315 / :410 assign), B_ji C_i^-1 (:471) and (B_ji C_i^-1) b_i (:473).
-template <bool TLDS>
-__global__ __launch_bounds__(64) void sba_update_point_kernel(SbaDev d, int update, int point) {
-  __shared__ double sT[TLDS ? 16 * SBA_LDS_FRAMES : 2];
-  __shared__ double sx[6 * SBA_MAX_OPT];
-  const int lane = threadIdx.x, sub = lane & (SBA_LQ - 1);
-  const long long st0 = SBA_TICK();
-  const int M = d.dyn ? d.dyn[0] : d.M;
-  if ((int)blockIdx.x * (64 / SBA_LQ) >= M) {  // (a launch sized by an upper bound of M)
-    if (point && lane == 0) d.err_part[blockIdx.x] = 0.0;
-    return;
-  }
-  const int i_raw = blockIdx.x * (64 / SBA_LQ) + lane / SBA_LQ;
-  const bool live = i_raw < M;
-  const int i = live ? i_raw : M - 1;  // a surplus quad repeats the last landmark and stores nothing (DPP needs all lanes)
-  // (the landmark's own loads are issued next to the staging of poses and x: one round of latency instead of two)
-  double X[3] = {d.X[3 * (size_t)i], d.X[3 * (size_t)i + 1], d.X[3 * (size_t)i + 2]};
+// What a landmark group (64 / SBA_LQ landmarks, one wavefront) loads before it computes: everything a landmark's lane
+// group will read next is known once its four list pointers are.
+constexpr int SBA_NPRE = 3;
+struct SbaPointPre {
+  int i, s0, s1, o0, o1, sA;
+  bool live, hasA;
+  double X[3];
+  double preBC[18], preCb[3], pre_px[SBA_NPRE][2];
+  int pre_j, pre_bobs, pre_f[SBA_NPRE], pre_r[SBA_NPRE];
+};
+// the landmark's own loads: issued next to whatever the caller does in front of sba_point_update (the staging of poses and
+// x; in sba_solve_point_kernel the whole dense solve). The group must hold a landmark (group * (64 / SBA_LQ) < M).
+__device__ __forceinline__ void sba_point_load(const SbaDev &d, int group, int M, int lane, int update, int point, SbaPointPre &P) {
+  const int sub = lane & (SBA_LQ - 1);
+  const int i_raw = group * (64 / SBA_LQ) + lane / SBA_LQ;
+  P.live = i_raw < M;
+  const int i = P.live ? i_raw : M - 1;  // a surplus quad repeats the last landmark and stores nothing (DPP needs all lanes)
+  P.i = i;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) P.X[c] = d.X[3 * (size_t)i + c];
   const int s0 = d.slot_ptr[i], s1 = d.slot_ptr[i + 1];
   const int o0 = d.obs_ptr[i], o1 = d.obs_ptr[i + 1];
-  if (TLDS)
-    for (int k = lane; k < 16 * d.n_frames; k += 64) sT[k] = d.T[k];
-  if (update)
-    for (int k = lane; k < 6 * d.n_opt; k += 64) sx[k] = d.x[k];
-  // Everything a landmark's lane group will read next is known once the four pointers above are: the slot blocks of the
-  // update, the landmark's observations (SBA_NPRE rounds of SBA_LQ: 24 observations cover a nine-keyframe stereo window) and
-  // the slots' observation indices go out as ONE batch here — the first version met them as five to seven dependent rounds
-  // of loads, each a microsecond on a wavefront with nothing else to do. Indices are clamped into the landmark's own range
-  // (every landmark has observations; the arrays have a spare entry for a landmark without slots); what a lane does not own
-  // is loaded and not used. The arithmetic and its order per lane are unchanged.
-  constexpr int SBA_NPRE = 3;
+  P.s0 = s0;
+  P.s1 = s1;
+  P.o0 = o0;
+  P.o1 = o1;
+  // The slot blocks of the update, the landmark's observations (SBA_NPRE rounds of SBA_LQ: 24 observations cover a
+  // nine-keyframe stereo window) and the slots' observation indices go out as ONE batch here — the first version met them as
+  // five to seven dependent rounds of loads, each a microsecond on a wavefront with nothing else to do. Indices are clamped
+  // into the landmark's own range (every landmark has observations; the arrays have a spare entry for a landmark without
+  // slots); what a lane does not own is loaded and not used. The arithmetic and its order per lane are unchanged.
   const int sA = s0 + sub;
   const bool hasA = sA < s1;
   const int sL = hasA ? sA : s0;  // (what is loaded for a lane without a slot: the landmark's first, or the spare entry)
-  double preBC[18];
-  int pre_j = 0, pre_bobs = o0;
-  double preCb[3] = {0, 0, 0};
+  P.sA = sA;
+  P.hasA = hasA;
+  P.pre_j = 0;
+  P.pre_bobs = o0;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) P.preCb[c] = 0.0;
   if (update) {
     const double *BC = d.BCs + 18 * (size_t)sL;
 #pragma unroll
-    for (int k = 0; k < 18; ++k) preBC[k] = BC[k];
-    pre_j = d.slot_j[sL];
+    for (int k = 0; k < 18; ++k) P.preBC[k] = BC[k];
+    P.pre_j = d.slot_j[sL];
 #pragma unroll
-    for (int c = 0; c < 3; ++c) preCb[c] = d.Cinvb[3 * (size_t)i + c];
+    for (int c = 0; c < 3; ++c) P.preCb[c] = d.Cinvb[3 * (size_t)i + c];
   }
-  double pre_px[SBA_NPRE][2];
-  int pre_f[SBA_NPRE], pre_r[SBA_NPRE];
   if (point) {
 #pragma unroll
     for (int q = 0; q < SBA_NPRE; ++q) {
       const int o = max(min(o0 + sub + SBA_LQ * q, o1 - 1), 0);
-      pre_px[q][0] = d.obs_px[2 * o];
-      pre_px[q][1] = d.obs_px[2 * o + 1];
-      pre_f[q] = d.obs_frame[o];
-      pre_r[q] = d.obs_right[o];
+      P.pre_px[q][0] = d.obs_px[2 * o];
+      P.pre_px[q][1] = d.obs_px[2 * o + 1];
+      P.pre_f[q] = d.obs_frame[o];
+      P.pre_r[q] = d.obs_right[o];
     }
-    pre_bobs = d.slot_bobs[sL];
+    P.pre_bobs = d.slot_bobs[sL];
   }
-  __syncthreads();
-  __builtin_amdgcn_sched_barrier(0);  // (the batch above stays above: the scheduler would sink the loads to their uses)
-  const long long st1 = SBA_TICK();
-  if (update) {
+}
+// the group's arithmetic behind its loads, in two parts. The update X_i += y_i needs x (sx, in LDS) but no pose: it leaves the
+// new X_i in P.X (sba_solve_point_kernel runs it next to the solve wavefront's pose update)
+__device__ __forceinline__ void sba_point_update(const SbaDev &d, const double *sx, int lane, SbaPointPre &P) {
+  const int sub = lane & (SBA_LQ - 1);
+  const int i = P.i, s1 = P.s1, sA = P.sA;
+  const bool live = P.live, hasA = P.hasA;
+  {
     double cbx[3] = {0, 0, 0};
     if (hasA) {
-      const double *x = sx + 6 * pre_j;
+      const double *x = sx + 6 * P.pre_j;
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         double t = 0.0;
 #pragma unroll
-        for (int r = 0; r < 6; ++r) t += preBC[r * 3 + c] * x[r];
+        for (int r = 0; r < 6; ++r) t += P.preBC[r * 3 + c] * x[r];
         cbx[c] += t;
       }
     }
@@ -1065,14 +1090,22 @@ __global__ __launch_bounds__(64) void sba_update_point_kernel(SbaDev d, int upda
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      X[c] += preCb[c] - sba_quad_sum(cbx[c]);
-      if (live && sub == 0) d.X[3 * (size_t)i + c] = X[c];
+      P.X[c] += P.preCb[c] - sba_quad_sum(cbx[c]);
+      if (live && sub == 0) d.X[3 * (size_t)i + c] = P.X[c];
     }
   }
-  if (!point) return;
+}
+// the linearisation at P.X: sT (TLDS: the poses in LDS) is complete; the group's squared-error sum goes to err_dst[group]
+template <bool TLDS>
+__device__ __forceinline__ void sba_point_linearize(const SbaDev &d, const double *sT, int group, int lane, SbaPointPre &P,
+                                                    double *err_dst, long long st0, long long st1) {
+  const int sub = lane & (SBA_LQ - 1);
+  const int i = P.i, s1 = P.s1, o0 = P.o0, o1 = P.o1, sA = P.sA;
+  const bool live = P.live, hasA = P.hasA;
+  const double X[3] = {P.X[0], P.X[1], P.X[2]};
   const long long st2 = SBA_TICK();
   // the first slot's observation (index known since the batch): on its way while the observations are linearised
-  const int ob = hasA ? pre_bobs : o0;
+  const int ob = hasA ? P.pre_bobs : o0;
   const double slot_px[2] = {d.obs_px[2 * ob], d.obs_px[2 * ob + 1]};
   const int slot_f = d.obs_frame[ob], slot_r = d.obs_right[ob];
   __builtin_amdgcn_sched_barrier(0);
@@ -1092,7 +1125,7 @@ __global__ __launch_bounds__(64) void sba_update_point_kernel(SbaDev d, int upda
   };
 #pragma unroll
   for (int q = 0; q < SBA_NPRE; ++q)
-    if (o0 + sub + SBA_LQ * q < o1) one_obs(pre_px[q], pre_f[q], pre_r[q]);
+    if (o0 + sub + SBA_LQ * q < o1) one_obs(P.pre_px[q], P.pre_f[q], P.pre_r[q]);
   for (int o = o0 + sub + SBA_LQ * SBA_NPRE; o < o1; o += SBA_LQ) {
     const double px[2] = {d.obs_px[2 * o], d.obs_px[2 * o + 1]};
     one_obs(px, d.obs_frame[o], d.obs_right[o]);
@@ -1152,7 +1185,136 @@ __global__ __launch_bounds__(64) void sba_update_point_kernel(SbaDev d, int upda
   SBA_STAMP_MAX(13, st4, st3);
   SBA_STAMP_MAX(14, st5, st4);
   const double e = sba_wave_sum(live && sub == 0 ? err : 0.0);
-  if (lane == 0) d.err_part[blockIdx.x] = e;
+  if (lane == 0) err_dst[group] = e;
+}
+
+template <bool TLDS>
+__global__ __launch_bounds__(64) void sba_update_point_kernel(SbaDev d, int update, int point) {
+  __shared__ double sT[TLDS ? 16 * SBA_LDS_FRAMES : 2];
+  __shared__ double sx[6 * SBA_MAX_OPT];
+  const int lane = threadIdx.x;
+  const long long st0 = SBA_TICK();
+  const int M = d.dyn ? d.dyn[0] : d.M;
+  // (the fused path's first launch, when its first iteration reads the second pose buffer: the initial poses go across)
+  if (d.T_out && blockIdx.x == 0)
+    for (int k = lane; k < 16 * d.n_frames; k += 64) d.T_out[k] = d.T[k];
+  if ((int)blockIdx.x * (64 / SBA_LQ) >= M) {  // (a launch sized by an upper bound of M)
+    if (point && lane == 0) {
+      d.err_part[blockIdx.x] = 0.0;
+      if (d.err_out) d.err_out[blockIdx.x] = 0.0;  // (the fused path's second buffer: its surplus groups are never written again)
+    }
+    return;
+  }
+  SbaPointPre P;
+  sba_point_load(d, blockIdx.x, M, lane, update, point, P);
+  // (the landmark's own loads are issued next to the staging of poses and x: one round of latency instead of two)
+  if (TLDS)
+    for (int k = lane; k < 16 * d.n_frames; k += 64) sT[k] = d.T[k];
+  if (update)
+    for (int k = lane; k < 6 * d.n_opt; k += 64) sx[k] = d.x[k];
+  __syncthreads();
+  __builtin_amdgcn_sched_barrier(0);  // (the batch above stays above: the scheduler would sink the loads to their uses)
+  const long long st1 = SBA_TICK();
+  if (update) sba_point_update(d, sx, lane, P);
+  if (point) sba_point_linearize<TLDS>(d, sT, blockIdx.x, lane, P, d.err_part, st0, st1);
+}
+
+// ---- the dense solve INSIDE the point-update launch (the steady-state iteration: two launches instead of three) ----------
+// Every workgroup assembles and solves the reduced system for itself, from the partial sums sba_pose_schur_kernel left behind
+// an ordinary kernel boundary, and then updates and re-linearises its own landmark groups from x and the poses in its own
+// LDS: the point update is a one-to-many consumer of a tiny result, and handing that result from one workgroup to the others
+// inside a launch (flags, polling, grid barriers: tools/rejected/) costs more than the boundary. Here NO workgroup reads what
+// another workgroup of the same launch writes: poses are read from d.T and written (workgroup 0) to d.T_out, the groups' error
+// sums are read (workgroup 0) from d.err_part and written to d.err_out, x is used from LDS and stored for the record only.
+// Wavefront 0 solves, 1 sums the error (workgroup 0 only), 2 makes exp(log T_f); wavefronts 4..7 issue the load batch of their
+// landmark group BEFORE the assembly and wait for it behind the solve, so the point phase starts without a launch ramp and
+// with its loads complete. The solve's 2 N doubles per lane and the point phase's ~150 registers never meet in one
+// wavefront. LAST: the trailing update without a re-linearisation.
+template <int N, bool LAST>
+__global__ __launch_bounds__(SBA_SOLVE_WG) void sba_solve_point_kernel(SbaDev d, int iter) {
+  __shared__ double sL[N * N + N];
+  __shared__ double s_dg[N];  // |diagonal| during a tie pre-pass, then x
+  __shared__ int s_sig[N];
+  __shared__ double s_Tpre[SBA_LDS_FRAMES * 16];
+  __shared__ double sT[SBA_LDS_FRAMES * 16];  // the poses the point phase linearises at: old ones, then the updated ones
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const long long t_0 = (long long)__builtin_amdgcn_s_memrealtime();
+  const int M = d.dyn ? d.dyn[0] : d.M;
+  const int n_grp = min((M + 64 / SBA_LQ - 1) / (64 / SBA_LQ), d.n_err);  // landmark groups that hold a landmark
+  if (blockIdx.x != 0 && (int)blockIdx.x * SBA_FUSED_PW >= n_grp) return;
+  int g = (int)blockIdx.x * SBA_FUSED_PW + (wave - (SBA_SOLVE_WG / 64 - SBA_FUSED_PW));
+  const bool pt = wave >= SBA_SOLVE_WG / 64 - SBA_FUSED_PW && g < n_grp;
+  SbaPointPre P;
+  if (pt) sba_point_load(d, g, M, lane, 1, LAST ? 0 : 1, P);
+  for (int k = tid; k < 16 * d.n_frames; k += SBA_SOLVE_WG) sT[k] = d.T[k];
+  sba_assemble_lds<N>(d, sL, tid);
+  const long long t_a = sba_stamp_after(0.0);
+  __syncthreads();
+  const long long t_b = sba_stamp_after(0.0);
+  // (from here on every barrier is met by all eight wavefronts, on either side of this branch: two more)
+  if (wave < SBA_SOLVE_WG / 64 - SBA_FUSED_PW) {
+    long long t_1 = 0, t_f = 0, t_2 = 0;
+    if (wave == 0) {
+      sba_reg_solve_wave<N>(sL, s_dg, s_sig, lane, t_1, t_f, t_2);
+    } else if (wave == 1) {
+      if (blockIdx.x == 0) sba_error_wave(d, iter, lane);
+    } else if (wave == 2) {
+      const int f = lane;
+      if (f < d.n_frames && d.opt_index[f] >= 0) {
+        double Tjw[16];
+        sba_pose_pre(d.T + 16 * (size_t)f, Tjw);
+#pragma unroll
+        for (int q = 0; q < 16; ++q) s_Tpre[f * 16 + q] = Tjw[q];
+      }
+    }
+    __syncthreads();  // x and the exp(log(T_f)) are in LDS (and, workgroup 0, the error and its flag in memory)
+    const double *xs = s_dg;
+    if (wave == 0) {  // pose updates (:560-576), into LDS
+      const int f = lane, j = f < d.n_frames ? d.opt_index[f] : -1;
+      if (j >= 0) {
+        double Tjw[16];
+#pragma unroll
+        for (int q = 0; q < 16; ++q) Tjw[q] = s_Tpre[f * 16 + q];
+        sba_pose_post(sT + 16 * f, Tjw, xs + 6 * j);
+      }
+    }
+    __syncthreads();  // the updated poses are in LDS
+    if (blockIdx.x != 0 || wave != 0) return;
+    // workgroup 0 keeps the record: x, every pose (fixed ones are copied across), the result block for the host, the ticks
+    if (lane < N) d.x[lane] = xs[lane];
+    for (int k = lane; k < 16 * d.n_frames; k += 64) d.T_out[k] = sT[k];
+    if (d.res_host && iter == d.max_iter - 1) {
+      // the last iteration: poses, errors, flags and counts are final (d.T_out is then the block res_src points at)
+      SBA_WAVE_SYNC();  // (this wavefront's own pose stores above)
+      for (int k = lane; k < d.res_words; k += 64)
+        if (k != d.res_seq_word) d.res_host[k] = d.res_src[k];
+      __threadfence_system();
+      if (lane == 0) __hip_atomic_store(&d.res_host[d.res_seq_word], d.res_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+    if (lane == 0) {
+      d.flags[1] = (int)(t_1 - t_0);
+      d.flags[2] = (int)(t_2 - t_1);
+      d.flags[3] = (int)((long long)__builtin_amdgcn_s_memrealtime() - t_2);
+      d.flags[4] = (int)(t_a - t_0);
+      d.flags[5] = (int)(t_b - t_a);
+      d.flags[6] = (int)(t_1 - t_b);
+      d.flags[7] = (int)(t_f - t_1);
+    }
+    return;
+  }
+  __syncthreads();  // x is in LDS
+  __builtin_amdgcn_sched_barrier(0);  // (the first group's batch stays in front of the solve)
+  if (pt) sba_point_update(d, s_dg, lane, P);  // (needs no pose: next to the solve wavefront's pose update)
+  __syncthreads();  // the updated poses are in LDS
+  if (!pt) return;
+  const int stride = (int)gridDim.x * SBA_FUSED_PW;
+  for (;;) {
+    if (!LAST) sba_point_linearize<true>(d, sT, g, lane, P, d.err_out, 0LL, 0LL);
+    g += stride;
+    if (g >= n_grp) break;
+    sba_point_load(d, g, M, lane, 1, LAST ? 0 : 1, P);
+    sba_point_update(d, s_dg, lane, P);
+  }
 }
 
 // ---- host side ---------------------------------------------------------------------
@@ -1200,6 +1362,7 @@ size_t vo_sba_place_work(SbaDev *d, uint8_t *base, size_t off, size_t M, size_t 
   const size_t oS = ar.take(sizeof(double) * 36 * SBA_SG * ((size_t)No * No + 1));
   const size_t oG = ar.take(sizeof(double) * ((size_t)36 * No * No + 6 * No + 1));
   const size_t ox = ar.take(sizeof(double) * 6 * (size_t)(No + 1));
+  const size_t oT2 = ar.take(sizeof(double) * 16 * SBA_LDS_FRAMES), oErr2 = ar.take(sizeof(double) * (size_t)(n_err + 1));
   (void)max_iter;
   if (base) {
     d->Cinvb = (double *)(base + oCinvb);
@@ -1213,6 +1376,8 @@ size_t vo_sba_place_work(SbaDev *d, uint8_t *base, size_t off, size_t M, size_t 
     d->S = (double *)(base + oS);
     d->G = (double *)(base + oG);
     d->x = (double *)(base + ox);
+    d->T_alt = (double *)(base + oT2);
+    d->err_alt = (double *)(base + oErr2);
   }
   return ar.off;
 }
@@ -1222,11 +1387,58 @@ bool vo_sba_delivers_result(const vo_ctx *c, const SbaDev &d) {
   return d.res_host && d.max_iter > 0 && sba_reg_solve(c, d.n_opt) && d.n_frames <= 64;
 }
 
-// three launches per iteration in the steady-state window (four otherwise): [update of the previous iteration +
-// per-landmark linearisation] -> [pose sums + Schur blocks] -> [assembly ->] solve; one last update behind the loop
+// The steady-state window (1..8 optimised poses among at most SBA_LDS_FRAMES frames) takes the fused iteration: one
+// [per-landmark linearisation] in front, then per iteration [pose sums + Schur blocks] -> [solve + update + linearisation in
+// every workgroup], 1 + 2 max_iter launches. VO_DBG_SBA_SPLIT = 1 and every other window: three launches per iteration (four
+// with the general solve): [update of the previous iteration + per-landmark linearisation] -> [pose sums + Schur blocks] ->
+// [assembly ->] solve; one last update behind the loop.
+template <int N>
+static void sba_launch_solve_point(const SbaDev &d, int grid, hipStream_t s, int iter, bool last) {
+  if (last)
+    hipLaunchKernelGGL((sba_solve_point_kernel<N, true>), dim3(grid), dim3(SBA_SOLVE_WG), 0, s, d, iter);
+  else
+    hipLaunchKernelGGL((sba_solve_point_kernel<N, false>), dim3(grid), dim3(SBA_SOLVE_WG), 0, s, d, iter);
+}
+static bool sba_fused(const vo_ctx *c, const SbaDev &d, int max_iter) {
+  return sba_reg_solve(c, d.n_opt) && d.n_frames <= SBA_LDS_FRAMES && max_iter > 0 && c->dbg[VO_DBG_SBA_SPLIT] != 1;
+}
 int vo_sba_enqueue_iterations(vo_ctx *c, const SbaDev &d, int max_iter) {
   const int No = d.n_opt, n = 6 * No, n_err = d.n_err;
   hipStream_t s = c->stream;
+  const int n_schur_wg = No * SBA_PG + (No * (No + 1) / 2) * SBA_SG;
+  if (sba_fused(c, d, max_iter)) {
+    // Pose and error buffers alternate by iteration; the parity is chosen so that the last iteration writes the primary
+    // pose block (what the host, the write-back and res_src read). Iteration `it` reads T_in(it) and writes T_in(it + 1).
+    auto T_in = [&](int it) { return ((max_iter - it) & 1) ? d.T_alt : d.T; };
+    double *const err_buf[2] = {d.err_part, d.err_alt};
+    int grid = std::min(SBA_FUSED_MAX_WG, (n_err + SBA_FUSED_PW - 1) / SBA_FUSED_PW);
+    if (c->dbg[VO_DBG_SBA_SPLIT] >= 2) grid = std::min(grid, c->dbg[VO_DBG_SBA_SPLIT]);  // (test hook: every workgroup strides)
+    grid = std::max(grid, 1);
+    SbaDev e = d;
+    e.T_out = T_in(0) != d.T ? T_in(0) : nullptr;  // (the first launch reads the caller's poses and copies them across)
+    e.err_out = err_buf[1];
+    hipLaunchKernelGGL(sba_update_point_kernel<true>, dim3(n_err), dim3(64), 0, s, e, 0, 1);
+    for (int iter = 0; iter < max_iter; ++iter) {
+      e.T = T_in(iter);
+      e.T_out = T_in(iter + 1);
+      e.err_part = err_buf[iter & 1];
+      e.err_out = err_buf[(iter + 1) & 1];
+      hipLaunchKernelGGL(sba_pose_schur_kernel, dim3(n_schur_wg), dim3(SBA_WG), 0, s, e);
+      const bool last = iter == max_iter - 1;
+      switch (No) {
+        case 1: sba_launch_solve_point<6>(e, grid, s, iter, last); break;
+        case 2: sba_launch_solve_point<12>(e, grid, s, iter, last); break;
+        case 3: sba_launch_solve_point<18>(e, grid, s, iter, last); break;
+        case 4: sba_launch_solve_point<24>(e, grid, s, iter, last); break;
+        case 5: sba_launch_solve_point<30>(e, grid, s, iter, last); break;
+        case 6: sba_launch_solve_point<36>(e, grid, s, iter, last); break;
+        case 7: sba_launch_solve_point<42>(e, grid, s, iter, last); break;
+        default: sba_launch_solve_point<48>(e, grid, s, iter, last); break;
+      }
+    }
+    VO_CHECK_HIP(c, hipGetLastError());
+    return VO_OK;
+  }
   const size_t lds = sizeof(double) * ((size_t)n * n + 3 * (size_t)n) + sizeof(int) * 2 * (size_t)n + 64;
   if (lds > 64 * 1024)
     VO_CHECK_HIP(c, hipFuncSetAttribute((const void *)sba_solve_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -1243,7 +1455,7 @@ int vo_sba_enqueue_iterations(vo_ctx *c, const SbaDev &d, int max_iter) {
   for (int iter = 0; iter < max_iter; ++iter) {
     launch_update_point(iter > 0 ? 1 : 0, 1);
     if (No > 0) {
-      hipLaunchKernelGGL(sba_pose_schur_kernel, dim3(No * SBA_PG + (No * (No + 1) / 2) * SBA_SG), dim3(SBA_WG), 0, s, d);
+      hipLaunchKernelGGL(sba_pose_schur_kernel, dim3(n_schur_wg), dim3(SBA_WG), 0, s, d);
       if (!reg_solve) hipLaunchKernelGGL(sba_assemble_kernel, dim3((n * n + n + 63) / 64), dim3(64), 0, s, d);
     }
     if (reg_solve) {  // (assembles the reduced system itself)

@@ -10,6 +10,8 @@
 #define SBA_SG 8        // partial-sum workgroups per block of B C^-1 B^T
 #define SBA_MAX_OPT 20  // reduced system up to 120 x 120 in LDS
 #define SBA_LQ 8        // lanes per landmark in the point kernel (4 or 8)
+#define SBA_FUSED_PW 4      // wavefronts of a workgroup of sba_solve_point_kernel that take landmark groups (the upper four of eight)
+#define SBA_FUSED_MAX_WG 256  // its grid: at most one workgroup per compute unit
 
 struct SbaDev {
   int n_frames, n_opt, M, n_obs, n_slots, stereo, max_iter;
@@ -31,8 +33,13 @@ struct SbaDev {
   const int *pose_slot_ptr, *pose_slot_end, *pose_slot, *slot_lm;
   const int *pair_ptr, *pair_end, *pair_a, *pair_b;
   double *Cinvb, *b;
-  double *err_part;  // squared-error sum of each workgroup of the point kernel (n_err of them)
+  double *err_part;  // squared-error sum of each landmark group (64 / SBA_LQ landmarks) of the point kernel (n_err of them)
   int n_err;
+  // second copies of the poses (16 n_frames) and of err_part, placed by vo_sba_place_work, and what ONE launch writes: set per
+  // launch by vo_sba_enqueue_iterations on the fused path, where a launch reads T / err_part and writes T_out / err_out — no
+  // workgroup reads what another workgroup of the same launch writes (null on the three-launch path)
+  double *T_alt, *err_alt;
+  double *T_out, *err_out;
   double *Bs, *BCs, *BCb;  // per slot: B_ji, B_ji C_i^-1 (6x3 each), (B_ji C_i^-1) b_i (6)
   double *Apart;  // n_opt * SBA_PG * 48 (36 A, 6 a, 6 BCinv_b)
   double *S;      // n_opt * n_opt * SBA_SG * 36 (partial sums; blocks below the diagonal are never used)

@@ -807,7 +807,8 @@ static int lba_warm_up(vo_svo *s) {
       for (int k = 0; k < 4; ++k) head.T_jw[16 * j + 5 * k] = 1.0;
     }
     const double *res = nullptr;
-    const int rc = lba_enqueue(s, w, 1, 1, head, ref, s->ts[0], 0, 1, &res);
+    // (two iterations: the fused iteration has one kernel for the last iteration and one for the others)
+    const int rc = lba_enqueue(s, w, 1, 1, head, ref, s->ts[0], 0, 2, &res);
     if (rc < 0) return rc;
   }
   hipLaunchKernelGGL(lba_keyframe_kernel, dim3(1), dim3(256), 0, c->stream, s->ts[0], 0, L->tab, L->kf_ids[0], L->kf_pl[0], L->kf_pr[0],
