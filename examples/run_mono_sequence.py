@@ -40,7 +40,21 @@ def write_ppm(path, img):
         f.write(np.ascontiguousarray(img, np.uint8).tobytes())
 
 
-def main():
+def mask_options(args):
+    """--mask / --mask-rectified as keyword arguments of from_yaml: the ignore mask every frame carries (0 = ignore)"""
+    if args.mask and args.mask_rectified is not None:
+        raise SystemExit("--mask and --mask-rectified exclude each other")
+    if args.mask:
+        from visual_odometry_ros_amd.config import read_pgm
+        return {"mask": read_pgm(args.mask)}
+    if args.mask_rectified is not None:
+        if not 0 <= args.mask_rectified <= 31:
+            raise SystemExit("--mask-rectified: ERODE is 0..31")
+        return {"mask": "rectified", "mask_erode": args.mask_rectified}
+    return {}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", required=True, help="a config/mono/*.yaml file of the reference")
     ap.add_argument("--images", required=True, help="directory of the images")
@@ -52,14 +66,22 @@ def main():
     ap.add_argument("--strict-border", type=int, default=4, help="see vo_stereo_frame_set_strict_border (0: masked border taps)")
     ap.add_argument("--no-local-ba", action="store_true")
     ap.add_argument("--debug-images", default=None, metavar="DIR", help="write the debug image of every frame there (binary PPM)")
-    args = ap.parse_args()
+    ap.add_argument("--mask", default=None, metavar="FILE.pgm",
+                    help="ignore mask (binary PGM of the image's size, 0 = ignore): no keypoints and no surviving tracks there")
+    ap.add_argument("--mask-rectified", nargs="?", type=int, const=0, default=None, metavar="ERODE",
+                    help="with flagDoUndistortion: ignore what the rectification fills in, and ERODE (0..31, default 0) pixels around it")
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
     import visual_odometry_ros_amd as V
     names = sorted(os.listdir(args.images))
     n = len(names) if not args.max_frames else min(len(names), args.max_frames)
     if n == 0:
         raise SystemExit("no images found")
     mvo = V.MonoVO.from_yaml(args.config, device=args.device, strict_border=args.strict_border, local_ba=not args.no_local_ba,
-                             debug_image=bool(args.debug_images), pose_covariance=bool(args.covariance))
+                             debug_image=bool(args.debug_images), pose_covariance=bool(args.covariance), **mask_options(args))
     cov_file = open(args.covariance, "w") if args.covariance else None
     if args.debug_images:
         os.makedirs(args.debug_images, exist_ok=True)

@@ -30,7 +30,21 @@ def load_grey(path):
     return np.ascontiguousarray(np.asarray(im, dtype=np.uint8))
 
 
-def main():
+def mask_options(args):
+    """--mask / --mask-rectified as keyword arguments of from_yaml: the ignore mask every frame carries (0 = ignore)"""
+    if args.mask and args.mask_rectified is not None:
+        raise SystemExit("--mask and --mask-rectified exclude each other")
+    if args.mask:
+        from visual_odometry_ros_amd.config import read_pgm
+        return {"mask": read_pgm(args.mask)}
+    if args.mask_rectified is not None:
+        if not 0 <= args.mask_rectified <= 31:
+            raise SystemExit("--mask-rectified: ERODE is 0..31")
+        return {"mask": "rectified", "mask_erode": args.mask_rectified}
+    return {}
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", required=True, help="a config/stereo/*.yaml file of the reference")
     ap.add_argument("--left", required=True, help="directory of the left images")
@@ -44,7 +58,15 @@ def main():
     ap.add_argument("--no-local-ba", action="store_true")
     ap.add_argument("--sum-order", choices=("tree", "reference"), default="tree",
                     help="see vo_set_sum_order (reference: the reference's summation order, bit-exact against it; slower)")
-    args = ap.parse_args()
+    ap.add_argument("--mask", default=None, metavar="FILE.pgm",
+                    help="ignore mask (binary PGM of the image's size, 0 = ignore): no keypoints and no surviving tracks there")
+    ap.add_argument("--mask-rectified", nargs="?", type=int, const=0, default=None, metavar="ERODE",
+                    help="with flagDoUndistortion: ignore what the rectification fills in, and ERODE (0..31, default 0) pixels around it")
+    return ap.parse_args(argv)
+
+
+def main():
+    args = parse_args()
     import visual_odometry_ros_amd as V
     names_l, names_r = sorted(os.listdir(args.left)), sorted(os.listdir(args.right))
     n = min(len(names_l), len(names_r))
@@ -53,7 +75,7 @@ def main():
     if n == 0:
         raise SystemExit("no image pairs found")
     svo = V.StereoVO.from_yaml(args.config, device=args.device, strict_border=args.strict_border, local_ba=not args.no_local_ba,
-                               pose_covariance=bool(args.covariance))
+                               pose_covariance=bool(args.covariance), **mask_options(args))
     cov_file = open(args.covariance, "w") if args.covariance else None
     svo.ctx.sum_order = args.sum_order
     pair = lambda k: (load_grey(os.path.join(args.left, names_l[k])), load_grey(os.path.join(args.right, names_r[k])))  # noqa: E731

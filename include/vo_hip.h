@@ -650,6 +650,41 @@ int vo_svo_get_pose_covariance(vo_svo *svo, double P[36], double Sigma_xi[36], d
  * sets; cap entries of room, NULL: the count only) and the T01 the BA returned */
 int vo_svo_get_pose_covariance_inputs(vo_svo *svo, float *X, float *pts_l, float *pts_r, int cap, int *n, float T01[16]);
 
+/* ---- Ignore mask: where keypoint detection and the track gate do not look ----------
+ * A mask is a width x height plane of bytes (`stride` bytes per row, host or device memory) in the pixels of the LEFT / mono
+ * image as the tracker sees it — after rectification, if any. 0 = ignore, non-zero = usable. The lookup of a float pixel
+ * (x, y) is mask[(int)(y + 0.5f)][(int)(x + 0.5f)] (cv::KeyPointsFilter::runByPixelsMask's rounding); an index outside the
+ * plane reads as 0. Two places read it:
+ *   detection   a keypoint whose (level-scaled) position reads 0 does not vote for its bucket: the result is "detect, drop the
+ *               masked keypoints, then bucket". The detection itself is not masked: the count of detected keypoints
+ *               (n_detected) is that of the unmasked image, and vo_orb_detect's list never reads a mask.
+ *   track gate  the BA launch promotes a feature to stage 4 only where the lookup at its current left pixel is non-zero (the
+ *               general form of the reference's y > 660 gate, stereo_vo.cpp:653-668). A masked feature stays at stage 3: it
+ *               took part in this frame's BA, is not in the next track set, and its bucket is free for this frame's new points.
+ * Without a mask (the default; NULL) every kernel runs exactly what it ran before the option existed, and a mask of all 255
+ * gives the same bits as none.
+ *
+ * vo_set_slot_mask: the mask of the image in `slot` (which must hold one: the mask has its dimensions), copied into storage the
+ * context owns (allocated at the slot's first mask); NULL clears it. It stays with the slot (vo_swap_slots moves it along) until
+ * cleared or replaced, or until an image of another size is put into the slot (the mask is dropped then). Read by vo_new_point_candidates_enqueue, vo_extract_orb_with_binning[_enqueue] and the frame operators'
+ * gate (the mask of slot_l1 / slot1); NOT by vo_orb_detect. VO_ERR_INVALID while a frame is in flight. Returns when the caller's
+ * buffer is free again. */
+int vo_set_slot_mask(vo_ctx *ctx, int slot, const void *mask, int stride, int on_device);
+/* the size of the image in `slot` (0 x 0: the slot holds none) — what a mask for it must measure. Host state only: no device work. */
+int vo_slot_image_size(vo_ctx *ctx, int slot, int *width, int *height);
+/* The drivers: the mask that pairs / images ingested FROM NOW ON carry (frame.width x frame.height; VO_ERR_INVALID for a stride
+ * below the width); NULL: none. Legal between any two of track / enqueue / prefetch / result — a per-frame mask is set before its
+ * pair is handed over. A pair keeps the mask it was ingested with: its detection (side stream, possibly a frame ahead) and the
+ * gate of its own frame read the same plane, whatever is set afterwards. vo_svo_run / vo_mvo_run use the mask current at the
+ * call. The call copies into library-owned storage and returns when the caller's buffer is free again. Storage: one master
+ * plane and one plane per left / mono image slot, all allocated at the FIRST set (vo_debug_allocation_count does not move
+ * afterwards); at ingestion a slot's plane is refreshed — one device copy in front of the detector — only when the master
+ * changed since. Creating and destroying a driver clears the masks of the slots it uses: a driver never sees its predecessor's
+ * mask, and operator calls on those slots do not see a destroyed driver's. MonoVO's first two images and its 5-point-fallback frames are host-driven and have no stage-4 gate: there the
+ * mask acts on the detection only. */
+int vo_svo_set_mask(vo_svo *svo, const void *mask, int stride, int on_device);
+/* (MonoVO: vo_mvo_set_mask, below) */
+
 /* ---- undistortion / stereo rectification in front of the trackers ----------
  * core/visual_odometry/camera.cpp. A context holds the maps of two cameras
  * (cam 0 = left or the mono camera, cam 1 = right), device-resident. */
@@ -664,6 +699,11 @@ int vo_rectify_init_stereo(vo_ctx *ctx, int width, int height, const float Kl[4]
 /* caller-made maps (what cv::remap takes as map1 / map2, CV_32FC1, width x height, tightly packed) */
 int vo_rectify_set_maps(vo_ctx *ctx, int cam, const float *map_u, const float *map_v, int width, int height);
 int vo_rectify_get_maps(vo_ctx *ctx, int cam, float *map_u, float *map_v, int *width, int *height);
+/* Where camera `cam`'s rectified image shows the source, as an ignore mask (above): cv::remap fills the rest with 0, and FAST
+ * fires along the edge. valid(x, y) iff 0 <= map_u <= width - 1 and 0 <= map_v <= height - 1 (float compares; NaN is invalid);
+ * out(x, y) = 255 iff every pixel of the (2 erode + 1)^2 square around it, clipped to the image, is valid, else 0. erode: 0..31.
+ * out: width x height bytes, `stride` per row, host or device memory. */
+int vo_rectify_validity_mask(vo_ctx *ctx, int cam, int erode, void *out, int stride, int on_device);
 /* Camera::undistortImage / StereoCamera::rectifyStereoImages (camera.cpp:166-183, :300-336) +
  * convertTo(CV_8UC1) (stereo_vo.cpp:420-421, mono_vo.cpp:512), fused into the pyramid build of the slot:
  * vo_set_image* with the raw image and the camera whose map applies. The image must have the map's
@@ -919,6 +959,8 @@ int vo_mvo_get_pose_covariance(vo_mvo *mvo, double P[36], double Sigma_xi[36], d
                                int *n_unknown_steps);
 /* test hook: the last steady-state frame's BA set (X in the previous camera's frame, pixels) and the R01, t01 the BA returned */
 int vo_mvo_get_pose_covariance_inputs(vo_mvo *mvo, float *X, float *pts, int cap, int *n, float R01[9], float t01[3]);
+/* the ignore mask of the images ingested from now on: vo_svo_set_mask's rules ("Ignore mask" above) */
+int vo_mvo_set_mask(vo_mvo *mvo, const void *mask, int stride, int on_device);
 
 /* ---- 5-point RANSAC pose: MotionEstimator::calcPose5PointsAlgorithm ------------------------------------------------
  * motion_estimator.cpp:21-123 + findCorrectRT (:205-263): cv::findEssentialMat(pts0, pts1, K, RANSAC, confidence, thres_px)

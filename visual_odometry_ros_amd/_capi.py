@@ -145,6 +145,7 @@ SYMBOLS = [
     "vo_gn_pose_information_stereo", "vo_gn_pose_information_mono",
     "vo_svo_set_pose_covariance", "vo_svo_get_pose_covariance", "vo_svo_get_pose_covariance_inputs",
     "vo_mvo_set_pose_covariance", "vo_mvo_get_pose_covariance", "vo_mvo_get_pose_covariance_inputs",
+    "vo_set_slot_mask", "vo_slot_image_size", "vo_svo_set_mask", "vo_mvo_set_mask", "vo_rectify_validity_mask",
 ]
 
 _lib = None
@@ -231,6 +232,11 @@ def load():
     lib.vo_mvo_set_pose_covariance.argtypes = [vp, ci, cd]
     lib.vo_mvo_get_pose_covariance.argtypes = [vp, vp, vp, vp, vp, vp, vp]
     lib.vo_mvo_get_pose_covariance_inputs.argtypes = [vp, vp, vp, ci, vp, vp, vp]
+    lib.vo_set_slot_mask.argtypes = [vp, ci, vp, ci, ci]
+    lib.vo_slot_image_size.argtypes = [vp, ci, vp, vp]
+    lib.vo_svo_set_mask.argtypes = [vp, vp, ci, ci]
+    lib.vo_mvo_set_mask.argtypes = [vp, vp, ci, ci]
+    lib.vo_rectify_validity_mask.argtypes = [vp, ci, ci, vp, ci, ci]
     lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_five_point_destroy.argtypes = [vp]
     lib.vo_five_point_destroy.restype = None

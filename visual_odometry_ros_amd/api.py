@@ -36,6 +36,37 @@ def _p(a, t=C.c_float):
     return a.ctypes.data_as(C.POINTER(t))
 
 
+def mask_lookup(mask, x, y):
+    """The ignore mask's lookup as the device does it (include/vo_hip.h, "Ignore mask"): mask[(int)(y + 0.5f)][(int)(x + 0.5f)]
+    in float32, an index outside the plane (or a NaN coordinate) reads as 0. `x`, `y`: scalars or arrays. Returns bool:
+    True = usable."""
+    mask = np.asarray(mask)
+    fx = np.asarray(x, np.float32) + np.float32(0.5)
+    fy = np.asarray(y, np.float32) + np.float32(0.5)
+    h, w = mask.shape
+    with np.errstate(invalid="ignore"):
+        ok = (fx > -1.0) & (fx < np.float32(w)) & (fy > -1.0) & (fy < np.float32(h))
+    xi = np.where(ok, fx, 0).astype(np.int64)  # (astype truncates toward zero, as the C cast)
+    yi = np.where(ok, fy, 0).astype(np.int64)
+    return ok & (mask[yi, xi] != 0)
+
+
+def _mask_arg(mask, width, height):
+    """A mask as the C calls take it: a (height, width) u8 array, or a (device address, stride) pair; None clears.
+    Returns (keep-alive, address, stride, on_device)."""
+    if mask is None:
+        return None, None, 0, 0
+    if isinstance(mask, np.ndarray):
+        if mask.dtype == bool:
+            mask = mask.astype(np.uint8) * np.uint8(255)
+        if mask.ndim != 2 or mask.shape != (height, width) or mask.dtype != np.uint8:
+            raise VoError(-1, f"a mask is a {width} x {height} plane of uint8, got {mask.dtype} {mask.shape}")
+        if mask.strides[1] != 1:
+            mask = np.ascontiguousarray(mask)
+        return mask, mask.ctypes.data, mask.strides[0], 0
+    return mask, int(mask[0]), int(mask[1]), 1
+
+
 class Context:
     """Owns one vo_ctx: a HIP stream, image-pyramid slots and point buffers."""
 
@@ -140,6 +171,23 @@ class Context:
         assert img.ndim == 2
         self.check(self.lib.vo_set_image(self._h, slot, _p(img, C.c_uint8), img.shape[1], img.shape[0],
                                          img.strides[0]))
+
+    def slot_image_size(self, slot):
+        """(width, height) of the image in `slot`, (0, 0) if it holds none (vo_slot_image_size: host state, no device work)"""
+        w, h = C.c_int(), C.c_int()
+        self.check(self.lib.vo_slot_image_size(self._h, slot, C.byref(w), C.byref(h)))
+        return w.value, h.value
+
+    def set_slot_mask(self, slot, mask):
+        """The ignore mask of the image in `slot` (vo_set_slot_mask): a u8 (or bool) array of the image's shape, 0 = ignore; a
+        (device address, stride) pair (a plane of the image's size; the stride is checked against its width); None clears it.
+        Read by the per-bin candidate table, extractORBwithBinning_fast and the frame operators' stage-4 gate for that image;
+        never by detect(). The slot must hold its image already; an image of another size put into the slot drops the mask."""
+        w, h = self.slot_image_size(slot) if mask is not None else (0, 0)
+        if mask is not None and w == 0:
+            raise VoError(-1, f"slot {slot} holds no image: a mask has the dimensions of the slot's image")
+        _, ptr, stride, dev = _mask_arg(mask, w, h)
+        self.check(self.lib.vo_set_slot_mask(self._h, slot, ptr, stride, dev))
 
     def set_image_device(self, slot, dev_ptr, width, height, stride):
         self.check(self.lib.vo_set_image_device(self._h, slot, C.c_void_p(dev_ptr), width, height, stride))
@@ -990,8 +1038,9 @@ class StereoVO:
     def __init__(self, ctx, width, height, Kl, Kr, T_lr, n_bins_u, n_bins_v, thres_fastscore=15, window_size=21, max_level=6,
                  thres_error=80.0, thres_bidirection=0.5, thres_poseba_error=3.0, thres_alive_ratio=0.6, thres_rotation=15.0,
                  thres_trans=10.0, n_max_keyframes_in_window=9, strict_border=4, local_ba=True, rectify=False, thres_sampson=60.0,
-                 debug_image=False, pose_covariance=False, sigma_px=0.0):
+                 debug_image=False, pose_covariance=False, sigma_px=0.0, mask=None):
         """debug_image=True: every tracked frame draws the reference's img_debug_ on the device (getDebugImage).
+        mask: the ignore mask every pair carries from the first one on (setMask).
         pose_covariance=True: every frame chains the covariance of its pose on the device (getPoseCovariance); sigma_px > 0
         scales by that pixel noise instead of the a-posteriori variance.
         rectify=True is system_flags_.flagDoUndistortion: the context's stereo rectification maps (StereoCamera.
@@ -1015,11 +1064,13 @@ class StereoVO:
             ctx.check(self.lib.vo_svo_set_debug_image(self._h, 1))
         if pose_covariance:
             ctx.check(self.lib.vo_svo_set_pose_covariance(self._h, 1, float(sigma_px)))
+        if mask is not None:
+            self.setMask(mask)
         self._info = SvoFrameInfo()
         self.stats_frame = []  # AlgorithmStatistics::FrameStatistics::Twc per frame (stereo_vo.cpp:979-980)
 
     @classmethod
-    def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", **overrides):
+    def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", mask=None, mask_erode=0, **overrides):
         """StereoVO(mode = "rosbag", directory_intrinsic = path) of the reference (stereo_vo.cpp:15-57, :118-280): the
         object configured by one of its config/stereo/*.yaml files. The context is created here (sized by the file) and
         closed with the object. With flagDoUndistortion the pairs go through the rectification maps and the loop runs on
@@ -1027,9 +1078,13 @@ class StereoVO:
         arguments of the constructor that the file does not know (strict_border, local_ba). `max_points`: capacity of a
         track set (default 2 * bins + 1024; the reference has no such bound — several survivors may share a bin while
         every empty bin adds a landmark — so a caller that sees VO_ERR_CAPACITY raises it). `input_format`: the pairs'
-        pixel format (Context.set_input_format); anything but "mono8" needs flagDoUndistortion in the file."""
+        pixel format (Context.set_input_format); anything but "mono8" needs flagDoUndistortion in the file.
+        `mask`: an ignore mask (setMask), or "rectified": the left camera's validity mask (StereoCamera.validityMask(mask_erode):
+        what cv::remap fills with 0 is not looked at), which needs flagDoUndistortion in the file."""
         from . import config as _config
         cfg = _config.load_stereo_config(path)
+        if isinstance(mask, str) and (mask != "rectified" or not cfg["flagDoUndistortion"]):
+            raise ValueError('mask="rectified" is the only named mask, and it needs flagDoUndistortion in the file')
         cl, cr = cfg["camera"]["left"], cfg["camera"]["right"]
         W, H = cl["width"], cl["height"]
         fe, ft, me, ku = cfg["feature_extractor"], cfg["feature_tracker"], cfg["motion_estimator"], cfg["keyframe_update"]
@@ -1047,12 +1102,14 @@ class StereoVO:
                 cam.initStereoCameraToRectify()
                 Kl = Kr = cam.getRectifiedCamera()
                 T_lr, rectify = cam.getRectifiedStereoPoseLeft2Right(), True
+                if isinstance(mask, str):
+                    mask = cam.validityMask(mask_erode)
             obj = cls(ctx, W, H, Kl, Kr, T_lr, fe["n_bins_u"], fe["n_bins_v"], thres_fastscore=fe["thres_fastscore"],
                       window_size=ft["window_size"], max_level=ft["max_level"], thres_error=ft["thres_error"],
                       thres_sampson=ft["thres_sampson"],
                       thres_bidirection=ft["thres_bidirection"], thres_poseba_error=me["thres_poseba_error"],
                       thres_alive_ratio=ku["thres_alive_ratio"], thres_rotation=ku["thres_rotation"], thres_trans=ku["thres_trans"],
-                      n_max_keyframes_in_window=ku["n_max_keyframes_in_window"], rectify=rectify, **overrides)
+                      n_max_keyframes_in_window=ku["n_max_keyframes_in_window"], rectify=rectify, mask=mask, **overrides)
         except Exception:
             ctx.close()
             raise
@@ -1073,6 +1130,17 @@ class StereoVO:
             self.close()
         except Exception:
             pass
+
+    def setMask(self, mask):
+        """The ignore mask (include/vo_hip.h, "Ignore mask") of every pair handed over FROM NOW ON: a (height, width) u8 / bool
+        array, 0 = ignore, or a (device address, stride) pair — a segmentation network's output stays on the device; None: no
+        mask. Legal between any two of trackStereoImages / enqueue / prefetch / result; a pair already handed over (a
+        prefetched one included) keeps the mask it came with. The library copies: the array is free on return."""
+        _, ptr, stride, dev = _mask_arg(mask, self.width, self.height)
+        self.ctx.check(self._set_mask_fn()(self._h, ptr, stride, dev))
+
+    def _set_mask_fn(self):
+        return self.lib.vo_svo_set_mask
 
     def _img(self, a):
         """a host image as the library reads it: a u8 plane, or — with rectify=True — an array of the context's input format"""
@@ -1425,11 +1493,24 @@ class Camera:
     def maps(self):
         return _get_maps(self.ctx, self.cam)
 
+    def validityMask(self, erode=0):
+        """Where the undistorted image shows the source (vo_rectify_validity_mask): 255 where every pixel within `erode`
+        (0..31) samples inside the raw image, else 0 — an ignore mask for MonoVO.setMask."""
+        return _validity_mask(self.ctx, self.cam, erode)
+
     def undistortImage(self, raw, slot):
         raw = self.ctx._format_image(raw)  # (an array of the context's input format: Context.set_input_format)
         if raw.size == 0 or raw.shape[:2] != (self.n_rows, self.n_cols):  # camera.cpp:168-169
             raise VoError(-4, "undistort image: provided image has not the same size as the camera model!")
         self.ctx.set_image_rectified(slot, raw, self.cam)
+
+
+def _validity_mask(ctx, cam, erode):
+    w, h = C.c_int(), C.c_int()
+    ctx.check(ctx.lib.vo_rectify_get_maps(ctx.handle, cam, None, None, C.byref(w), C.byref(h)))
+    out = np.zeros((h.value, w.value), np.uint8)
+    ctx.check(ctx.lib.vo_rectify_validity_mask(ctx.handle, cam, int(erode), out.ctypes.data, out.strides[0], 0))
+    return out
 
 
 def _get_maps(ctx, cam):
@@ -1485,6 +1566,12 @@ class StereoCamera:
 
     def maps(self):
         return _get_maps(self.ctx, 0), _get_maps(self.ctx, 1)
+
+    def validityMask(self, erode=0, cam=0):
+        """Where the rectified LEFT image (cam=1: the right one) shows the source (vo_rectify_validity_mask): 255 where every
+        pixel within `erode` (0..31) samples inside the raw image, else 0 — an ignore mask for StereoVO.setMask."""
+        self._need_init("validityMask()")
+        return _validity_mask(self.ctx, cam, erode)
 
     def rectifyStereoImages(self, img_left, img_right, slot_l, slot_r):
         self._need_init("rectifyStereoImages()")
@@ -1642,10 +1729,12 @@ class MonoVO:
     def __init__(self, ctx, width, height, K, n_bins_u, n_bins_v, five_point=None, thres_fastscore=15, window_size=15, max_level=5,
                  thres_error=20.0, thres_bidirection=1.0, thres_poseba_error=5, thres_sampson=1.0, thres_parallax=1.0,
                  thres_overlap_ratio=0.7, thres_rotation=3.0, thres_translation=3.0, n_max_keyframes_in_window=9, strict_border=4,
-                 local_ba=True, rectify=False, thres_5p_error=2.0, debug_image=False, pose_covariance=False, sigma_px=0.0):
+                 local_ba=True, rectify=False, thres_5p_error=2.0, debug_image=False, pose_covariance=False, sigma_px=0.0,
+                 mask=None):
         """debug_image=True: every frame draws the reference's img_debug_ on the device (getDebugImage, getDebugPoints).
         pose_covariance=True: every frame chains the covariance of its pose on the device, in map units (getPoseCovariance);
-        sigma_px > 0 scales by that pixel noise instead of the a-posteriori variance."""
+        sigma_px > 0 scales by that pixel noise instead of the a-posteriori variance.
+        mask: the ignore mask every image carries from the first one on (setMask)."""
         self.ctx, self.lib = ctx, ctx.lib
         self._own_fp = None
         if five_point is None:
@@ -1696,20 +1785,25 @@ class MonoVO:
             ctx.check(self.lib.vo_mvo_set_debug_image(self._h, 1))
         if pose_covariance:
             ctx.check(self.lib.vo_mvo_set_pose_covariance(self._h, 1, float(sigma_px)))
+        if mask is not None:
+            self.setMask(mask)
         self._info = MvoFrameInfo()
         self.stats_frame = []
 
     @classmethod
-    def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", **overrides):
+    def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", mask=None, mask_erode=0, **overrides):
         """MonoVO(mode = "rosbag", directory_intrinsic = path) of the reference (mono_vo.cpp:15-60, :137-225): the object
         configured by one of its config/mono/*.yaml files, with the library's 5-point solver at motion_estimator.
         thres_5p_error. The context is created here (sized by the file) and closed with the object. With flagDoUndistortion
         the images go through the camera's undistortion map (mono_vo.cpp:509-513). `overrides`: keyword arguments of the
         constructor (five_point, strict_border, local_ba, debug_image, ...). `max_points`: capacity of a track set (default
         2 * bins + 1024, as StereoVO.from_yaml). `input_format`: the images' pixel format (Context.set_input_format); anything but
-        "mono8" needs flagDoUndistortion in the file."""
+        "mono8" needs flagDoUndistortion in the file. `mask`: an ignore mask (setMask), or "rectified": the camera's validity
+        mask (Camera.validityMask(mask_erode)), which needs flagDoUndistortion in the file."""
         from . import config as _config
         cfg = _config.load_mono_config(path)
+        if isinstance(mask, str) and (mask != "rectified" or not cfg["flagDoUndistortion"]):
+            raise ValueError('mask="rectified" is the only named mask, and it needs flagDoUndistortion in the file')
         cam = cfg["camera"]
         W, H = cam["width"], cam["height"]
         fe, ft, me, ku = cfg["feature_extractor"], cfg["feature_tracker"], cfg["motion_estimator"], cfg["keyframe_update"]
@@ -1719,7 +1813,10 @@ class MonoVO:
             if input_format != "mono8":
                 ctx.set_input_format(input_format)
             if cfg["flagDoUndistortion"]:
-                Camera(ctx, 0).initParams(W, H, cam["K"], cam["D"])
+                camera = Camera(ctx, 0)
+                camera.initParams(W, H, cam["K"], cam["D"])
+                if isinstance(mask, str):
+                    mask = camera.validityMask(mask_erode)
             # (keys the file does not have keep the constructor's defaults: a 0 there is refused or meaningless — mono0.yaml
             # has no motion_estimator.* and no keyframe window)
             names = {"feature_extractor.thres_fastscore": ("thres_fastscore", fe["thres_fastscore"]),
@@ -1737,6 +1834,7 @@ class MonoVO:
                      "keyframe_update.n_max_keyframes_in_window": ("n_max_keyframes_in_window", ku["n_max_keyframes_in_window"])}
             kw = {arg: v for key, (arg, v) in names.items() if key not in cfg["missing"]}
             kw["rectify"] = bool(cfg["flagDoUndistortion"])
+            kw["mask"] = mask
             kw.update(overrides)
             obj = cls(ctx, W, H, cam["K"], fe["n_bins_u"], fe["n_bins_v"], **kw)
         except Exception:
@@ -1765,6 +1863,11 @@ class MonoVO:
             pass
 
     _img, _nd = StereoVO._img, StereoVO._nd
+    setMask = StereoVO.setMask  # (the mono image's mask; MonoVO's first two images and 5-point-fallback frames have no stage-4 gate:
+                                # there it acts on the detection only)
+
+    def _set_mask_fn(self):
+        return self.lib.vo_mvo_set_mask
 
     def _ptr(self, img):
         if isinstance(img, np.ndarray):

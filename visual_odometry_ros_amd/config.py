@@ -110,3 +110,35 @@ def load_mono_config(path_or_text):
                              n_max_keyframes_in_window=_num(d, "keyframe_update.n_max_keyframes_in_window", int)),
         map_update=dict(thres_parallax=_num(d, "map_update.thres_parallax")),
     )
+
+
+def read_pgm(path):
+    """A binary PGM (P5, maxval <= 255; comments allowed in the header) as a (height, width) uint8 array — the file form of an
+    ignore mask (StereoVO.setMask): 0 = ignore."""
+    import numpy as np
+    with open(path, "rb") as f:
+        data = f.read()
+    tok, pos = [], 0
+    while len(tok) < 4:
+        while pos < len(data) and data[pos:pos + 1].isspace():
+            pos += 1
+        if data[pos:pos + 1] == b"#":
+            while pos < len(data) and data[pos:pos + 1] != b"\n":
+                pos += 1
+            continue
+        end = pos
+        while end < len(data) and not data[end:end + 1].isspace():
+            end += 1
+        if end == pos:
+            raise ValueError(f"{path}: truncated PGM header")
+        tok.append(data[pos:end])
+        pos = end
+    if tok[0] != b"P5":
+        raise ValueError(f"{path}: not a binary PGM (P5)")
+    w, h, maxval = int(tok[1]), int(tok[2]), int(tok[3])
+    if not 0 < maxval <= 255:
+        raise ValueError(f"{path}: maxval {maxval} (8-bit masks only)")
+    pos += 1  # the single whitespace byte behind maxval
+    if len(data) - pos < w * h:
+        raise ValueError(f"{path}: {len(data) - pos} bytes of pixels, {w} x {h} expected")
+    return np.frombuffer(data, np.uint8, w * h, pos).reshape(h, w).copy()

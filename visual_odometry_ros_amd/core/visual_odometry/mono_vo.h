@@ -228,6 +228,14 @@ class MonoVO {
   // device behind every frame's BA launch (vo_mvo_set_pose_covariance), in map units (up to the stream's scale) off by default. sigma_px > 0 scales by that pixel
   // noise instead of the a-posteriori variance.
   void setPoseCovariance(bool on, double sigma_px = 0.0) { ctx_->check(vo_mvo_set_pose_covariance(mvo_, on ? 1 : 0, sigma_px)); }
+  // NOT in the reference: the ignore mask of the images handed over FROM NOW ON (vo_mvo_set_mask; include/vo_hip.h, "Ignore
+  // mask") — width x height bytes in the image as the tracker sees it, 0 = ignore; nullptr: none. The first two images and the
+  // 5-point-fallback frames have no stage-4 gate: there the mask acts on the detection only. The library copies.
+  void setMask(const std::uint8_t *mask, int stride, bool on_device = false) {
+    ctx_->check(vo_mvo_set_mask(mvo_, mask, stride, on_device ? 1 : 0));
+  }
+  int width() const { return prm_.width; }
+  int height() const { return prm_.height; }
   // of the last tracked frame: waits for that frame's covariance launch only
   PoseCovariance getPoseCovariance() {
     PoseCovariance c;

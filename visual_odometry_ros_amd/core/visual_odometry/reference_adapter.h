@@ -166,6 +166,17 @@ class LazyContext {
   int device_ = 0, w_ = 0, h_ = 0, n_ = 0, lvl_ = 0, slots_ = 0;
 };
 
+// setMask(const cv::Mat &) of the two drivers: a CV_8UC1 plane of the camera's size (0 = ignore), an empty Mat clears
+template <class Impl>
+inline void set_mask(Impl &impl, const cv::Mat &m) {
+  if (m.empty()) {
+    impl.setMask(nullptr, 0);
+    return;
+  }
+  if (m.type() != CV_8UC1 || m.cols != impl.width() || m.rows != impl.height())
+    throw std::runtime_error("libvo_hip adapter: a mask is a CV_8UC1 image of the camera's size");
+  impl.setMask(m.data, (int)m.step);
+}
 }  // namespace vo_adapter
 
 // ===== FeatureTracker (core/visual_odometry/feature_tracker.h) =========================================
@@ -450,6 +461,9 @@ class StereoVO {
   void setPoseCovariance(bool on, double sigma_px = 0.0) { impl_.setPoseCovariance(on, sigma_px); }
   vo::PoseCovariance getPoseCovariance() { return impl_.getPoseCovariance(); }
   std::array<double, 36> getPoseCovarianceRos() { return impl_.getPoseCovarianceRos(); }
+  // NOT in the reference: the ignore mask of the pairs tracked from now on (vo::StereoVO::setMask) — CV_8UC1, the left image's
+  // size as the tracker sees it, 0 = ignore; an empty Mat: none
+  void setMask(const cv::Mat &mask) { vo_adapter::set_mask(impl_, mask); }
   vo::StereoVO &device() { return impl_; }
 
  private:
@@ -547,6 +561,9 @@ class MonoVO {
   void setPoseCovariance(bool on, double sigma_px = 0.0) { impl_.setPoseCovariance(on, sigma_px); }
   vo::PoseCovariance getPoseCovariance() { return impl_.getPoseCovariance(); }
   std::array<double, 36> getPoseCovarianceRos() { return impl_.getPoseCovarianceRos(); }
+  // NOT in the reference: the ignore mask of the images tracked from now on (vo::MonoVO::setMask) — CV_8UC1, the image's size, 0 =
+  // ignore; an empty Mat: none
+  void setMask(const cv::Mat &mask) { vo_adapter::set_mask(impl_, mask); }
   vo::MonoVO &device() { return impl_; }
 
  private:

@@ -225,6 +225,14 @@ class StereoVO {
   // device behind every frame's BA launch (vo_svo_set_pose_covariance), off by default. sigma_px > 0 scales by that pixel
   // noise instead of the a-posteriori variance.
   void setPoseCovariance(bool on, double sigma_px = 0.0) { ctx_->check(vo_svo_set_pose_covariance(svo_, on ? 1 : 0, sigma_px)); }
+  // NOT in the reference (whose only such device is the y > 660 row gate): the ignore mask of the pairs handed over FROM NOW ON
+  // (vo_svo_set_mask; include/vo_hip.h, "Ignore mask") — width x height bytes in the left image as the tracker sees it, 0 =
+  // ignore; nullptr: none. on_device: the plane is device memory (a segmentation network's output). The library copies.
+  void setMask(const std::uint8_t *mask, int stride, bool on_device = false) {
+    ctx_->check(vo_svo_set_mask(svo_, mask, stride, on_device ? 1 : 0));
+  }
+  int width() const { return prm_.width; }
+  int height() const { return prm_.height; }
   // of the last tracked frame: waits for that frame's covariance launch only
   PoseCovariance getPoseCovariance() {
     PoseCovariance c;

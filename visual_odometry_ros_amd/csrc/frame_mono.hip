@@ -607,6 +607,7 @@ static int mono_enqueue_impl(vo_ctx *c, const vo_mono_params *prm, int slot0, in
     memcpy(g.dT_prior, dT01_prior, sizeof(g.dT_prior));
     memcpy(g.K, prm->K, sizeof(g.K));
     g.thres_sampson = prm->thres_sampson;
+    if (vo_slot_mask_acquire(c, slot1, &g.ign) < 0) return VO_ERR_HIP;  // (the current image's ignore mask, if it has one)
     g.motion = f->st2;
     g.stage = f->stage;
     g.pts1 = f->F_pl1;

@@ -580,6 +580,7 @@ static int vo_frame_enqueue_body(vo_ctx *c, const vo_stereo_params *prm, int slo
     gf.C_orig = f->C_orig;
     gf.cnt = cnt;
     gf.hdr_flags = &f->hdr->flags;
+    if (vo_slot_mask_acquire(c, slot_l1, &gf.ign) < 0) return VO_ERR_HIP;  // (the current left image's ignore mask, if it has one)
   }
   if (fused) {
     gf.ctl = f->ctl;

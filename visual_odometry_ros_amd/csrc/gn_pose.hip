@@ -77,6 +77,7 @@ struct GnArgs {
   const uint8_t *f_m1, *f_m2, *f_m3;  // mono frame: selection masks in place of f_stage
   int f_mono;               // epilogue = mono_gate_body(f_gate)
   MonoGateArgs f_gate;
+  vo_mask_view f_ign;       // stereo frame: ignore mask of the current left image (vo_gn_frame::ign); p == null: none
 };
 static_assert(sizeof(GnArgs) <= 3072, "kernel arguments of the BA launch: keep well below the 4 KB segment");
 
@@ -800,14 +801,16 @@ __global__ __launch_bounds__(GN_T) void gn_pose_kernel(GnArgs a) {
   if (a.stage) {
     for (int i = tid; i < n; i += GN_T) {
       const float gate = a.p1[2 * i + 1] > 660 ? 100.f : 0.f;
-      if (a.mask[i] && gate < a.gate_thres) a.stage[a.orig[i]] = (uint8_t)a.stage_val;
+      if (a.mask[i] && gate < a.gate_thres && (!a.f_ign.p || vo_mask_usable(a.f_ign, a.p1[2 * i], a.p1[2 * i + 1])))
+        a.stage[a.orig[i]] = (uint8_t)a.stage_val;
     }
     // survivors of [5] outside the BA set keep mask_motion = true (stereo_vo.cpp:582) and meet the same gate
     if (a.f_n > 0 && a.f_lmflags && !a.f_mono)
       for (int i = tid; i < a.f_n; i += GN_T)
         if (a.f_stage[i] == 3 && !(a.f_lmflags[i] & VO_LM_TRIANGULATED)) {
           const float gate = a.f_pl1[2 * i + 1] > 660 ? 100.f : 0.f;
-          if (gate < a.gate_thres) a.stage[i] = (uint8_t)a.stage_val;
+          if (gate < a.gate_thres && (!a.f_ign.p || vo_mask_usable(a.f_ign, a.f_pl1[2 * i], a.f_pl1[2 * i + 1])))
+            a.stage[i] = (uint8_t)a.stage_val;
         }
   }
   if (tid == 0) {
@@ -1155,6 +1158,7 @@ int vo_gn_enqueue(vo_ctx *c, bool stereo, bool mono_general_inverse, const float
       a.f_mono = 1;
       a.f_gate = *frame->mono_gate;
     }
+    a.f_ign = frame->ign;
   }
   a.X = dX;
   a.p1 = dP1;

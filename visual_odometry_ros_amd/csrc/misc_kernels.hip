@@ -462,6 +462,7 @@ struct BinArgs {
   int32_t *idx_out;
   int *n_out;
   const int *d_n;         // arg-max: keypoint count on the device (overrides n when set)
+  vo_mask_view mask;      // arg-max: the image's ignore mask (p == null: none); a keypoint on an ignored pixel does not vote
 };
 __global__ __launch_bounds__(256) void weight_bin_update_kernel(BinArgs a) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -480,6 +481,7 @@ __global__ __launch_bounds__(256) void bucket_key_kernel(BinArgs a) {
   const unsigned v = (unsigned)(int)floorf(a.xy[2 * i + 1] * a.inv_v);
   if (u >= (unsigned)a.n_bins_u || v >= (unsigned)a.n_bins_v) return;
   const int bin = (int)(v * (unsigned)a.n_bins_u + u);
+  if (a.mask.p && !vo_mask_usable(a.mask, a.xy[2 * i], a.xy[2 * i + 1])) return;
   if (a.weight && a.weight[bin] == 0) return;  // (no weights: the best keypoint of EVERY bin, gated by the consumer)
   float r = a.response[i];
   if (!(-1.0f < r)) return;  // never beats the initial max_score of -1 (NaN included)
@@ -541,7 +543,7 @@ __global__ __launch_bounds__(256) void bucket_table_kernel(BinArgs a, uint8_t *h
 }
 int vo_bucket_table_enqueue(vo_ctx *c, const float *d_xy, const float *d_response, int n_max, float inv_u, float inv_v,
                             int n_bins_u, int n_bins_v, unsigned long long *d_key, float *d_tab_xy, uint8_t *d_tab_has,
-                            const int *d_n) {
+                            const int *d_n, const vo_mask_view *mask) {
   const int total = n_bins_u * n_bins_v;
   VO_CHECK_HIP(c, hipMemsetAsync(d_key, 0, sizeof(unsigned long long) * (size_t)total, c->stream));
   BinArgs a;
@@ -557,6 +559,7 @@ int vo_bucket_table_enqueue(vo_ctx *c, const float *d_xy, const float *d_respons
   a.key = d_key;
   a.pts_out = d_tab_xy;
   a.d_n = d_n;
+  if (mask) a.mask = *mask;
   vo_prof_begin(c, VO_K_AUX);
   if (n_max > 0) hipLaunchKernelGGL(bucket_key_kernel, dim3((n_max + 255) / 256), dim3(256), 0, c->stream, a);
   hipLaunchKernelGGL(bucket_table_kernel, dim3((total + 255) / 256), dim3(256), 0, c->stream, a, d_tab_has);
@@ -588,7 +591,7 @@ int vo_weight_bin_update_enqueue(vo_ctx *c, const float *d_pts, int n, int u_ste
 }
 int vo_bucket_argmax_enqueue(vo_ctx *c, const float *d_xy, const float *d_response, int n, float inv_u, float inv_v,
                              int n_bins_u, int n_bins_v, const int32_t *d_weight, unsigned long long *d_key,
-                             float *d_pts_out, int32_t *d_idx_out, int *d_n_out, const int *d_n) {
+                             float *d_pts_out, int32_t *d_idx_out, int *d_n_out, const int *d_n, const vo_mask_view *mask) {
   const int total = n_bins_u * n_bins_v;
   VO_CHECK_HIP(c, hipMemsetAsync(d_key, 0, sizeof(unsigned long long) * (size_t)total, c->stream));
   BinArgs a;
@@ -606,6 +609,7 @@ int vo_bucket_argmax_enqueue(vo_ctx *c, const float *d_xy, const float *d_respon
   a.idx_out = d_idx_out;
   a.n_out = d_n_out;
   a.d_n = d_n;
+  if (mask) a.mask = *mask;
   vo_prof_begin(c, VO_K_AUX);
   if (n > 0) hipLaunchKernelGGL(bucket_key_kernel, dim3((n + 255) / 256), dim3(256), 0, c->stream, a);
   hipLaunchKernelGGL(bucket_emit_kernel, dim3(1), dim3(1024), 0, c->stream, a);

@@ -383,6 +383,8 @@ extern "C" void vo_mvo_destroy(vo_mvo *s) {
     if (p) (void)hipFree(p);
   if (s->h_hdr) (void)hipHostFree(s->h_hdr);
   vo_pose_cov_state_free(&s->core.cov);
+  if (s->c) vo_driver_mask_release_slots(s->c, s->slot, 3);
+  vo_driver_mask_free(&s->core.mask);
   vo_svo_lba_free(&s->core);
   delete s;
 }
@@ -402,6 +404,7 @@ extern "C" int vo_mvo_create(vo_ctx *c, const vo_mvo_params *prm, vo_mvo **out) 
   s->c = c;
   s->prm = *prm;
   s->cap = c->cfg.max_points;
+  vo_driver_mask_release_slots(c, s->slot, 3);  // (whatever an earlier user of these slots left switched on)
   memset(&s->info, 0, sizeof(s->info));
   int rc = VO_OK;
   for (int k = 0; k < 2 && rc == VO_OK; ++k) rc = mvo_alloc_set(c, &s->ts[k], s->cap);
@@ -477,9 +480,22 @@ static int mvo_ingest(vo_mvo *s, const void *img, int stride, int on_device, boo
   return VO_OK;
 }
 
+// The image about to be ingested carries the mask that is current NOW (as StereoVO's svo_bind_mask). The steady-state gate
+// (mono_gate.hpp) reads it; the initialisation and the 5-point fallback are host-driven and have no such gate: there the mask
+// acts on the detection only.
+static int mvo_bind_mask(vo_mvo *s) {
+  return vo_driver_mask_bind(s->c, &s->core.mask, s->slot[2], s->prm.frame.width, s->prm.frame.height);
+}
+
+extern "C" int vo_mvo_set_mask(vo_mvo *s, const void *mask, int stride, int on_device) {
+  if (!s) return VO_ERR_INVALID;
+  return vo_driver_mask_set(s->c, &s->core.mask, s->slot, 3, mask, stride, on_device, s->prm.frame.width, s->prm.frame.height);
+}
+
 extern "C" int vo_mvo_prefetch(vo_mvo *s, const void *img, int stride, int on_device) {
   if (!s || !img) return VO_ERR_INVALID;
   VO_CHECK_HIP(s->c, hipSetDevice(s->c->device));
+  RC(mvo_bind_mask(s));
   RC(mvo_ingest(s, img, stride, on_device));
   s->pre = img;
   s->prefetched = true;
@@ -1052,13 +1068,14 @@ extern "C" int vo_mvo_enqueue(vo_mvo *s, const void *img, int stride, int on_dev
   // image it starts at once, before the pyramid is queued — and the candidates follow as a launch of their own (frame_mono.hip)
   int deferred = 0;
   if (!(s->prefetched && s->pre == img)) {
+    RC(mvo_bind_mask(s));
     const bool defer = s->init_done && s->n > 0 && c->ingest_side;
     if (defer) {
       deferred = 1;
       if (!s->prm.rectify && vo_orb_cand_table(c, s->tab_next)) {
         if (on_device) {
           const int rc = vo_new_point_candidates_enqueue_image(c, (const uint8_t *)img, stride, s->prm.frame.width, s->prm.frame.height,
-                                                               &s->prm.bins, s->tab_next);
+                                                               &s->prm.bins, s->tab_next, s->slot[2]);
           if (rc < 0) return rc;
           if (rc == VO_OK) deferred = 2;
         } else {  // (a host image: behind its upload, vo_set_image_host_async)

@@ -500,7 +500,8 @@ static int orb_prepare(vo_ctx *c, int w, int h, const vo_orb_params *p, int max_
 // The per-bin candidate table of the image in `slot` by the two tile kernels (orb_tile.hpp), on c->stream. Needs
 // S->plan.ok. Leaves lvl_total / done / keys zeroed, as it needs them.
 // src != null: level 0 is read from that image (device memory, src_stride bytes per row, w x h) instead of the slot's plane
-static int orb_tile_enqueue(vo_ctx *c, int slot, const vo_bin_params *bp, vo_cand_table &T, const uint8_t *src = nullptr,
+// mask_slot: the slot whose ignore mask is the image's (the slot itself, or where `src` is on its way to); < 0: none
+static int orb_tile_enqueue(vo_ctx *c, int slot, const vo_bin_params *bp, vo_cand_table &T, int mask_slot, const uint8_t *src = nullptr,
                             int src_stride = 0, int src_w = 0, int src_h = 0) {
   const vo_orb_params *p = &bp->orb;
   if (!src && (slot < 0 || slot >= c->cfg.n_slots || c->slots[slot].n_levels <= 0)) VO_FAIL(c, VO_ERR_INVALID, "slot holds no image");
@@ -511,6 +512,8 @@ static int orb_tile_enqueue(vo_ctx *c, int slot, const vo_bin_params *bp, vo_can
   vo_orb_state *S = c->orb;
   if (!S->plan.ok) return 1;  // (the caller takes the per-stage kernels)
   if (!src && vo_slot_acquire(c, slot) < 0) return VO_ERR_HIP;
+  vo_mask_view mask;
+  if (vo_slot_mask_acquire(c, mask_slot, &mask) < 0) return VO_ERR_HIP;
   hipStream_t s = c->stream;
   uint8_t *A = S->arena;
   if (!S->tile_clean) {  // (once after the per-stage kernels ran on this arena, never in a steady stream)
@@ -596,6 +599,7 @@ static int orb_tile_enqueue(vo_ctx *c, int slot, const vo_bin_params *bp, vo_can
   f.tab_has = T.has;
   f.host_flags = T.h_flags;
   f.dev_flags = (int *)(A + S->o_devflags);
+  f.mask = mask;
   vo_prof_begin(c, VO_K_AUX);
   hipLaunchKernelGGL(orb_tile_kernel, dim3(a.nx * a.ny), dim3(ORB_TILE_NT), (size_t)S->plan.lds_bytes, s, a);
   hipLaunchKernelGGL(orb_finish_kernel, dim3(p->n_levels * f.parts), dim3(ORB_ST), 0, s, f);
@@ -783,10 +787,12 @@ extern "C" int vo_extract_orb_with_binning(vo_ctx *c, int slot, const vo_orb_par
   vo_orb_state *S = c->orb;
   uint8_t *A = S->arena;
   VO_CHECK_HIP(c, hipMemcpyAsync(A + S->o_weight, weight, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, c->stream));
+  vo_mask_view mask;  // (the slot's ignore mask: keypoints on it take part in the detection, not in the arg-max)
+  if (vo_slot_mask_acquire(c, slot, &mask) < 0) return VO_ERR_HIP;
   rc = vo_bucket_argmax_enqueue(c, (const float *)(A + S->o_oxy), (const float *)(A + S->o_oresp), S->max_out, inv_u_step,
                                 inv_v_step, n_bins_u, n_bins_v, (const int32_t *)(A + S->o_weight),
                                 (unsigned long long *)(A + S->o_keys), (float *)(A + S->o_bpts), (int32_t *)(A + S->o_bidx),
-                                (int *)(A + S->o_bn), (const int *)(A + S->o_on));
+                                (int *)(A + S->o_bn), (const int *)(A + S->o_on), &mask);
   if (rc < 0) return rc;
   int m = 0, n = 0, flags = 0;
   VO_CHECK_HIP(c, hipMemcpyAsync(&m, A + S->o_bn, sizeof(int), hipMemcpyDeviceToHost, c->stream));
@@ -835,11 +841,13 @@ extern "C" int vo_extract_orb_with_binning_enqueue(vo_ctx *c, int slot, const vo
   if (rc == VO_OK) {
     uint8_t *A = S->arena;
     hipError_t e = hipMemcpyAsync(A + S->o_weight, h_w, sizeof(int32_t) * (size_t)total, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess)
+    vo_mask_view mask;
+    if (e == hipSuccess && vo_slot_mask_acquire(c, slot, &mask) < 0) rc = VO_ERR_HIP;
+    if (e == hipSuccess && rc == VO_OK)
       rc = vo_bucket_argmax_enqueue(c, (const float *)(A + S->o_oxy), (const float *)(A + S->o_oresp), S->max_out, inv_u_step,
                                     inv_v_step, n_bins_u, n_bins_v, (const int32_t *)(A + S->o_weight),
                                     (unsigned long long *)(A + S->o_keys), (float *)(A + S->o_bpts),
-                                    (int32_t *)(A + S->o_bidx), (int *)(A + S->o_bn), (const int *)(A + S->o_on));
+                                    (int32_t *)(A + S->o_bidx), (int *)(A + S->o_bn), (const int *)(A + S->o_on), &mask);
     if (e == hipSuccess && rc == VO_OK) e = hipMemcpyAsync(S->h_res, A + S->o_bn, sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && rc == VO_OK) e = hipMemcpyAsync(S->h_res + 4, A + S->o_on, sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess && rc == VO_OK) e = hipMemcpyAsync(S->h_res + 8, A + S->o_flags, sizeof(int), hipMemcpyDeviceToHost, c->stream);
@@ -889,16 +897,17 @@ const vo_cand_table *vo_orb_cand_table(vo_ctx *c, int table) {
 vo_cand_table *vo_orb_cand_table_mut(vo_ctx *c, int table) { return const_cast<vo_cand_table *>(vo_orb_cand_table(c, table)); }
 
 static int cand_table_enqueue(vo_ctx *c, int slot, const vo_bin_params *bp, int table, const uint8_t *src, int src_stride, int src_w,
-                              int src_h);
+                              int src_h, int mask_slot);
 extern "C" int vo_new_point_candidates_enqueue(vo_ctx *c, int slot, const vo_bin_params *bp, int table) {
-  return cand_table_enqueue(c, slot, bp, table, nullptr, 0, 0, 0);
+  return cand_table_enqueue(c, slot, bp, table, nullptr, 0, 0, 0, slot);
 }
-int vo_new_point_candidates_enqueue_image(vo_ctx *c, const uint8_t *dev_img, int stride, int w, int h, const vo_bin_params *bp, int table) {
+int vo_new_point_candidates_enqueue_image(vo_ctx *c, const uint8_t *dev_img, int stride, int w, int h, const vo_bin_params *bp, int table,
+                                          int mask_slot) {
   if (!dev_img || stride < w || w <= 0 || h <= 0) return VO_ERR_INVALID;
-  return cand_table_enqueue(c, -1, bp, table, dev_img, stride, w, h);
+  return cand_table_enqueue(c, -1, bp, table, dev_img, stride, w, h, mask_slot);
 }
 static int cand_table_enqueue(vo_ctx *c, int slot, const vo_bin_params *bp, int table, const uint8_t *src, int src_stride, int src_w,
-                              int src_h) {
+                              int src_h, int mask_slot) {
   if (!c || !bp || table < 0 || table > 1 || bp->n_bins_u <= 0 || bp->n_bins_v <= 0) return VO_ERR_INVALID;
   const int total = bp->n_bins_u * bp->n_bins_v;
   if (total > 32768) VO_FAIL(c, VO_ERR_CAPACITY, "%d bins: the closed step [10] handles at most 32768", total);
@@ -943,7 +952,7 @@ static int cand_table_enqueue(vo_ctx *c, int slot, const vo_bin_params *bp, int 
   // VO_DBG_STAGED_DETECT forces the per-stage kernels (19 launches), the same table bit for bit
   int rc = 1;
   if (!c->dbg[VO_DBG_STAGED_DETECT]) {
-    rc = orb_tile_enqueue(c, slot, bp, T, src, src_stride, src_w, src_h);
+    rc = orb_tile_enqueue(c, slot, bp, T, mask_slot, src, src_stride, src_w, src_h);
     if (rc == VO_OK) {
       hipError_t e = hipEventRecord(T.ready, c->stream);
       if (e != hipSuccess) {
@@ -957,11 +966,13 @@ static int cand_table_enqueue(vo_ctx *c, int slot, const vo_bin_params *bp, int 
     return rc;
   }
   rc = orb_enqueue(c, slot, &bp->orb, total);
+  vo_mask_view mask;
+  if (rc == VO_OK && vo_slot_mask_acquire(c, mask_slot, &mask) < 0) rc = VO_ERR_HIP;
   if (rc == VO_OK) {
     uint8_t *A = S->arena;
     rc = vo_bucket_table_enqueue(c, (const float *)(A + S->o_oxy), (const float *)(A + S->o_oresp), S->max_out,
                                  bp->inv_u_step, bp->inv_v_step, bp->n_bins_u, bp->n_bins_v,
-                                 (unsigned long long *)(A + S->o_keys), T.xy, T.has, (const int *)(A + S->o_on));
+                                 (unsigned long long *)(A + S->o_keys), T.xy, T.has, (const int *)(A + S->o_on), &mask);
     hipError_t e = hipSuccess;
     if (rc == VO_OK) e = hipMemcpyAsync(T.h_flags, A + S->o_flags, sizeof(int), hipMemcpyDeviceToHost, c->stream);
     if (rc == VO_OK && e == hipSuccess)

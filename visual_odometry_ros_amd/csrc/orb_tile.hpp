@@ -411,6 +411,8 @@ struct OrbFinishArgs {
   uint8_t *tab_has;          // [n_bins]
   int *host_flags;           // pinned: [0] capacity flags (1 candidate lists, 2 keypoint count), [1] keypoints detected
   int *dev_flags;            // the same two words on the device (test hooks)
+  vo_mask_view mask;         // the image's ignore mask (vo_set_slot_mask); p == null: none. Only the VOTE reads it: the cuts, the
+                             // counts and the keypoint count reported in host_flags[1] are those of the unmasked detection
 };
 
 // one candidate that survived both cuts: its bin's key. xs / ys as orb_output_kernel writes keypoint coordinates
@@ -419,6 +421,7 @@ __device__ __forceinline__ void orb_finish_vote(const OrbFinishArgs &a, int l, i
   const float xs = l ? (float)x * a.scale[l] : (float)x, ys = l ? (float)y * a.scale[l] : (float)y;
   const unsigned u = (unsigned)(int)floorf(xs * a.inv_u), v = (unsigned)(int)floorf(ys * a.inv_v);
   if (u >= (unsigned)a.n_bins_u || v >= (unsigned)a.n_bins_v) return;
+  if (a.mask.p && !vo_mask_usable(a.mask, xs, ys)) return;  // an ignored keypoint does not vote: "detect, drop, then bucket"
   if (!(-1.0f < r)) return;  // never beats the initial max_score of -1 (NaN included)
   r = r + 0.0f;              // -0 -> +0: the reference's "<" does not tell them apart
   const unsigned ord = orb_ord(r);

@@ -77,6 +77,10 @@ static void layout_slot(vo_ctx *c, vo_pyramid *P, int w, int h) {
   size_t off = 0;
   P->w = w;
   P->h = h;
+  if (P->mask_on && (P->mask_w != w || P->mask_h != h)) {  // a mask of another image size does not describe this image: dropped
+    P->mask_on = 0;
+    P->mask_ver = 0;
+  }
   for (int l = 0; l <= c->cfg.max_level && l < VO_MAX_LEVELS; ++l) {
     const int stride = ((w + 2 * VO_PAD) + 63) & ~63;
     P->lv[l].w = w;

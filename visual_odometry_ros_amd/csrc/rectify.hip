@@ -269,6 +269,76 @@ extern "C" int vo_rectify_get_maps(vo_ctx *c, int cam, float *map_u, float *map_
   return VO_OK;
 }
 
+// ---- where the rectified image shows the source: vo_rectify_validity_mask ------------------------------------------------
+// cv::remap fills what lies outside the source with 0 (pyramid.hip: remap_level0_kernel); FAST fires along the edge between
+// picture and fill. valid(x, y) iff the map's sample point lies inside the source image (float compares, NaN is invalid); the
+// mask is 255 where every pixel of the (2 erode + 1)^2 square around (x, y), clipped to the image, is valid — a square minimum,
+// done as a row pass and a column pass. One thread per pixel, coalesced byte stores; runs once per camera model.
+struct ValidArgs {
+  int w, h, r;
+  const float *mu, *mv;   // pass 0
+  const uint8_t *src;     // passes 1, 2
+  uint8_t *dst;
+};
+template <int PASS>
+__global__ __launch_bounds__(256) void rectify_valid_kernel(ValidArgs a) {
+  const int x = blockIdx.x * blockDim.x + threadIdx.x, y = blockIdx.y;
+  if (x >= a.w || y >= a.h) return;
+  const size_t o = (size_t)y * a.w + x;
+  if (PASS == 0) {
+    const float u = a.mu[o], v = a.mv[o];
+    a.dst[o] = (u >= 0.0f && u <= (float)(a.w - 1) && v >= 0.0f && v <= (float)(a.h - 1)) ? 255 : 0;
+  } else if (PASS == 1) {
+    const int x0 = max(x - a.r, 0), x1 = min(x + a.r, a.w - 1);
+    int m = 255;
+    for (int k = x0; k <= x1; ++k) m = min(m, (int)a.src[(size_t)y * a.w + k]);
+    a.dst[o] = (uint8_t)m;
+  } else {
+    const int y0 = max(y - a.r, 0), y1 = min(y + a.r, a.h - 1);
+    int m = 255;
+    for (int k = y0; k <= y1; ++k) m = min(m, (int)a.src[(size_t)k * a.w + x]);
+    a.dst[o] = (uint8_t)m;
+  }
+}
+
+extern "C" int vo_rectify_validity_mask(vo_ctx *c, int cam, int erode, void *out, int stride, int on_device) {
+  if (!c || !out || cam < 0 || cam > 1) return VO_ERR_INVALID;
+  if (!c->rect_u[cam]) VO_FAIL(c, VO_ERR_INVALID, "no rectification map for camera %d", cam);
+  if (erode < 0 || erode > 31) VO_FAIL(c, VO_ERR_INVALID, "erode must be in 0..31, got %d", erode);
+  const int w = c->rect_w[cam], h = c->rect_h[cam];
+  if (stride < w) VO_FAIL(c, VO_ERR_INVALID, "mask stride %d is below the map width %d", stride, w);
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  uint8_t *tmp = nullptr;  // two planes, for the length of this call (a set-up call, like the maps' own)
+  VO_CHECK_HIP(c, vo_dev_malloc(c, (void **)&tmp, 2 * (size_t)w * h));
+  ValidArgs a;
+  memset(&a, 0, sizeof(a));
+  a.w = w;
+  a.h = h;
+  a.r = erode;
+  a.mu = c->rect_u[cam];
+  a.mv = c->rect_v[cam];
+  const dim3 grid((w + 255) / 256, h), block(256);
+  uint8_t *A = tmp, *B = tmp + (size_t)w * h;
+  a.dst = A;
+  hipLaunchKernelGGL(rectify_valid_kernel<0>, grid, block, 0, c->stream, a);
+  if (erode > 0) {
+    a.src = A;
+    a.dst = B;
+    hipLaunchKernelGGL(rectify_valid_kernel<1>, grid, block, 0, c->stream, a);
+    a.src = B;
+    a.dst = A;
+    hipLaunchKernelGGL(rectify_valid_kernel<2>, grid, block, 0, c->stream, a);
+  }
+  hipError_t e = hipGetLastError();
+  if (e == hipSuccess)
+    e = hipMemcpy2DAsync(out, (size_t)stride, A, (size_t)w, (size_t)w, (size_t)h, on_device ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost,
+                         c->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+  (void)hipFree(tmp);
+  VO_CHECK_HIP(c, e);
+  return VO_OK;
+}
+
 // ---- image ingestion through the maps ---------------------------------------------------
 static int fmt_bytes(int format) {
   switch (format) {

@@ -245,6 +245,7 @@ extern "C" int vo_svo_create(vo_ctx *c, const vo_svo_params *prm, vo_svo **out) 
   s->kf_rot = prm->kf_rotation_deg * (float)(3.14159265358979323846 / 180.0);  // thres_rotation * D2R
   s->first = true;
   for (int k = 0; k < 5; ++k) s->slot[k] = k;
+  vo_driver_mask_release_slots(c, s->slot, 5);  // (whatever an earlier user of these slots left switched on)
   // the keyframes' device storage (landmark table, keyframe ring, the local BA's scratch and arena) is made here, so that a
   // failure surfaces at construction and no keyframe ever allocates
   rc = vo_svo_lba_init(s);
@@ -273,6 +274,8 @@ extern "C" void vo_svo_destroy(vo_svo *s) {
   if (s->dbg.fork) (void)hipEventDestroy(s->dbg.fork);
   if (s->dbg.done) (void)hipEventDestroy(s->dbg.done);
   vo_pose_cov_state_free(&s->cov);
+  if (s->c && !s->mono) vo_driver_mask_release_slots(s->c, s->slot, 5);  // (operator calls on these slots no longer see this driver's mask)
+  vo_driver_mask_free(&s->mask);
   vo_svo_lba_free(s);
   delete s;
 }
@@ -321,11 +324,25 @@ static int svo_ingest(vo_svo *s, const void *left, const void *right, int stride
   return VO_OK;
 }
 
+// The pair about to be ingested carries the mask that is current NOW: the left slot's plane is brought up to the master (a device
+// copy on the side stream, only when the master changed since that plane's copy) before anything of the pair is enqueued. The
+// detector (side stream) and the gate of the pair's own frame (main stream, one event per refresh) read that plane.
+static int svo_bind_mask(vo_svo *s) {
+  return vo_driver_mask_bind(s->c, &s->mask, s->slot[S_NL], s->prm.frame.width, s->prm.frame.height);
+}
+
+extern "C" int vo_svo_set_mask(vo_svo *s, const void *mask, int stride, int on_device) {
+  if (!s) return VO_ERR_INVALID;
+  const int left[3] = {s->slot[S_P], s->slot[S_CL], s->slot[S_NL]};  // (the three slots left images rotate through)
+  return vo_driver_mask_set(s->c, &s->mask, left, 3, mask, stride, on_device, s->prm.frame.width, s->prm.frame.height);
+}
+
 extern "C" int vo_svo_prefetch(vo_svo *s, const void *left, const void *right, int stride, int on_device) {
   if (!s || !left || !right) return VO_ERR_INVALID;
   const double t_in = g_trace ? svo_now() : 0.0;
   VO_CHECK_HIP(s->c, hipSetDevice(s->c->device));
   s->prefetched = false;  // (whatever was handed over before is overwritten from here on, also if this fails half-way)
+  RC(svo_bind_mask(s));
   RC(svo_ingest(s, left, right, stride, on_device, true, true));
   if (g_trace) s->ht.acc[2] += svo_now() - t_in;
   s->pre_l = left;
@@ -431,13 +448,14 @@ extern "C" int vo_svo_enqueue(vo_svo *s, const void *left, const void *right, in
     // a pair handed over early that is not this one: its candidates' launch may still read the slots this pair goes into, and
     // the synchronous call builds its pyramids on the MAIN stream — behind that launch, then (one event; nothing in the loop)
     RC(vo_frame_candidates_abandon(c, s->tab_next));
+    RC(svo_bind_mask(s));
     deferred = !s->first && s->c->ingest_side;
     if (deferred && !s->prm.rectify && s->n > 0 && vo_orb_cand_table(c, s->tab_next)) {
       // the detector needs the left IMAGE, not its pyramid: it starts now, on the side stream — from the caller's device image at
       // once, from the slot's staging plane as soon as a host image's upload is queued — while the main stream builds the pyramids
       if (on_device) {
         const int rc = vo_new_point_candidates_enqueue_image(c, (const uint8_t *)left, stride, s->prm.frame.width, s->prm.frame.height,
-                                                             &s->prm.bins, s->tab_next);
+                                                             &s->prm.bins, s->tab_next, s->slot[S_NL]);
         if (rc < 0) return rc;
         issued = rc == VO_OK;
       } else {

@@ -52,6 +52,7 @@ struct vo_svo {
   // vo_svo_set_pose_covariance (MonoVO: vo_mvo_set_pose_covariance): one launch of pose_covariance.hip behind every frame's BA
   // launch, in stream order
   VoPoseCovState cov;
+  vo_driver_mask mask;  // vo_svo_set_mask (MonoVO: vo_mvo_set_mask): the ignore mask the pairs ingested from now on carry
   int mono = 0;  // the keyframe storage serves a MonoVO (mono_vo.hip): one observation per keyframe entry, bundled flags
   // all_stkeyframes_ (stats_keyframe): every keyframe's current pose (host) and where its related landmarks' ids are kept
   // on the device (a pool that only grows)

@@ -160,6 +160,8 @@ extern "C" void vo_destroy(vo_ctx *c) {
       (void)hipFree(c->slots[s].mem);
       if (c->slots[s].stage) (void)hipFree(c->slots[s].stage);
       if (c->slots[s].ready) (void)hipEventDestroy(c->slots[s].ready);
+      if (c->slots[s].mask) (void)hipFree(c->slots[s].mask);
+      if (c->slots[s].mask_ready) (void)hipEventDestroy(c->slots[s].mask_ready);
     }
     free(c->slots);
   }
@@ -372,7 +374,7 @@ extern "C" int vo_set_stereo_pair_host_async(vo_ctx *c, int slot_l, const uint8_
       // event), under the right image's upload and the pair's pyramids
       VO_CHECK_HIP(c, hipEventRecord(c->ev_fork, s));
       VO_CHECK_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-      const int rc = vo_new_point_candidates_enqueue_image(c, P.stage, width, width, height, c->early_bins, c->early_table);
+      const int rc = vo_new_point_candidates_enqueue_image(c, P.stage, width, width, height, c->early_bins, c->early_table, slots[i]);
       if (rc < 0) return rc;
       c->early_issued = rc == VO_OK ? 1 : 0;
     }
@@ -400,11 +402,127 @@ int vo_set_image_host_async(vo_ctx *c, int slot, const uint8_t *host, int width,
   if (c->early_bins && s != c->stream2) {  // (MonoVO's synchronous call: the detection follows the upload on the side stream)
     VO_CHECK_HIP(c, hipEventRecord(c->ev_fork, s));
     VO_CHECK_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_fork, 0));
-    const int rc = vo_new_point_candidates_enqueue_image(c, P.stage, width, width, height, c->early_bins, c->early_table);
+    const int rc = vo_new_point_candidates_enqueue_image(c, P.stage, width, width, height, c->early_bins, c->early_table, slot);
     if (rc < 0) return rc;
     c->early_issued = rc == VO_OK ? 1 : 0;
   }
   return vo_pyramid_build(c, slot, P.stage, width, height, width);
+}
+
+// ---- ignore masks (vo_hip.h: "Ignore mask") -------------------------------------------------------------------------------
+// A slot's mask travels with the slot (vo_swap_slots swaps it with the pyramid). The plane is allocated once per slot, at the
+// first mask the slot gets; every later mask of the slot is a copy into it.
+int vo_slot_mask_reserve(vo_ctx *c, int slot) {
+  vo_pyramid &P = c->slots[slot];
+  if (!P.mask) VO_CHECK_HIP(c, vo_dev_malloc(c, (void **)&P.mask, (size_t)c->cfg.max_width * c->cfg.max_height));
+  if (!P.mask_ready) VO_CHECK_HIP(c, hipEventCreateWithFlags(&P.mask_ready, hipEventDisableTiming));
+  return VO_OK;
+}
+int vo_slot_mask_write(vo_ctx *c, int slot, const void *src, int stride, int w, int h, hipMemcpyKind kind) {
+  vo_pyramid &P = c->slots[slot];
+  P.mask_ver = 0;
+  if (!src) {
+    P.mask_on = 0;
+    return VO_OK;
+  }
+  int rc = vo_slot_mask_reserve(c, slot);
+  if (rc) return rc;
+  if (stride == w)  // (one linear copy: a 2-D copy from the host is issued row by row)
+    VO_CHECK_HIP(c, hipMemcpyAsync(P.mask, src, (size_t)w * h, kind, c->stream));
+  else
+    VO_CHECK_HIP(c, hipMemcpy2DAsync(P.mask, (size_t)w, src, (size_t)stride, (size_t)w, (size_t)h, kind, c->stream));
+  VO_CHECK_HIP(c, hipEventRecord(P.mask_ready, c->stream));
+  P.mask_seen[0] = P.mask_seen[1] = 0;
+  P.mask_seen[c->stream == c->stream2 ? 1 : 0] = 1;
+  P.mask_w = w;
+  P.mask_h = h;
+  P.mask_on = 1;
+  return VO_OK;
+}
+
+extern "C" int vo_slot_image_size(vo_ctx *c, int slot, int *width, int *height) {
+  if (!c || !width || !height) return VO_ERR_INVALID;
+  if (slot < 0 || slot >= c->cfg.n_slots) VO_FAIL(c, VO_ERR_INVALID, "slot out of range");
+  const vo_pyramid &P = c->slots[slot];
+  *width = P.n_levels > 0 ? P.w : 0;
+  *height = P.n_levels > 0 ? P.h : 0;
+  return VO_OK;
+}
+
+extern "C" int vo_set_slot_mask(vo_ctx *c, int slot, const void *mask, int stride, int on_device) {
+  if (!c) return VO_ERR_INVALID;
+  if (slot < 0 || slot >= c->cfg.n_slots) VO_FAIL(c, VO_ERR_INVALID, "slot out of range");
+  if (vo_frame_in_flight(c)) VO_FAIL(c, VO_ERR_INVALID, "a frame is in flight: collect its result before changing a slot's mask");
+  if (!mask) return vo_slot_mask_write(c, slot, nullptr, 0, 0, 0, hipMemcpyHostToDevice);
+  const vo_pyramid &P = c->slots[slot];
+  if (P.n_levels <= 0) VO_FAIL(c, VO_ERR_INVALID, "slot %d holds no image: a mask has the dimensions of the slot's image", slot);
+  if (stride < P.w) VO_FAIL(c, VO_ERR_INVALID, "mask stride %d is below the image width %d", stride, P.w);
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  VO_CHECK_HIP(c, hipStreamSynchronize(c->stream2));  // a detection that still reads the slot's previous mask
+  int rc = vo_slot_mask_write(c, slot, mask, stride, P.w, P.h, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice);
+  if (rc) return rc;
+  SYNC();  // the caller's buffer is free again
+  return VO_OK;
+}
+
+// The drivers' mask (vo_svo_set_mask / vo_mvo_set_mask): one master plane; the pairs ingested from now on carry a copy of it in
+// their left slot's plane, refreshed on the side stream — the detector's — in front of the pair's detection, and only when the
+// master has changed since that slot's copy was made.
+int vo_driver_mask_set(vo_ctx *c, vo_driver_mask *m, const int *slots, int n_slots, const void *mask, int stride, int on_device,
+                       int w, int h) {
+  if (!mask) {
+    m->on = 0;
+    return VO_OK;
+  }
+  if (stride < w) VO_FAIL(c, VO_ERR_INVALID, "mask stride %d is below the image width %d: a mask is a %d x %d plane of bytes", stride, w, w, h);
+  if (w <= 0 || h <= 0 || w > c->cfg.max_width || h > c->cfg.max_height)
+    VO_FAIL(c, VO_ERR_INVALID, "a %d x %d mask does not fit vo_config %d x %d", w, h, c->cfg.max_width, c->cfg.max_height);
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  if (!m->master) {  // every allocation of the option, at the first mask
+    VO_CHECK_HIP(c, vo_dev_malloc(c, (void **)&m->master, (size_t)w * h));
+    for (int k = 0; k < n_slots; ++k) {
+      const int rc = vo_slot_mask_reserve(c, slots[k]);
+      if (rc) return rc;
+    }
+  }
+  // on the side stream: behind every refresh that still reads the previous content, in front of every later one
+  const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+  if (stride == w)
+    VO_CHECK_HIP(c, hipMemcpyAsync(m->master, mask, (size_t)w * h, kind, c->stream2));
+  else
+    VO_CHECK_HIP(c, hipMemcpy2DAsync(m->master, (size_t)w, mask, (size_t)stride, (size_t)w, (size_t)h, kind, c->stream2));
+  VO_CHECK_HIP(c, hipStreamSynchronize(c->stream2));  // the caller's buffer is free again
+  if (++c->mask_ver_next == 0) ++c->mask_ver_next;
+  m->ver = c->mask_ver_next;
+  m->on = 1;
+  return VO_OK;
+}
+int vo_driver_mask_bind(vo_ctx *c, const vo_driver_mask *m, int slot, int w, int h) {
+  vo_pyramid &P = c->slots[slot];
+  if (!m->on) {
+    P.mask_on = 0;
+    return VO_OK;
+  }
+  if (P.mask_on && P.mask_ver == m->ver) return VO_OK;  // (a static mask costs an ingestion nothing)
+  hipStream_t caller = c->stream;
+  c->stream = c->stream2;
+  const int rc = vo_slot_mask_write(c, slot, m->master, w, w, h, hipMemcpyDeviceToDevice);
+  c->stream = caller;
+  if (rc) return rc;
+  P.mask_ver = m->ver;
+  return VO_OK;
+}
+void vo_driver_mask_release_slots(vo_ctx *c, const int *slots, int n_slots) {
+  for (int k = 0; k < n_slots; ++k)
+    if (slots[k] >= 0 && slots[k] < c->cfg.n_slots) {
+      c->slots[slots[k]].mask_on = 0;
+      c->slots[slots[k]].mask_ver = 0;
+    }
+}
+void vo_driver_mask_free(vo_driver_mask *m) {
+  if (m->master) (void)hipFree(m->master);
+  m->master = nullptr;
+  m->on = 0;
 }
 
 extern "C" int vo_set_pyramid_window_hint(vo_ctx *c, int win) {

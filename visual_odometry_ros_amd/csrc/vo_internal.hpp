@@ -27,6 +27,14 @@ struct vo_pyramid {
   uint8_t seen[2];  // [0] main stream / [1] side stream is already ordered behind the last build
   unsigned gen;     // counts the builds of this slot: what was computed from a slot names the build it read
   uint8_t *stage;  // device staging for an image that arrives from the host asynchronously (allocated on demand)
+  // the ignore mask of the image in this slot (vo_set_slot_mask, the drivers' ingestion): a tightly packed mask_w x mask_h plane,
+  // allocated at the first set (vo_config.max_width x max_height bytes), read by the detector's vote and the track gate while
+  // mask_on. Ordered across the two streams like the pyramid: mask_ready behind every write, mask_seen per stream.
+  uint8_t *mask;
+  int mask_w, mask_h, mask_on;
+  hipEvent_t mask_ready;
+  uint8_t mask_seen[2];
+  unsigned mask_ver;  // the drivers: version of their master plane this copy was made from (0: none)
 };
 
 struct vo_gn_dev_info {
@@ -107,6 +115,9 @@ struct vo_ctx {
   long long n_allocs;
   // vo_debug_set: test / measurement switches of THIS context (never read from the environment inside the library)
   int dbg[VO_DBG_COUNT];
+  // versions of the drivers' mask masters (vo_driver_mask_set): drawn from ONE counter per context, so that a slot's copy made
+  // from one driver's master is never taken for a copy of another driver's (several drivers follow each other on a context)
+  unsigned mask_ver_next;
 };
 
 static inline hipError_t vo_dev_malloc(vo_ctx *c, void **p, size_t bytes) {
@@ -167,6 +178,41 @@ static inline int vo_slot_acquire(vo_ctx *c, int slot) {
   }
   return VO_OK;
 }
+
+// Work about to be enqueued on c->stream reads the slot's ignore mask: the view (p == null without a mask), ordered behind the
+// mask's last write if that ran on the other stream.
+static inline int vo_slot_mask_acquire(vo_ctx *c, int slot, vo_mask_view *v) {
+  v->p = nullptr;
+  v->stride = v->w = v->h = 0;
+  if (slot < 0 || slot >= c->cfg.n_slots) return VO_OK;
+  vo_pyramid &P = c->slots[slot];
+  if (!P.mask_on || !P.mask) return VO_OK;
+  const int k = c->stream == c->stream2 ? 1 : 0;
+  if (!P.mask_seen[k]) {
+    VO_CHECK_HIP(c, hipStreamWaitEvent(c->stream, P.mask_ready, 0));
+    P.mask_seen[k] = 1;
+  }
+  v->p = P.mask;
+  v->stride = v->w = P.mask_w;
+  v->h = P.mask_h;
+  return VO_OK;
+}
+// vo_capi.hip: the slot's plane exists (the only allocation of a slot's mask) / a w x h mask copied into it on c->stream
+// (src == null: the slot has no mask from here on); kind: hipMemcpyHostToDevice or hipMemcpyDeviceToDevice
+int vo_slot_mask_reserve(vo_ctx *c, int slot);
+int vo_slot_mask_write(vo_ctx *c, int slot, const void *src, int stride, int w, int h, hipMemcpyKind kind);
+// the mask a driver (StereoVO, MonoVO) gives to the pairs it ingests (vo_capi.hip)
+struct vo_driver_mask {
+  uint8_t *master = nullptr;  // w x h, tightly packed
+  unsigned ver = 0;           // the context-wide version of the master's content (vo_ctx::mask_ver_next; never 0 once set)
+  int on = 0;
+};
+int vo_driver_mask_set(vo_ctx *c, vo_driver_mask *m, const int *slots, int n_slots, const void *mask, int stride, int on_device,
+                       int w, int h);
+int vo_driver_mask_bind(vo_ctx *c, const vo_driver_mask *m, int slot, int w, int h);  // at ingestion, before the pair's detection
+void vo_driver_mask_free(vo_driver_mask *m);
+// a driver takes or gives up its image slots: none of them carries a mask any longer (the planes stay allocated)
+void vo_driver_mask_release_slots(vo_ctx *c, const int *slots, int n_slots);
 
 // Image ingestion (H2D + pyramid chain) enqueues on the side stream when vo_set_ingest_side_stream is on: launchers
 // use c->stream, which this scope points at the ingest stream and restores on exit.

@@ -30,6 +30,9 @@ struct vo_gn_frame {
   // and the epilogue is mono_gate_body(*mono_gate) — a MonoGateArgs, copied into the kernel arguments
   const uint8_t *m1, *m2, *m3;
   const struct MonoGateArgs *mono_gate;
+  // stereo: the ignore mask of the current left image (p == null: none) — a feature is promoted to stage 4 only where the lookup
+  // at its current left pixel is non-zero (the general form of the y > 660 gate). Mono: MonoGateArgs::ign.
+  vo_mask_view ign;
   // closed step [10] (stereo): updateWeightBin(lmtrack_final.pts_l1) + the emission of the bucketed candidates of the
   // bins left empty, from the speculative per-bin results of the frame kernel
   int np_bins;              // > 0: enabled; n_bins_u * n_bins_v
@@ -213,11 +216,12 @@ int vo_weight_bin_update_enqueue(vo_ctx *c, const float *d_pts, int n, int u_ste
                                  int n_bins_v, int32_t *d_weight);
 int vo_bucket_argmax_enqueue(vo_ctx *c, const float *d_xy, const float *d_response, int n, float inv_u, float inv_v,
                              int n_bins_u, int n_bins_v, const int32_t *d_weight, unsigned long long *d_key,
-                             float *d_pts_out, int32_t *d_idx_out, int *d_n_out, const int *d_n = nullptr);
+                             float *d_pts_out, int32_t *d_idx_out, int *d_n_out, const int *d_n = nullptr,
+                             const vo_mask_view *mask = nullptr);
 
 int vo_bucket_table_enqueue(vo_ctx *c, const float *d_xy, const float *d_response, int n_max, float inv_u, float inv_v,
                             int n_bins_u, int n_bins_v, unsigned long long *d_key, float *d_tab_xy, uint8_t *d_tab_has,
-                            const int *d_n);
+                            const int *d_n, const vo_mask_view *mask = nullptr);
 
 // orb_detect.hip: per-bin candidate tables of the closed step [10] (vo_new_point_candidates_enqueue)
 struct vo_cand_table {
@@ -248,7 +252,9 @@ vo_cand_table *vo_orb_cand_table_mut(vo_ctx *c, int table);
 // the tile kernels on the side stream with NO wait for anything — the caller orders the side stream behind whatever fills the
 // image. Returns 1 (nothing enqueued) where the tile kernels do not apply: the caller detects from the slot as usual.
 int vo_set_image_host_async(vo_ctx *c, int slot, const uint8_t *host, int width, int height, int stride);  // vo_capi.hip
-int vo_new_point_candidates_enqueue_image(vo_ctx *c, const uint8_t *dev_img, int stride, int w, int h, const vo_bin_params *bp, int table);
+// mask_slot: the slot the image is on its way into — its ignore mask (vo_set_slot_mask) is the image's; < 0: none
+int vo_new_point_candidates_enqueue_image(vo_ctx *c, const uint8_t *dev_img, int stride, int w, int h, const vo_bin_params *bp, int table,
+                                          int mask_slot);
 
 // frame_pipeline.hip
 void vo_frame_free(vo_ctx *c);

@@ -22,6 +22,19 @@ __host__ __device__ inline int vo_reflect101(int p, int n) {
   return p;
 }
 
+// The ignore mask of an image (vo_set_slot_mask): a w x h byte plane in the image's level-0 pixels, 0 = ignore. p == null:
+// no mask. The lookup of a float pixel rounds as cv::KeyPointsFilter::runByPixelsMask does — (int)(v + 0.5f) — and an index
+// outside the plane reads as 0 (so does a NaN coordinate). Callers test `m.p` first: without a mask nothing of this runs.
+struct vo_mask_view {
+  const uint8_t *p;
+  int stride, w, h;
+};
+__host__ __device__ inline bool vo_mask_usable(const vo_mask_view &m, float x, float y) {
+  const float fx = x + 0.5f, fy = y + 0.5f;
+  if (!(fx > -1.0f && fx < (float)m.w && fy > -1.0f && fy < (float)m.h)) return false;  // ((int) of (-1, 0) is 0, as in the reference)
+  return m.p[(size_t)(int)fy * (size_t)m.stride + (size_t)(int)fx] != 0;
+}
+
 // i / d and i % d for 0 <= i * d < 2^32 by a multiplication (m = 2^32 / d rounded up): the tile kernels run over
 // rectangles of a few thousand elements whose width is only known at run time (a software division costs ~40 instructions)
 __host__ __device__ inline unsigned vo_magic(int d) { return d > 1 ? 0xFFFFFFFFu / (unsigned)d + 1u : 0u; }
