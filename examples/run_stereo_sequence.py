@@ -44,6 +44,18 @@ def mask_options(args):
     return {}
 
 
+def clahe_options(args):
+    """--clahe [CLIP] / --clahe-tiles X Y as the `equalize` argument of from_yaml: CLAHE on every image before the tracker"""
+    if args.clahe is None:
+        if args.clahe_tiles is not None:
+            raise SystemExit("--clahe-tiles needs --clahe")
+        return {}
+    tiles = tuple(args.clahe_tiles) if args.clahe_tiles is not None else (8, 8)
+    if not (args.clahe >= 0 and args.clahe < float("inf")) or not all(1 <= t <= 32 for t in tiles):
+        raise SystemExit("--clahe: CLIP is finite and >= 0; --clahe-tiles: X and Y are 1..32")
+    return {"equalize": {"clip_limit": args.clahe, "tiles": tiles}}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", required=True, help="a config/stereo/*.yaml file of the reference")
@@ -62,6 +74,9 @@ def parse_args(argv=None):
                     help="ignore mask (binary PGM of the image's size, 0 = ignore): no keypoints and no surviving tracks there")
     ap.add_argument("--mask-rectified", nargs="?", type=int, const=0, default=None, metavar="ERODE",
                     help="with flagDoUndistortion: ignore what the rectification fills in, and ERODE (0..31, default 0) pixels around it")
+    ap.add_argument("--clahe", nargs="?", type=float, const=40.0, default=None, metavar="CLIP",
+                    help="equalise every image with CLAHE before the tracker (clip limit CLIP, default 40; 0: no clipping)")
+    ap.add_argument("--clahe-tiles", nargs=2, type=int, default=None, metavar=("X", "Y"), help="CLAHE tile grid (default 8 8; each 1..32)")
     return ap.parse_args(argv)
 
 
@@ -75,7 +90,7 @@ def main():
     if n == 0:
         raise SystemExit("no image pairs found")
     svo = V.StereoVO.from_yaml(args.config, device=args.device, strict_border=args.strict_border, local_ba=not args.no_local_ba,
-                               pose_covariance=bool(args.covariance), **mask_options(args))
+                               pose_covariance=bool(args.covariance), **mask_options(args), **clahe_options(args))
     cov_file = open(args.covariance, "w") if args.covariance else None
     svo.ctx.sum_order = args.sum_order
     pair = lambda k: (load_grey(os.path.join(args.left, names_l[k])), load_grey(os.path.join(args.right, names_r[k])))  # noqa: E731

@@ -102,7 +102,8 @@ int vo_synchronize(vo_ctx *ctx);
  * It applies to every entry that runs IC or GN on this context: vo_track_with_scale, vo_gn_pose_mono /_stereo, the
  * stereo and mono frame operators (the _closed forms included), vo_svo_* and vo_mvo_*. The order is read when work is
  * enqueued: a change between two frames of a running stream takes effect at the next frame's enqueue. vo_batch
- * streams stay in tree order. Any other value returns VO_ERR_INVALID and changes nothing. */
+ * streams stay in tree order (and unequalised: vo_set_equalize is a property of a context, and a batch's contexts are
+ * its own). Any other value returns VO_ERR_INVALID and changes nothing. */
 enum { VO_SUM_ORDER_TREE = 0, VO_SUM_ORDER_REFERENCE = 1 };
 int vo_set_sum_order(vo_ctx *ctx, int order);
 int vo_get_sum_order(const vo_ctx *ctx); /* VO_SUM_ORDER_*, or VO_ERR_INVALID for a NULL context */
@@ -750,6 +751,57 @@ int vo_set_stereo_pair_rectified_device(vo_ctx *ctx, int slot_l, const void *dev
 enum { VO_PIX_MONO8 = 0, VO_PIX_RGB8 = 1, VO_PIX_BGR8 = 2, VO_PIX_MONO16U = 3, VO_PIX_MONO16S = 4, VO_PIX_F32 = 5 };
 int vo_set_input_format(vo_ctx *ctx, int format);
 int vo_get_input_format(vo_ctx *ctx, int *format);
+
+/* ---- CLAHE equalisation in front of the ingestion ----------------------------------------------------------
+ * An opt-in property of the context, off by default. While it is on, every 8-bit grey image that enters a slot — vo_set_image,
+ * vo_set_image_device, vo_set_stereo_pair_device, vo_set_stereo_pair_host_async, the three *_rectified* entry points and,
+ * through them, vo_svo_* / vo_mvo_* (synchronous call, enqueue / prefetch / result, run; host and device images) — is first
+ * equalised as cv::createCLAHE(clip_limit, Size(tiles_x, tiles_y))->apply would, and everything downstream (the rectifying
+ * remap, the pyramid, the detector, KLT / IC / the frame kernels, the debug image) reads the equalised image. The two images of
+ * a pair are equalised independently. Under rectification the RAW image is equalised, then remapped: cv::remap's zero fill never
+ * enters a histogram. The caller's device image is never written: the result goes into a plane per slot that the context owns.
+ * With the option off no kernel, launch, allocation or result bit differs from a context that never had it.
+ *
+ * The arithmetic (OpenCV 4.x imgproc/src/clahe.cpp, 8-bit path; restated from knowledge of upstream and NOT pinned against an
+ * OpenCV build, like every third-party restatement here), for an image w x h:
+ *   extension  if w % tiles_x == 0 and h % tiles_y == 0 the histograms are taken from the image itself; otherwise from the image
+ *              extended to the right by tiles_x - w % tiles_x columns and at the bottom by tiles_y - h % tiles_y rows with
+ *              BORDER_REFLECT_101 — both amounts whenever either remainder is non-zero, so a dimension that divides evenly is
+ *              then extended by a full tiles_x / tiles_y (upstream's behaviour). tw = w_ext / tiles_x, th = h_ext / tiles_y.
+ *   per tile   the int histogram of its tw x th pixels. If clip_limit > 0: limit = max((int)(clip_limit * tw*th / 256), 1) in
+ *              double; every bin above limit is cut to it, clipped = the sum of what was cut, batch = clipped / 256,
+ *              residual = clipped - 256 * batch; every bin += batch; if residual != 0, step = max(256 / residual, 1) and bins
+ *              0, step, 2 step, ... each += 1 until residual increments are made or the index reaches 256.
+ *   table      lut[i] = saturate_cast<uchar>((float)(running sum up to bin i) * ((float)255 / (float)(tw*th))) — rounded
+ *              half to even, clamped to 0..255.
+ *   blend      per column x: txf = (float)x * (1.0f / tw) - 0.5f, tx1 = floor(txf), xa = txf - tx1, xa1 = 1.0f - xa (weights from
+ *              the unclamped tx1), then tx2 = min(tx1 + 1, tiles_x - 1), tx1 = max(tx1, 0); rows alike with th. Per pixel of
+ *              value v: res = (L[ty1][tx1][v]*xa1 + L[ty1][tx2][v]*xa)*ya1 + (L[ty2][tx1][v]*xa1 + L[ty2][tx2][v]*xa)*ya in float,
+ *              every product and every sum rounded on its own (no FMA); out = saturate_cast<uchar>(res).
+ *
+ * vo_set_equalize: mode VO_EQ_OFF / VO_EQ_CLAHE; tiles_x, tiles_y in 1..32; clip_limit finite and >= 0 (0: no clipping);
+ * anything else returns VO_ERR_INVALID and changes nothing. VO_ERR_INVALID as well while the input format is not VO_PIX_MONO8
+ * (and vo_set_input_format to another format is refused while equalisation is on), and while a frame is in flight. The first call
+ * that turns the option on makes every allocation of it (per slot: the plane, the tables and the histogram counters; one more
+ * set for vo_equalize_image); vo_debug_allocation_count does not move on any later call or frame. At an ingestion entry point an
+ * image with width <= tiles_x or height <= tiles_y returns VO_ERR_SIZE (the reflected extension needs more). The launches run on
+ * the stream of the ingestion chain (vo_set_ingest_side_stream). While the option is on the drivers' synchronous call starts the
+ * keypoint detection from the slot, behind the pyramid, instead of from the caller's image next to it: the same table.
+ * vo_batch streams stay unequalised (their contexts are the batch's own).
+ * vo_get_equalize: the current values (the defaults before any set: VO_EQ_OFF, 40.0, 8 x 8 — cv::createCLAHE's). */
+enum { VO_EQ_OFF = 0, VO_EQ_CLAHE = 1 };
+int vo_set_equalize(vo_ctx *ctx, int mode, double clip_limit, int tiles_x, int tiles_y);
+int vo_get_equalize(vo_ctx *ctx, int *mode, double *clip_limit, int *tiles_x, int *tiles_y);
+/* the operator on its own: dst = CLAHE(src) with the context's current parameters (mode must be VO_EQ_CLAHE);
+ * luts may be NULL, else tiles_y*tiles_x*256 bytes, row-major by tile; src/dst/luts host (on_device 0) or device (1);
+ * VO_EQ_DEVICE_TO_HOST (2): src in device memory, dst and luts in host memory. Any other value is VO_ERR_INVALID. Both strides
+ * are at least the width; VO_ERR_SIZE as at ingestion. Returns when dst is written.
+ * The work is queued on the context's stream behind whatever is queued there, and the call waits for it: called while a frame is
+ * in flight it is correct (stream order; its staging is the operator's own, not a slot's) but returns only after that frame's
+ * device work. One call at a time per context, like every other call on a vo_ctx. */
+enum { VO_EQ_HOST = 0, VO_EQ_DEVICE = 1, VO_EQ_DEVICE_TO_HOST = 2 };
+int vo_equalize_image(vo_ctx *ctx, const void *src, int stride, int width, int height,
+                      void *dst, int dst_stride, uint8_t *luts, int on_device);
 
 /* ---- the drivers' debug image: showTracking / showTrackingBA -----------------------------------------------------
  * Both drivers share one text for each (stereo_vo.cpp:685-688 -> showTrackingBA; mono_vo.cpp:554-555, :626-627 ->

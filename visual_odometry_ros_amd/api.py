@@ -67,6 +67,17 @@ def _mask_arg(mask, width, height):
     return mask, int(mask[0]), int(mask[1]), 1
 
 
+def _equalize_arg(equalize):
+    """from_yaml's `equalize`: None -> None; "clahe" -> {} (OpenCV's defaults); a dict with clip_limit and / or tiles -> itself"""
+    if equalize is None:
+        return None
+    if equalize == "clahe":
+        return {}
+    if isinstance(equalize, dict) and set(equalize) <= {"clip_limit", "tiles"}:
+        return dict(equalize)
+    raise ValueError(f'equalize must be None, "clahe" or dict(clip_limit=, tiles=), not {equalize!r}')
+
+
 class Context:
     """Owns one vo_ctx: a HIP stream, image-pyramid slots and point buffers."""
 
@@ -219,6 +230,52 @@ class Context:
         f = C.c_int()
         self.check(self.lib.vo_get_input_format(self._h, C.byref(f)))
         return {v: k for k, v in self.INPUT_FORMATS.items()}[f.value]
+
+    # ---- CLAHE equalisation in front of the ingestion (include/vo_hip.h: vo_set_equalize) ----------------------------------
+    def set_equalize(self, mode="clahe", clip_limit=40.0, tiles=(8, 8)):
+        """mode "clahe": every 8-bit grey image that enters a slot from now on — through any ingestion call of this context and
+        the StereoVO / MonoVO drivers on it — is first equalised as cv::createCLAHE(clip_limit, tiles).apply would; everything
+        downstream reads the equalised image. None: off (the default). tiles = (tiles_x, tiles_y), each 1..32; clip_limit >= 0
+        (0: no clipping). Refused while the input format is not "mono8" and while a frame is in flight. The first call that turns
+        it on allocates everything the option needs."""
+        if mode not in (None, "clahe"):
+            raise ValueError(f'equalisation mode must be "clahe" or None, not {mode!r}')
+        tx, ty = tiles
+        self.check(self.lib.vo_set_equalize(self._h, 1 if mode else 0, float(clip_limit), int(tx), int(ty)))
+
+    @property
+    def equalize(self):
+        """None while equalisation is off, else {"mode": "clahe", "clip_limit": ..., "tiles": (tiles_x, tiles_y)}"""
+        m, tx, ty, clip = C.c_int(), C.c_int(), C.c_int(), C.c_double()
+        self.check(self.lib.vo_get_equalize(self._h, C.byref(m), C.byref(clip), C.byref(tx), C.byref(ty)))
+        return {"mode": "clahe", "clip_limit": clip.value, "tiles": (tx.value, ty.value)} if m.value else None
+
+    def equalizeImage(self, img):
+        """The operator on its own (vo_equalize_image) with the current parameters: (out, luts), both numpy arrays. `img`: a
+        (H, W) uint8 array (rows may be padded), or (device_ptr, stride, w, h): an image in device memory (read only; the result
+        comes back to the host). out: (H, W) uint8; luts: uint8 [tiles_y, tiles_x, 256], the per-tile
+        look-up tables."""
+        eq = self.equalize
+        if eq is None:
+            raise VoError(-1, "equalizeImage: equalisation is off (set_equalize)")
+        tx, ty = eq["tiles"]
+        luts = np.zeros((ty, tx, 256), np.uint8)
+        if isinstance(img, tuple):
+            ptr, stride, w, h = (int(v) for v in img)
+            if w <= 0 or h <= 0:
+                raise VoError(-1, f"equalizeImage: a {w} x {h} image")
+            out = np.empty((h, w), np.uint8)
+            self.check(self.lib.vo_equalize_image(self._h, C.c_void_p(ptr), stride, w, h, C.c_void_p(out.ctypes.data), w,
+                                                  C.c_void_p(luts.ctypes.data), 2))  # VO_EQ_DEVICE_TO_HOST
+            return out, luts
+        if not isinstance(img, np.ndarray) or img.dtype != np.uint8 or img.ndim != 2 or img.strides[1] != 1 or img.strides[0] < img.shape[1]:
+            img = _u8(img)
+            assert img.ndim == 2
+        h, w = img.shape
+        out = np.empty((h, w), np.uint8)
+        self.check(self.lib.vo_equalize_image(self._h, C.c_void_p(img.ctypes.data), img.strides[0], w, h, C.c_void_p(out.ctypes.data), w,
+                                              C.c_void_p(luts.ctypes.data), 0))
+        return out, luts
 
     def _format_image(self, img):
         """`img` as the C-contiguous array the rectifying entry points read: for "mono8" what _u8 makes of it (as always),
@@ -1070,7 +1127,7 @@ class StereoVO:
         self.stats_frame = []  # AlgorithmStatistics::FrameStatistics::Twc per frame (stereo_vo.cpp:979-980)
 
     @classmethod
-    def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", mask=None, mask_erode=0, **overrides):
+    def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", mask=None, mask_erode=0, equalize=None, **overrides):
         """StereoVO(mode = "rosbag", directory_intrinsic = path) of the reference (stereo_vo.cpp:15-57, :118-280): the
         object configured by one of its config/stereo/*.yaml files. The context is created here (sized by the file) and
         closed with the object. With flagDoUndistortion the pairs go through the rectification maps and the loop runs on
@@ -1080,9 +1137,11 @@ class StereoVO:
         every empty bin adds a landmark — so a caller that sees VO_ERR_CAPACITY raises it). `input_format`: the pairs'
         pixel format (Context.set_input_format); anything but "mono8" needs flagDoUndistortion in the file.
         `mask`: an ignore mask (setMask), or "rectified": the left camera's validity mask (StereoCamera.validityMask(mask_erode):
-        what cv::remap fills with 0 is not looked at), which needs flagDoUndistortion in the file."""
+        what cv::remap fills with 0 is not looked at), which needs flagDoUndistortion in the file.
+        `equalize`: None, "clahe" (OpenCV's defaults) or dict(clip_limit=, tiles=): Context.set_equalize on the new context."""
         from . import config as _config
         cfg = _config.load_stereo_config(path)
+        eq = _equalize_arg(equalize)
         if isinstance(mask, str) and (mask != "rectified" or not cfg["flagDoUndistortion"]):
             raise ValueError('mask="rectified" is the only named mask, and it needs flagDoUndistortion in the file')
         cl, cr = cfg["camera"]["left"], cfg["camera"]["right"]
@@ -1094,6 +1153,8 @@ class StereoVO:
         try:
             if input_format != "mono8":
                 ctx.set_input_format(input_format)
+            if eq is not None:
+                ctx.set_equalize("clahe", **eq)
             Kl, Kr, T_lr, rectify = cl["K"], cr["K"], cfg["T_lr"], False
             if cfg["flagDoUndistortion"]:
                 cam = StereoCamera(ctx)
@@ -1791,7 +1852,7 @@ class MonoVO:
         self.stats_frame = []
 
     @classmethod
-    def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", mask=None, mask_erode=0, **overrides):
+    def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", mask=None, mask_erode=0, equalize=None, **overrides):
         """MonoVO(mode = "rosbag", directory_intrinsic = path) of the reference (mono_vo.cpp:15-60, :137-225): the object
         configured by one of its config/mono/*.yaml files, with the library's 5-point solver at motion_estimator.
         thres_5p_error. The context is created here (sized by the file) and closed with the object. With flagDoUndistortion
@@ -1799,9 +1860,11 @@ class MonoVO:
         constructor (five_point, strict_border, local_ba, debug_image, ...). `max_points`: capacity of a track set (default
         2 * bins + 1024, as StereoVO.from_yaml). `input_format`: the images' pixel format (Context.set_input_format); anything but
         "mono8" needs flagDoUndistortion in the file. `mask`: an ignore mask (setMask), or "rectified": the camera's validity
-        mask (Camera.validityMask(mask_erode)), which needs flagDoUndistortion in the file."""
+        mask (Camera.validityMask(mask_erode)), which needs flagDoUndistortion in the file. `equalize`: None, "clahe" (OpenCV's
+        defaults) or dict(clip_limit=, tiles=): Context.set_equalize on the new context."""
         from . import config as _config
         cfg = _config.load_mono_config(path)
+        eq = _equalize_arg(equalize)
         if isinstance(mask, str) and (mask != "rectified" or not cfg["flagDoUndistortion"]):
             raise ValueError('mask="rectified" is the only named mask, and it needs flagDoUndistortion in the file')
         cam = cfg["camera"]
@@ -1812,6 +1875,8 @@ class MonoVO:
         try:
             if input_format != "mono8":
                 ctx.set_input_format(input_format)
+            if eq is not None:
+                ctx.set_equalize("clahe", **eq)
             if cfg["flagDoUndistortion"]:
                 camera = Camera(ctx, 0)
                 camera.initParams(W, H, cam["K"], cam["D"])

@@ -231,6 +231,9 @@ class StereoVO {
   void setMask(const std::uint8_t *mask, int stride, bool on_device = false) {
     ctx_->check(vo_svo_set_mask(svo_, mask, stride, on_device ? 1 : 0));
   }
+  // NOT in the reference: CLAHE on every image before the tracker (vo::Context::setEqualize on this driver's context): legal
+  // between frames, applies to the images handed over from now on
+  void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) { ctx_->setEqualize(mode, clip_limit, tiles_x, tiles_y); }
   int width() const { return prm_.width; }
   int height() const { return prm_.height; }
   // of the last tracked frame: waits for that frame's covariance launch only

@@ -43,6 +43,11 @@ class Context {
     format_ = format;
   }
   int inputFormat() const { return format_; }
+  // CLAHE equalisation in front of every ingestion of this context (vo_set_equalize): mode VO_EQ_CLAHE / VO_EQ_OFF, OpenCV's
+  // defaults. Refused (throws) while the input format is not VO_PIX_MONO8 and while a frame is in flight.
+  void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) {
+    check(vo_set_equalize(ctx_, mode, clip_limit, tiles_x, tiles_y));
+  }
   // an image handed to the rectifying ingestion (rectifying = true) must be of the context's format, any other a u8 plane
   void checkFormat(int image_format, bool rectifying) const {
     if (image_format != (rectifying ? format_ : (int)VO_PIX_MONO8))

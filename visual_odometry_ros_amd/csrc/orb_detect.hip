@@ -904,6 +904,9 @@ extern "C" int vo_new_point_candidates_enqueue(vo_ctx *c, int slot, const vo_bin
 int vo_new_point_candidates_enqueue_image(vo_ctx *c, const uint8_t *dev_img, int stride, int w, int h, const vo_bin_params *bp, int table,
                                           int mask_slot) {
   if (!dev_img || stride < w || w <= 0 || h <= 0) return VO_ERR_INVALID;
+  // vo_set_equalize: the detector reads the EQUALISED image, which exists behind the ingestion's blend launch only — the caller
+  // takes the deferred detection from the slot (the same table bit for bit, as with VO_DBG_STAGED_DETECT below)
+  if (c && c->eq_mode) return 1;
   return cand_table_enqueue(c, -1, bp, table, dev_img, stride, w, h, mask_slot);
 }
 static int cand_table_enqueue(vo_ctx *c, int slot, const vo_bin_params *bp, int table, const uint8_t *src, int src_stride, int src_w,

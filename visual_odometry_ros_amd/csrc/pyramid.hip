@@ -110,8 +110,22 @@ static int build(vo_ctx *c, int slot_l, const uint8_t *d_l, int slot_r, const ui
       for (int k = 0; k < 3; ++k)
         if (c->frame_slot[k] == (i ? slot_r : slot_l))
           VO_FAIL(c, VO_ERR_INVALID, "slot %d is read by the frame in flight: collect its result first", c->frame_slot[k]);
+  if (c->eq_mode) {  // (refused before the slots change)
+    const int rc = vo_equalize_check(c, w, h);
+    if (rc) return rc;
+  }
   for (int i = 0; i < nimg; ++i) layout_slot(c, P[i], w, h);
   vo_ingest_scope ingest(c);  // launchers enqueue on c->stream: the ingest stream for the duration of this chain
+  if (c->eq_mode) {
+    // vo_set_equalize: the raw image(s) into the slots' equalised planes first — each image on its own — and everything below,
+    // the remap included, reads those
+    const int slots[2] = {slot_l, slot_r};
+    const uint8_t *raw[2] = {d_l, d_r}, *eq[2] = {nullptr, nullptr};
+    const int rc = vo_equalize_enqueue(c, nimg, slots, raw, stride, w, h, eq, &stride);
+    if (rc) return rc;
+    d_l = eq[0];
+    if (d_r) d_r = eq[1];
+  }
   int top = c->cfg.max_level;
   if (c->pyr_win_hint > 0) top = vo_pyr_levels_host(w, h, c->pyr_win_hint, c->cfg.max_level);
   if (cams)

@@ -359,6 +359,8 @@ extern "C" int vo_set_input_format(vo_ctx *c, int format) {
   const int bpp = fmt_bytes(format);
   if (!bpp) VO_FAIL(c, VO_ERR_INVALID, "unknown input format %d (VO_PIX_MONO8 .. VO_PIX_F32)", format);
   if (vo_frame_in_flight(c)) VO_FAIL(c, VO_ERR_INVALID, "a frame is in flight: collect its result before changing the input format");
+  if (c->eq_mode && format != VO_PIX_MONO8)
+    VO_FAIL(c, VO_ERR_INVALID, "equalisation is on (vo_set_equalize) and takes 8-bit grey images only: turn it off before changing the input format");
   if (bpp > c->stage_bpp) {
     VO_CHECK_HIP(c, hipSetDevice(c->device));
     VO_CHECK_HIP(c, hipStreamSynchronize(c->stream2));  // the staging buffers' last use, whichever stream it was on

@@ -132,6 +132,8 @@ extern "C" int vo_create(const vo_config *cfg, vo_ctx **out) {
   VO_CHECK_HIP(c, vo_host_malloc(c, (void **)&c->h_stage, c->h_stage_bytes, hipHostMallocDefault));
   VO_CHECK_HIP(c, vo_dev_malloc(c, (void **)&c->d_img_stage, (size_t)cfg->max_width * cfg->max_height));
   c->stage_bpp = 1;
+  c->eq_clip = 40.0;  // (cv::createCLAHE's defaults; the option itself is off)
+  c->eq_tiles_x = c->eq_tiles_y = 8;
   VO_CHECK_HIP(c, hipStreamSynchronize(c->stream));
   return VO_OK;
 }
@@ -144,6 +146,7 @@ extern "C" void vo_destroy(vo_ctx *c) {
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   vo_frame_free(c);
   vo_rectify_free(c);
+  vo_equalize_free(c);
   vo_draw_free(c);
   vo_sba_free(c);
   vo_orb_describe_free(c);

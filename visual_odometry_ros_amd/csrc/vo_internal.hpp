@@ -35,6 +35,9 @@ struct vo_pyramid {
   hipEvent_t mask_ready;
   uint8_t mask_seen[2];
   unsigned mask_ver;  // the drivers: version of their master plane this copy was made from (0: none)
+  // vo_set_equalize (clahe.hip): the equalised image of this slot, the look-up tables and the histogram counters behind it in one
+  // allocation, made when the option is first turned on. Written and read by the slot's ingestion chain only, on its stream.
+  uint8_t *eq;
 };
 
 struct vo_gn_dev_info {
@@ -118,6 +121,10 @@ struct vo_ctx {
   // versions of the drivers' mask masters (vo_driver_mask_set): drawn from ONE counter per context, so that a slot's copy made
   // from one driver's master is never taken for a copy of another driver's (several drivers follow each other on a context)
   unsigned mask_ver_next;
+  // vo_set_equalize (clahe.hip): every 8-bit image that enters a slot is equalised first. eq_mode == VO_EQ_OFF: nothing of it runs.
+  int eq_mode, eq_tiles_x, eq_tiles_y;
+  double eq_clip;
+  uint8_t *eq_op;  // vo_equalize_image's own storage: a staging plane in front of what a slot has
 };
 
 static inline hipError_t vo_dev_malloc(vo_ctx *c, void **p, size_t bytes) {

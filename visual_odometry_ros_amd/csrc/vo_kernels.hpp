@@ -69,6 +69,14 @@ int vo_pyramid_build_pair_rectified(vo_ctx *c, int slot_l, const uint8_t *d_l, i
 // rectify.hip
 void vo_rectify_free(vo_ctx *c);
 
+// clahe.hip
+void vo_equalize_free(vo_ctx *c);
+// the ingestion's hook (pyramid.hip), with equalisation on: src[i] (w x h, stride bytes per row) equalised into slots[i]'s plane on
+// c->stream; eq[i] / *eq_stride: where the chain reads on. VO_ERR_SIZE for an image not larger than the tile counts.
+int vo_equalize_check(vo_ctx *c, int w, int h);
+int vo_equalize_enqueue(vo_ctx *c, int nimg, const int *slots, const uint8_t *const *src, int stride, int w, int h, const uint8_t **eq,
+                        int *eq_stride);
+
 // frame_pipeline.hip
 bool vo_frame_in_flight(const vo_ctx *c);
 
