@@ -66,6 +66,19 @@ def clahe_options(args):
     return {"equalize": {"clip_limit": args.clahe, "tiles": tiles}}
 
 
+def zncc_options(args):
+    """--zncc THRES [--zncc-win N] as the `zncc_gate` argument of from_yaml: a track survives only where the ZNCC of its
+    N x N patches (centred) exceeds THRES"""
+    if args.zncc is None:
+        if args.zncc_win is not None:
+            raise SystemExit("--zncc-win needs --zncc")
+        return {}
+    win = 15 if args.zncc_win is None else args.zncc_win
+    if not (win % 2 == 1 and 3 <= win <= 31) or args.zncc != args.zncc:
+        raise SystemExit("--zncc: THRES is a number; --zncc-win: N is odd, 3..31")
+    return {"zncc_gate": {"thres": args.zncc, "win": win, "pattern": "centered", "pairs": ("temporal",)}}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", required=True, help="a config/mono/*.yaml file of the reference")
@@ -85,6 +98,9 @@ def parse_args(argv=None):
     ap.add_argument("--clahe", nargs="?", type=float, const=40.0, default=None, metavar="CLIP",
                     help="equalise every image with CLAHE before the tracker (clip limit CLIP, default 40; 0: no clipping)")
     ap.add_argument("--clahe-tiles", nargs=2, type=int, default=None, metavar=("X", "Y"), help="CLAHE tile grid (default 8 8; each 1..32)")
+    ap.add_argument("--zncc", type=float, default=None, metavar="THRES",
+                    help="appearance gate: a track survives only where the ZNCC of its patches in the previous and the current image exceeds THRES")
+    ap.add_argument("--zncc-win", type=int, default=None, metavar="N", help="patch size of --zncc (odd, 3..31; default 15)")
     return ap.parse_args(argv)
 
 
@@ -96,7 +112,8 @@ def main():
     if n == 0:
         raise SystemExit("no images found")
     mvo = V.MonoVO.from_yaml(args.config, device=args.device, strict_border=args.strict_border, local_ba=not args.no_local_ba,
-                             debug_image=bool(args.debug_images), pose_covariance=bool(args.covariance), **mask_options(args), **clahe_options(args))
+                             debug_image=bool(args.debug_images), pose_covariance=bool(args.covariance), **mask_options(args), **clahe_options(args),
+                             **zncc_options(args))
     cov_file = open(args.covariance, "w") if args.covariance else None
     if args.debug_images:
         os.makedirs(args.debug_images, exist_ok=True)

@@ -56,6 +56,19 @@ def clahe_options(args):
     return {"equalize": {"clip_limit": args.clahe, "tiles": tiles}}
 
 
+def zncc_options(args):
+    """--zncc THRES [--zncc-win N] [--zncc-stereo] as the `zncc_gate` argument of from_yaml: a track survives only where the ZNCC of its
+    N x N patches (centred) exceeds THRES"""
+    if args.zncc is None:
+        if args.zncc_win is not None or args.zncc_stereo:
+            raise SystemExit("--zncc-win / --zncc-stereo need --zncc")
+        return {}
+    win = 15 if args.zncc_win is None else args.zncc_win
+    if not (win % 2 == 1 and 3 <= win <= 31) or args.zncc != args.zncc:
+        raise SystemExit("--zncc: THRES is a number; --zncc-win: N is odd, 3..31")
+    return {"zncc_gate": {"thres": args.zncc, "win": win, "pattern": "centered", "pairs": ("temporal", "stereo") if args.zncc_stereo else ("temporal",)}}
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", required=True, help="a config/stereo/*.yaml file of the reference")
@@ -77,6 +90,10 @@ def parse_args(argv=None):
     ap.add_argument("--clahe", nargs="?", type=float, const=40.0, default=None, metavar="CLIP",
                     help="equalise every image with CLAHE before the tracker (clip limit CLIP, default 40; 0: no clipping)")
     ap.add_argument("--clahe-tiles", nargs=2, type=int, default=None, metavar=("X", "Y"), help="CLAHE tile grid (default 8 8; each 1..32)")
+    ap.add_argument("--zncc", type=float, default=None, metavar="THRES",
+                    help="appearance gate: a track survives only where the ZNCC of its patches in the previous and the current image exceeds THRES")
+    ap.add_argument("--zncc-win", type=int, default=None, metavar="N", help="patch size of --zncc (odd, 3..31; default 15)")
+    ap.add_argument("--zncc-stereo", action="store_true", help="--zncc also between the current left and right image")
     return ap.parse_args(argv)
 
 
@@ -90,7 +107,8 @@ def main():
     if n == 0:
         raise SystemExit("no image pairs found")
     svo = V.StereoVO.from_yaml(args.config, device=args.device, strict_border=args.strict_border, local_ba=not args.no_local_ba,
-                               pose_covariance=bool(args.covariance), **mask_options(args), **clahe_options(args))
+                               pose_covariance=bool(args.covariance), **mask_options(args), **clahe_options(args),
+                               **zncc_options(args))
     cov_file = open(args.covariance, "w") if args.covariance else None
     svo.ctx.sum_order = args.sum_order
     pair = lambda k: (load_grey(os.path.join(args.left, names_l[k])), load_grey(os.path.join(args.right, names_r[k])))  # noqa: E731

@@ -686,6 +686,58 @@ int vo_slot_image_size(vo_ctx *ctx, int slot, int *width, int *height);
 int vo_svo_set_mask(vo_svo *svo, const void *mask, int stride, int on_device);
 /* (MonoVO: vo_mvo_set_mask, below) */
 
+/* ---- ZNCC: image_processing::calcZNCC and the appearance gate ---------------------------------------
+ * core/util/image_processing.cpp:195-266 with interpImage (:28-77). The reference has the function and, commented out in
+ * FeatureTracker::trackWithPrior (feature_tracker.cpp:198-202), the place for it: calcZNCC(img0, img1, pts0[i], pts_track[i],
+ * 15) > 0.5f. ZNCC does not change under gain and offset: the one test of a track that keeps its meaning under auto-exposure
+ * and between two cameras of different gain.
+ *
+ * vo_zncc: n values, out[i] = ZNCC of the win x win patch of slot0's image at pts0[i] and of slot1's image at pts1[i] (level 0 as
+ * the tracker sees it: after rectification / equalisation; both images of one size, VO_ERR_SIZE otherwise). Host pointers;
+ * synchronous. n == 0 is legal. The arithmetic, all in float32, every operation rounded on its own (no FMA):
+ *   window   win odd, 3 .. 31 (VO_ERR_INVALID otherwise; the reference throws on even).
+ *   taps     n_elem = win * win; tap k = i * win + j has the offset (i - o, j - o) in (x, y).
+ *            VO_ZNCC_PATTERN_REFERENCE: o = win. This is the reference's own text (patt[ind] = (i - win_sz, j - win_sz); win_half
+ *            is computed and not used): the patch lies up-left of the point, its nearest corner at (-1, -1). Restated as written.
+ *            VO_ZNCC_PATTERN_CENTERED:  o = win / 2: the patch the commented-out call presumably meant.
+ *   position pt + offset, one float add per coordinate.
+ *   sample   u0 = (int)u, v0 = (int)v (toward zero); valid iff 0 <= u0 < W - 1 and 0 <= v0 < H - 1 (the image, not the padded
+ *            plane); ax = u - u0, ay = v - v0; value = ((axay * (((I1 - I2) - I3) + I4) + ax * (-I1 + I2)) + ay * (-I1 + I3)) + I1
+ *            with I1 = I[v0][u0], I2 = I[v0][u0 + 1], I3 = I[v0 + 1][u0], I4 = I[v0 + 1][u0 + 1]. An invalid tap reads -2.0f
+ *            (interpImage's resize(n, -2.0f)). A NaN coordinate, and one beyond the int range, is invalid. u in (-1, 0) gives
+ *            u0 = 0 and a negative ax, as the text does.
+ *   result   mean = sum / (float)n_elem per patch; numer = sum (I0 - mean_l)(I1 - mean_r), denom_l = sum (I0 - mean_l)^2,
+ *            denom_r = sum (I1 - mean_r)^2; numer / sqrtf(denom_l * denom_r). A flat pair gives 0 / 0 = NaN.
+ *   sums     vo_set_sum_order decides. VO_SUM_ORDER_REFERENCE: index order k = 0 .. n_elem - 1. VO_SUM_ORDER_TREE (default): the
+ *            terms zero-padded to P, the next power of two >= max(n_elem, 64); for stride = P/2 .. 1: s[i] += s[i + stride]
+ *            (i < stride); s[0]. One wavefront per feature: lane l holds taps l, l + 64, ...
+ *
+ * The gate (StereoVO / MonoVO; off by default — with it off no launch, wait, allocation or result bit differs): a feature the
+ * BA launch would promote to stage 4 additionally needs zncc > thres (NaN fails), in the same place and with the same
+ * consequences as the ignore mask's track gate, and combined with it by AND: a failing feature stays at stage 3 — it took
+ * part in this frame's BA, is not in the next track set, and its bucket is free for this frame's new points.
+ *   VO_ZNCC_TEMPORAL  the previous left / mono image at the feature's input pixel against the current left / mono image at its
+ *                     final pixel
+ *   VO_ZNCC_STEREO    (StereoVO only) the current left image at the final left pixel against the current right image at the
+ *                     final right pixel
+ * The values come from one launch of the operator's kernel in front of the BA launch, over the whole input track set, behind
+ * everything that writes the final pixels: with the gate on, a strict-border replay that would run on its own stream next to
+ * the frame kernel (vo_stereo_frame_set_strict_border 3, 4, 5) runs stream-ordered instead — the results are the same. A feature that was lost
+ * on the way has whatever its pixels give (often NaN); it is not promoted anyway. MonoVO's host-driven frames (the first two
+ * images, a 5-point fallback) have no gate, as with the mask. vo_batch streams have no gate.
+ * vo_svo_set_zncc_gate: pairs = a bit set of VO_ZNCC_*, 0 = off (win, pattern, thres are then not looked at). The first call
+ * with pairs != 0 allocates the per-feature floats (vo_debug_allocation_count does not move afterwards). VO_ERR_INVALID while a
+ * frame is in flight, for a bad window or pattern, a NaN threshold, unknown bits, and VO_ZNCC_STEREO on a MonoVO.
+ * vo_svo_get_zncc: inspection, like vo_svo_get_new_points — the values the last steady-state frame computed, per input feature
+ * (*n = that frame's input count, 0 before any; at most cap are written; zncc_s is written only where VO_ZNCC_STEREO was on;
+ * either pointer may be NULL). VO_ERR_INVALID while a frame is in flight or with the gate off. */
+enum { VO_ZNCC_PATTERN_REFERENCE = 0, VO_ZNCC_PATTERN_CENTERED = 1 };
+enum { VO_ZNCC_TEMPORAL = 1, VO_ZNCC_STEREO = 2 };
+int vo_zncc(vo_ctx *ctx, int slot0, int slot1, const float *pts0, const float *pts1, int n, int win, int pattern, float *out);
+int vo_svo_set_zncc_gate(vo_svo *svo, int pairs, int win, int pattern, float thres);
+int vo_svo_get_zncc(vo_svo *svo, float *zncc_t, float *zncc_s, int cap, int *n);
+/* (MonoVO: vo_mvo_set_zncc_gate / vo_mvo_get_zncc, below) */
+
 /* ---- undistortion / stereo rectification in front of the trackers ----------
  * core/visual_odometry/camera.cpp. A context holds the maps of two cameras
  * (cam 0 = left or the mono camera, cam 1 = right), device-resident. */
@@ -1013,6 +1065,9 @@ int vo_mvo_get_pose_covariance(vo_mvo *mvo, double P[36], double Sigma_xi[36], d
 int vo_mvo_get_pose_covariance_inputs(vo_mvo *mvo, float *X, float *pts, int cap, int *n, float R01[9], float t01[3]);
 /* the ignore mask of the images ingested from now on: vo_svo_set_mask's rules ("Ignore mask" above) */
 int vo_mvo_set_mask(vo_mvo *mvo, const void *mask, int stride, int on_device);
+/* the ZNCC gate of the steady-state frames ("ZNCC" above): VO_ZNCC_TEMPORAL only, VO_ZNCC_STEREO is VO_ERR_INVALID */
+int vo_mvo_set_zncc_gate(vo_mvo *mvo, int pairs, int win, int pattern, float thres);
+int vo_mvo_get_zncc(vo_mvo *mvo, float *zncc_t, int cap, int *n);
 
 /* ---- 5-point RANSAC pose: MotionEstimator::calcPose5PointsAlgorithm ------------------------------------------------
  * motion_estimator.cpp:21-123 + findCorrectRT (:205-263): cv::findEssentialMat(pts0, pts1, K, RANSAC, confidence, thres_px)

@@ -147,6 +147,7 @@ SYMBOLS = [
     "vo_mvo_set_pose_covariance", "vo_mvo_get_pose_covariance", "vo_mvo_get_pose_covariance_inputs",
     "vo_set_slot_mask", "vo_slot_image_size", "vo_svo_set_mask", "vo_mvo_set_mask", "vo_rectify_validity_mask",
     "vo_set_equalize", "vo_get_equalize", "vo_equalize_image",
+    "vo_zncc", "vo_svo_set_zncc_gate", "vo_svo_get_zncc", "vo_mvo_set_zncc_gate", "vo_mvo_get_zncc",
 ]
 
 _lib = None
@@ -241,6 +242,11 @@ def load():
     lib.vo_set_equalize.argtypes = [vp, ci, cd, ci, ci]
     lib.vo_get_equalize.argtypes = [vp, vp, vp, vp, vp]
     lib.vo_equalize_image.argtypes = [vp, vp, ci, ci, ci, vp, ci, vp, ci]
+    lib.vo_zncc.argtypes = [vp, ci, ci, vp, vp, ci, ci, ci, vp]
+    lib.vo_svo_set_zncc_gate.argtypes = [vp, ci, ci, ci, C.c_float]
+    lib.vo_svo_get_zncc.argtypes = [vp, vp, vp, ci, vp]
+    lib.vo_mvo_set_zncc_gate.argtypes = [vp, ci, ci, ci, C.c_float]
+    lib.vo_mvo_get_zncc.argtypes = [vp, vp, ci, vp]
     lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_five_point_destroy.argtypes = [vp]
     lib.vo_five_point_destroy.restype = None

@@ -78,6 +78,29 @@ def _equalize_arg(equalize):
     raise ValueError(f'equalize must be None, "clahe" or dict(clip_limit=, tiles=), not {equalize!r}')
 
 
+def _zncc_gate_arg(gate, stereo):
+    """zncc_gate= / setZnccGate: None -> off; dict(thres=, win=15, pattern="centered", pairs=("temporal",)) -> the C call's
+    (pairs, win, pattern, thres). pairs: names out of "temporal", "stereo" (StereoVO only)."""
+    if gate is None:
+        return 0, 15, 1, 0.0
+    if not isinstance(gate, dict) or "thres" not in gate or not set(gate) <= {"thres", "win", "pattern", "pairs"}:
+        raise ValueError(f"zncc_gate must be None or dict(thres=, win=, pattern=, pairs=), not {gate!r}")
+    pattern = gate.get("pattern", "centered")
+    if pattern not in Context.ZNCC_PATTERNS:
+        raise ValueError(f"pattern must be one of {sorted(Context.ZNCC_PATTERNS)}, not {pattern!r}")
+    pairs = gate.get("pairs", ("temporal",))
+    if isinstance(pairs, str):
+        pairs = (pairs,)
+    bits = 0
+    for p in pairs:
+        if p not in Context.ZNCC_PAIRS or (p == "stereo" and not stereo):
+            raise ValueError(f'pairs must be out of {"temporal, stereo" if stereo else "temporal"}, not {p!r}')
+        bits |= Context.ZNCC_PAIRS[p]
+    if not bits:
+        raise ValueError("pairs is empty: pass None to switch the gate off")
+    return bits, int(gate.get("win", 15)), Context.ZNCC_PATTERNS[pattern], float(gate["thres"])
+
+
 class Context:
     """Owns one vo_ctx: a HIP stream, image-pyramid slots and point buffers."""
 
@@ -199,6 +222,26 @@ class Context:
             raise VoError(-1, f"slot {slot} holds no image: a mask has the dimensions of the slot's image")
         _, ptr, stride, dev = _mask_arg(mask, w, h)
         self.check(self.lib.vo_set_slot_mask(self._h, slot, ptr, stride, dev))
+
+    # ---- image_processing::calcZNCC (include/vo_hip.h, "ZNCC") ---------------------------------------------------------------
+    ZNCC_PATTERNS = {"reference": 0, "centered": 1}  # VO_ZNCC_PATTERN_*
+    ZNCC_PAIRS = {"temporal": 1, "stereo": 2}         # VO_ZNCC_*
+
+    def calcZNCC(self, slot0, slot1, pts0, pts1, win=15, pattern="reference"):
+        """calcZNCC(img0, img1, pt0, pt1, win) for every pair of points: float32 [n], the ZNCC of the win x win patches of the
+        images in slot0 / slot1 (level 0, as the tracker sees them). pattern "reference": the reference's own taps (the patch
+        lies up-left of the point); "centered": the patch around the point. The sums follow the context's sum_order. A flat
+        pair gives NaN."""
+        if pattern not in self.ZNCC_PATTERNS:
+            raise ValueError(f"pattern must be one of {sorted(self.ZNCC_PATTERNS)}, not {pattern!r}")
+        p0 = np.ascontiguousarray(pts0, np.float32).reshape(-1, 2)
+        p1 = np.ascontiguousarray(pts1, np.float32).reshape(-1, 2)
+        if len(p0) != len(p1):
+            raise ValueError("pts0 and pts1 must hold the same number of points")
+        out = np.zeros(len(p0), np.float32)
+        self.check(self.lib.vo_zncc(self._h, int(slot0), int(slot1), p0.ctypes.data, p1.ctypes.data, len(p0), int(win),
+                                    self.ZNCC_PATTERNS[pattern], out.ctypes.data))
+        return out
 
     def set_image_device(self, slot, dev_ptr, width, height, stride):
         self.check(self.lib.vo_set_image_device(self._h, slot, C.c_void_p(dev_ptr), width, height, stride))
@@ -1095,9 +1138,10 @@ class StereoVO:
     def __init__(self, ctx, width, height, Kl, Kr, T_lr, n_bins_u, n_bins_v, thres_fastscore=15, window_size=21, max_level=6,
                  thres_error=80.0, thres_bidirection=0.5, thres_poseba_error=3.0, thres_alive_ratio=0.6, thres_rotation=15.0,
                  thres_trans=10.0, n_max_keyframes_in_window=9, strict_border=4, local_ba=True, rectify=False, thres_sampson=60.0,
-                 debug_image=False, pose_covariance=False, sigma_px=0.0, mask=None):
+                 debug_image=False, pose_covariance=False, sigma_px=0.0, mask=None, zncc_gate=None):
         """debug_image=True: every tracked frame draws the reference's img_debug_ on the device (getDebugImage).
         mask: the ignore mask every pair carries from the first one on (setMask).
+        zncc_gate: dict(thres=, win=15, pattern="centered", pairs=("temporal",)) — the appearance gate (setZnccGate).
         pose_covariance=True: every frame chains the covariance of its pose on the device (getPoseCovariance); sigma_px > 0
         scales by that pixel noise instead of the a-posteriori variance.
         rectify=True is system_flags_.flagDoUndistortion: the context's stereo rectification maps (StereoCamera.
@@ -1123,11 +1167,14 @@ class StereoVO:
             ctx.check(self.lib.vo_svo_set_pose_covariance(self._h, 1, float(sigma_px)))
         if mask is not None:
             self.setMask(mask)
+        if zncc_gate is not None:
+            self.setZnccGate(zncc_gate)
         self._info = SvoFrameInfo()
         self.stats_frame = []  # AlgorithmStatistics::FrameStatistics::Twc per frame (stereo_vo.cpp:979-980)
 
     @classmethod
-    def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", mask=None, mask_erode=0, equalize=None, **overrides):
+    def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", mask=None, mask_erode=0, equalize=None, zncc_gate=None,
+                  **overrides):
         """StereoVO(mode = "rosbag", directory_intrinsic = path) of the reference (stereo_vo.cpp:15-57, :118-280): the
         object configured by one of its config/stereo/*.yaml files. The context is created here (sized by the file) and
         closed with the object. With flagDoUndistortion the pairs go through the rectification maps and the loop runs on
@@ -1138,7 +1185,8 @@ class StereoVO:
         pixel format (Context.set_input_format); anything but "mono8" needs flagDoUndistortion in the file.
         `mask`: an ignore mask (setMask), or "rectified": the left camera's validity mask (StereoCamera.validityMask(mask_erode):
         what cv::remap fills with 0 is not looked at), which needs flagDoUndistortion in the file.
-        `equalize`: None, "clahe" (OpenCV's defaults) or dict(clip_limit=, tiles=): Context.set_equalize on the new context."""
+        `equalize`: None, "clahe" (OpenCV's defaults) or dict(clip_limit=, tiles=): Context.set_equalize on the new context.
+        `zncc_gate`: the constructor's (setZnccGate)."""
         from . import config as _config
         cfg = _config.load_stereo_config(path)
         eq = _equalize_arg(equalize)
@@ -1170,7 +1218,7 @@ class StereoVO:
                       thres_sampson=ft["thres_sampson"],
                       thres_bidirection=ft["thres_bidirection"], thres_poseba_error=me["thres_poseba_error"],
                       thres_alive_ratio=ku["thres_alive_ratio"], thres_rotation=ku["thres_rotation"], thres_trans=ku["thres_trans"],
-                      n_max_keyframes_in_window=ku["n_max_keyframes_in_window"], rectify=rectify, mask=mask, **overrides)
+                      n_max_keyframes_in_window=ku["n_max_keyframes_in_window"], rectify=rectify, mask=mask, zncc_gate=zncc_gate, **overrides)
         except Exception:
             ctx.close()
             raise
@@ -1202,6 +1250,28 @@ class StereoVO:
 
     def _set_mask_fn(self):
         return self.lib.vo_svo_set_mask
+
+    _zncc_pairs = 0
+
+    def setZnccGate(self, gate):
+        """The ZNCC appearance gate (include/vo_hip.h, "ZNCC") of the frames tracked FROM NOW ON: dict(thres=, win=15,
+        pattern="centered", pairs=("temporal",)) — a feature is promoted to the next track set only where the ZNCC of its
+        win x win patches exceeds thres: "temporal" the previous left image at its input pixel against the current left image
+        at its final pixel, "stereo" the current left against the current right image. None: off (the default). Refused while
+        a frame is in flight."""
+        pairs, win, pattern, thres = _zncc_gate_arg(gate, True)
+        self.ctx.check(self.lib.vo_svo_set_zncc_gate(self._h, pairs, win, pattern, thres))
+        self._zncc_pairs = pairs
+
+    def getZncc(self):
+        """Inspection: the values the gate computed for the last steady-state frame, per INPUT feature of that frame (the
+        track set before it): {"temporal": float32 [n] or None, "stereo": float32 [n] or None}. A feature that was lost on the
+        way has whatever its pixels gave."""
+        n = C.c_int()
+        self.ctx.check(self.lib.vo_svo_get_zncc(self._h, None, None, 0, C.byref(n)))
+        t, s = np.full(n.value, np.nan, np.float32), np.full(n.value, np.nan, np.float32)
+        self.ctx.check(self.lib.vo_svo_get_zncc(self._h, t.ctypes.data, s.ctypes.data, n.value, C.byref(n)))
+        return {"temporal": t if self._zncc_pairs & 1 else None, "stereo": s if self._zncc_pairs & 2 else None}
 
     def _img(self, a):
         """a host image as the library reads it: a u8 plane, or — with rectify=True — an array of the context's input format"""
@@ -1791,8 +1861,9 @@ class MonoVO:
                  thres_error=20.0, thres_bidirection=1.0, thres_poseba_error=5, thres_sampson=1.0, thres_parallax=1.0,
                  thres_overlap_ratio=0.7, thres_rotation=3.0, thres_translation=3.0, n_max_keyframes_in_window=9, strict_border=4,
                  local_ba=True, rectify=False, thres_5p_error=2.0, debug_image=False, pose_covariance=False, sigma_px=0.0,
-                 mask=None):
+                 mask=None, zncc_gate=None):
         """debug_image=True: every frame draws the reference's img_debug_ on the device (getDebugImage, getDebugPoints).
+        zncc_gate: dict(thres=, win=15, pattern="centered") — the appearance gate of the steady-state frames (setZnccGate).
         pose_covariance=True: every frame chains the covariance of its pose on the device, in map units (getPoseCovariance);
         sigma_px > 0 scales by that pixel noise instead of the a-posteriori variance.
         mask: the ignore mask every image carries from the first one on (setMask)."""
@@ -1848,11 +1919,14 @@ class MonoVO:
             ctx.check(self.lib.vo_mvo_set_pose_covariance(self._h, 1, float(sigma_px)))
         if mask is not None:
             self.setMask(mask)
+        if zncc_gate is not None:
+            self.setZnccGate(zncc_gate)
         self._info = MvoFrameInfo()
         self.stats_frame = []
 
     @classmethod
-    def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", mask=None, mask_erode=0, equalize=None, **overrides):
+    def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", mask=None, mask_erode=0, equalize=None, zncc_gate=None,
+                  **overrides):
         """MonoVO(mode = "rosbag", directory_intrinsic = path) of the reference (mono_vo.cpp:15-60, :137-225): the object
         configured by one of its config/mono/*.yaml files, with the library's 5-point solver at motion_estimator.
         thres_5p_error. The context is created here (sized by the file) and closed with the object. With flagDoUndistortion
@@ -1861,7 +1935,8 @@ class MonoVO:
         2 * bins + 1024, as StereoVO.from_yaml). `input_format`: the images' pixel format (Context.set_input_format); anything but
         "mono8" needs flagDoUndistortion in the file. `mask`: an ignore mask (setMask), or "rectified": the camera's validity
         mask (Camera.validityMask(mask_erode)), which needs flagDoUndistortion in the file. `equalize`: None, "clahe" (OpenCV's
-        defaults) or dict(clip_limit=, tiles=): Context.set_equalize on the new context."""
+        defaults) or dict(clip_limit=, tiles=): Context.set_equalize on the new context. `zncc_gate`: the constructor's
+        (setZnccGate)."""
         from . import config as _config
         cfg = _config.load_mono_config(path)
         eq = _equalize_arg(equalize)
@@ -1900,6 +1975,7 @@ class MonoVO:
             kw = {arg: v for key, (arg, v) in names.items() if key not in cfg["missing"]}
             kw["rectify"] = bool(cfg["flagDoUndistortion"])
             kw["mask"] = mask
+            kw["zncc_gate"] = zncc_gate
             kw.update(overrides)
             obj = cls(ctx, W, H, cam["K"], fe["n_bins_u"], fe["n_bins_v"], **kw)
         except Exception:
@@ -1933,6 +2009,21 @@ class MonoVO:
 
     def _set_mask_fn(self):
         return self.lib.vo_mvo_set_mask
+
+    def setZnccGate(self, gate):
+        """StereoVO.setZnccGate for the mono stream: dict(thres=, win=15, pattern="centered"), the previous image at the
+        feature's input pixel against the current image at its final pixel; None: off. pairs, if given, is ("temporal",). The
+        first two images and a 5-point-fallback frame are host-driven and have no gate. Refused while a frame is in flight."""
+        pairs, win, pattern, thres = _zncc_gate_arg(gate, False)
+        self.ctx.check(self.lib.vo_mvo_set_zncc_gate(self._h, pairs, win, pattern, thres))
+
+    def getZncc(self):
+        """Inspection: float32 [n], the values the gate computed for the last steady-state frame, per INPUT feature."""
+        n = C.c_int()
+        self.ctx.check(self.lib.vo_mvo_get_zncc(self._h, None, 0, C.byref(n)))
+        t = np.full(n.value, np.nan, np.float32)
+        self.ctx.check(self.lib.vo_mvo_get_zncc(self._h, t.ctypes.data, n.value, C.byref(n)))
+        return t
 
     def _ptr(self, img):
         if isinstance(img, np.ndarray):

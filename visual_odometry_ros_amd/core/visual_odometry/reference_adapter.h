@@ -464,6 +464,11 @@ class StereoVO {
   // NOT in the reference: the ignore mask of the pairs tracked from now on (vo::StereoVO::setMask) — CV_8UC1, the left image's
   // size as the tracker sees it, 0 = ignore; an empty Mat: none
   void setMask(const cv::Mat &mask) { vo_adapter::set_mask(impl_, mask); }
+  // The reference's commented-out ZNCC check (feature_tracker.cpp:198-202) as an option (vo::StereoVO::setZnccGate): pairs =
+  // VO_ZNCC_TEMPORAL | VO_ZNCC_STEREO, 0 = off
+  void setZnccGate(int pairs, float thres = 0.5f, int win = 15, int pattern = VO_ZNCC_PATTERN_CENTERED) {
+    impl_.setZnccGate(pairs, thres, win, pattern);
+  }
   // NOT in the reference: CLAHE equalisation of every image before the tracker (vo::StereoVO::setEqualize; VO_EQ_CLAHE / VO_EQ_OFF)
   void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) { impl_.setEqualize(mode, clip_limit, tiles_x, tiles_y); }
   vo::StereoVO &device() { return impl_; }
@@ -566,6 +571,11 @@ class MonoVO {
   // NOT in the reference: the ignore mask of the images tracked from now on (vo::MonoVO::setMask) — CV_8UC1, the image's size, 0 =
   // ignore; an empty Mat: none
   void setMask(const cv::Mat &mask) { vo_adapter::set_mask(impl_, mask); }
+  // The reference's commented-out ZNCC check (feature_tracker.cpp:198-202) as an option (vo::MonoVO::setZnccGate): pairs =
+  // VO_ZNCC_TEMPORAL, 0 = off
+  void setZnccGate(int pairs, float thres = 0.5f, int win = 15, int pattern = VO_ZNCC_PATTERN_CENTERED) {
+    impl_.setZnccGate(pairs, thres, win, pattern);
+  }
   // NOT in the reference: CLAHE equalisation of every image before the tracker (vo::MonoVO::setEqualize; VO_EQ_CLAHE / VO_EQ_OFF)
   void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) { impl_.setEqualize(mode, clip_limit, tiles_x, tiles_y); }
   vo::MonoVO &device() { return impl_; }

@@ -231,6 +231,12 @@ class StereoVO {
   void setMask(const std::uint8_t *mask, int stride, bool on_device = false) {
     ctx_->check(vo_svo_set_mask(svo_, mask, stride, on_device ? 1 : 0));
   }
+  // In the reference only as a commented-out line (feature_tracker.cpp:198-202): the ZNCC appearance gate of the frames tracked
+  // FROM NOW ON (vo_svo_set_zncc_gate; include/vo_hip.h, "ZNCC"). pairs: VO_ZNCC_TEMPORAL | VO_ZNCC_STEREO, 0 = off. A feature is
+  // promoted to the next track set only where the ZNCC of its win x win patches exceeds thres. Throws while a frame is in flight.
+  void setZnccGate(int pairs, float thres = 0.5f, int win = 15, int pattern = VO_ZNCC_PATTERN_CENTERED) {
+    ctx_->check(vo_svo_set_zncc_gate(svo_, pairs, win, pattern, thres));
+  }
   // NOT in the reference: CLAHE on every image before the tracker (vo::Context::setEqualize on this driver's context): legal
   // between frames, applies to the images handed over from now on
   void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) { ctx_->setEqualize(mode, clip_limit, tiles_x, tiles_y); }

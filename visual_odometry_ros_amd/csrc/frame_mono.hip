@@ -484,6 +484,9 @@ static int mono_enqueue_impl(vo_ctx *c, const vo_mono_params *prm, int slot0, in
     if (strict == 4) strict = (f->last_replayed >= VO_CONC_MIN_REPLAYED && n + n_new <= VO_CONC_MAX_WORKGROUPS) ? 3 : 1;
     if (strict == 5) strict = 1;
     if (c->frame_conc_off && strict >= 3) strict = 1;  // a join timed out before: stream order
+    // the ZNCC gate's launch reads the final pixels in front of the BA launch, on the main stream: the replay stays on it too
+    const bool zncc_on = c->zncc_gate && c->zncc_gate->pairs;
+    if (zncc_on && strict >= 3) strict = 1;
     c->frame_strict_now = strict;
     a.strict = strict;
     {
@@ -608,6 +611,12 @@ static int mono_enqueue_impl(vo_ctx *c, const vo_mono_params *prm, int slot0, in
     memcpy(g.K, prm->K, sizeof(g.K));
     g.thres_sampson = prm->thres_sampson;
     if (vo_slot_mask_acquire(c, slot1, &g.ign) < 0) return VO_ERR_HIP;  // (the current image's ignore mask, if it has one)
+    // the ZNCC gate (vo_mvo_set_zncc_gate): every input feature's value at its refined pixel — what a feature that can reach
+    // stage 4 ends on — behind the replay, on this stream
+    if (zncc_on) {
+      rc = vo_zncc_gate_enqueue(c, c->zncc_gate, slot0, slot1, -1, d_p0, f->A_ref, nullptr, n, &g.zn);
+      if (rc < 0) return rc;
+    }
     g.motion = f->st2;
     g.stage = f->stage;
     g.pts1 = f->F_pl1;

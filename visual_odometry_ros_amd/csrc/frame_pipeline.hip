@@ -357,6 +357,9 @@ static int vo_frame_enqueue_body(vo_ctx *c, const vo_stereo_params *prm, int slo
     c->frame_strict_now = (fused && f->last_replayed >= VO_CONC_MIN_REPLAYED && n + n_new <= VO_CONC_MAX_WORKGROUPS) ? 3 : 1;
   if (c->frame_strict_ic == 5 && !fused) c->frame_strict_now = 1;
   if (c->frame_conc_off && c->frame_strict_now >= 3) c->frame_strict_now = 1;  // a join timed out before: stream order
+  // the ZNCC gate's launch reads the final pixels in front of the BA launch, on the main stream: the replay stays on it too
+  const bool zncc_on = n > 0 && c->zncc_gate && c->zncc_gate->pairs;
+  if (zncc_on && c->frame_strict_now >= 3) c->frame_strict_now = 1;
   {
     int g = ((f->last_replayed + 32 + 31) / 32) * 32;
     f->conc_grid = g < 64 ? 64 : (g > 256 ? 256 : g);
@@ -581,6 +584,8 @@ static int vo_frame_enqueue_body(vo_ctx *c, const vo_stereo_params *prm, int slo
     gf.cnt = cnt;
     gf.hdr_flags = &f->hdr->flags;
     if (vo_slot_mask_acquire(c, slot_l1, &gf.ign) < 0) return VO_ERR_HIP;  // (the current left image's ignore mask, if it has one)
+    // the ZNCC gate (vo_svo_set_zncc_gate): every input feature's values, behind whatever wrote F_pl1 / F_pr1 on this stream
+    if (zncc_on) RC(vo_zncc_gate_enqueue(c, c->zncc_gate, slot_l0, slot_l1, slot_r1, d_l0, f->F_pl1, f->F_pr1, n, &gf.zn));
   }
   if (fused) {
     gf.ctl = f->ctl;

@@ -78,6 +78,7 @@ struct GnArgs {
   int f_mono;               // epilogue = mono_gate_body(f_gate)
   MonoGateArgs f_gate;
   vo_mask_view f_ign;       // stereo frame: ignore mask of the current left image (vo_gn_frame::ign); p == null: none
+  vo_zncc_view f_zn;        // stereo frame: the ZNCC gate's values per input feature (vo_gn_frame::zn); on == 0: none
 };
 static_assert(sizeof(GnArgs) <= 3072, "kernel arguments of the BA launch: keep well below the 4 KB segment");
 
@@ -801,7 +802,8 @@ __global__ __launch_bounds__(GN_T) void gn_pose_kernel(GnArgs a) {
   if (a.stage) {
     for (int i = tid; i < n; i += GN_T) {
       const float gate = a.p1[2 * i + 1] > 660 ? 100.f : 0.f;
-      if (a.mask[i] && gate < a.gate_thres && (!a.f_ign.p || vo_mask_usable(a.f_ign, a.p1[2 * i], a.p1[2 * i + 1])))
+      if (a.mask[i] && gate < a.gate_thres && (!a.f_ign.p || vo_mask_usable(a.f_ign, a.p1[2 * i], a.p1[2 * i + 1])) &&
+          (!a.f_zn.on || vo_zncc_pass(a.f_zn, a.orig[i])))
         a.stage[a.orig[i]] = (uint8_t)a.stage_val;
     }
     // survivors of [5] outside the BA set keep mask_motion = true (stereo_vo.cpp:582) and meet the same gate
@@ -809,7 +811,8 @@ __global__ __launch_bounds__(GN_T) void gn_pose_kernel(GnArgs a) {
       for (int i = tid; i < a.f_n; i += GN_T)
         if (a.f_stage[i] == 3 && !(a.f_lmflags[i] & VO_LM_TRIANGULATED)) {
           const float gate = a.f_pl1[2 * i + 1] > 660 ? 100.f : 0.f;
-          if (gate < a.gate_thres && (!a.f_ign.p || vo_mask_usable(a.f_ign, a.f_pl1[2 * i], a.f_pl1[2 * i + 1])))
+          if (gate < a.gate_thres && (!a.f_ign.p || vo_mask_usable(a.f_ign, a.f_pl1[2 * i], a.f_pl1[2 * i + 1])) &&
+              (!a.f_zn.on || vo_zncc_pass(a.f_zn, i)))
             a.stage[i] = (uint8_t)a.stage_val;
         }
   }
@@ -1159,6 +1162,7 @@ int vo_gn_enqueue(vo_ctx *c, bool stereo, bool mono_general_inverse, const float
       a.f_gate = *frame->mono_gate;
     }
     a.f_ign = frame->ign;
+    a.f_zn = frame->zn;
   }
   a.X = dX;
   a.p1 = dP1;

@@ -16,6 +16,7 @@ struct MonoGateArgs {
   float dT_prior[16], K[4];
   float thres_sampson;
   vo_mask_view ign;         // ignore mask of the current image (p == null: none): stage 4 also needs a non-zero lookup at pts1
+  vo_zncc_view zn;          // the ZNCC gate's values of this frame (on == 0: none): stage 4 also needs vo_zncc_pass(zn, i)
   uint8_t *motion;          // scratch [n]
   uint8_t *stage;           // out
   float *pts1;              // out
@@ -95,7 +96,8 @@ __device__ __forceinline__ void mono_gate_body(const MonoGateArgs &a, int tid, i
       float num = mono_dot3(x1, p[0], y1, p[1], 1.0f, p[2]);
       num *= num;
       const float den = ((p[0] * p[0] + p[1] * p[1]) + q[0] * q[0]) + q[1] * q[1];
-      if (num / den < a.thres_sampson && (!a.ign.p || vo_mask_usable(a.ign, x1, y1))) st = 4;
+      if (num / den < a.thres_sampson && (!a.ign.p || vo_mask_usable(a.ign, x1, y1)) && (!a.zn.on || vo_zncc_pass(a.zn, i)))
+        st = 4;
     }
     a.stage[i] = (uint8_t)st;
     a.pts1[2 * i] = x1;

@@ -385,6 +385,7 @@ extern "C" void vo_mvo_destroy(vo_mvo *s) {
   vo_pose_cov_state_free(&s->core.cov);
   if (s->c) vo_driver_mask_release_slots(s->c, s->slot, 3);
   vo_driver_mask_free(&s->core.mask);
+  vo_zncc_gate_free(&s->core.zncc);
   vo_svo_lba_free(&s->core);
   delete s;
 }
@@ -490,6 +491,20 @@ static int mvo_bind_mask(vo_mvo *s) {
 extern "C" int vo_mvo_set_mask(vo_mvo *s, const void *mask, int stride, int on_device) {
   if (!s) return VO_ERR_INVALID;
   return vo_driver_mask_set(s->c, &s->core.mask, s->slot, 3, mask, stride, on_device, s->prm.frame.width, s->prm.frame.height);
+}
+
+// The ZNCC gate of the steady-state frames (include/vo_hip.h, "ZNCC"): the state only — the mono frame operator launches, the BA
+// launch's epilogue (mono_gate.hpp) gates. The host-driven frames (the first two images, the 5-point fallback) have none.
+extern "C" int vo_mvo_set_zncc_gate(vo_mvo *s, int pairs, int win, int pattern, float thres) {
+  if (!s) return VO_ERR_INVALID;
+  if (s->pending) VO_FAIL(s->c, VO_ERR_INVALID, "vo_mvo_set_zncc_gate: a frame is in flight: call vo_mvo_result first");
+  return vo_zncc_gate_set(s->c, &s->core.zncc, pairs, win, pattern, thres, false, s->cap);
+}
+
+extern "C" int vo_mvo_get_zncc(vo_mvo *s, float *zncc_t, int cap, int *n) {
+  if (!s || !n) return VO_ERR_INVALID;
+  if (s->pending) VO_FAIL(s->c, VO_ERR_INVALID, "call vo_mvo_result first");
+  return vo_zncc_gate_get(s->c, &s->core.zncc, zncc_t, nullptr, cap, n);
 }
 
 extern "C" int vo_mvo_prefetch(vo_mvo *s, const void *img, int stride, int on_device) {
@@ -1144,8 +1159,10 @@ extern "C" int vo_mvo_enqueue(vo_mvo *s, const void *img, int stride, int on_dev
     int rc = vo_mono_frame_set_track_flags(c, s->core.keyframes.size() > 5 ? 2 : 1);
     if (rc >= 0 && deferred) rc = vo_frame_set_deferred_detection(c, deferred == 2 ? 1 : 0);
     if (rc < 0) return undo(rc);
+    c->zncc_gate = s->core.zncc.pairs ? &s->core.zncc : nullptr;  // (the frame operator launches the gate's kernel in front of its BA launch)
     rc = vo_mono_frame_enqueue_closed(c, &s->prm.frame, s->slot[0], s->slot[1], t.t.pts_l, t.t.Xw, t.t.flags, s->n, Tcw_prev, Tcw_prior,
                                       s->dT01, &s->prm.bins, s->tab_cur, 1);
+    c->zncc_gate = nullptr;
     if (rc < 0) return undo(rc);
   }
   s->frame_id = c->next_frame_id;  // Frame(cam, timestamp): id = frame_counter_++ (frame.cpp:22-41)
@@ -1255,7 +1272,9 @@ extern "C" int vo_mvo_result(vo_mvo *s, vo_mvo_frame_info *info) {
       }
       c->frame->known_done = true;  // (the word just seen is the last store of the frame's last launch)
     }
+    c->zncc_gate = s->core.zncc.pairs ? &s->core.zncc : nullptr;  // (a frame that is issued again computes its gate again)
     rc = vo_mono_frame_result(c, nullptr, nullptr, nullptr, dT01, &I.counts, &I.gn);
+    c->zncc_gate = nullptr;
     if (rc < 0) return rc;
     vo_frame_state *f = c->frame;
     const vo_frame_hdr *fh = (const vo_frame_hdr *)f->res_host;

@@ -276,6 +276,7 @@ extern "C" void vo_svo_destroy(vo_svo *s) {
   vo_pose_cov_state_free(&s->cov);
   if (s->c && !s->mono) vo_driver_mask_release_slots(s->c, s->slot, 5);  // (operator calls on these slots no longer see this driver's mask)
   vo_driver_mask_free(&s->mask);
+  vo_zncc_gate_free(&s->zncc);
   vo_svo_lba_free(s);
   delete s;
 }
@@ -335,6 +336,19 @@ extern "C" int vo_svo_set_mask(vo_svo *s, const void *mask, int stride, int on_d
   if (!s) return VO_ERR_INVALID;
   const int left[3] = {s->slot[S_P], s->slot[S_CL], s->slot[S_NL]};  // (the three slots left images rotate through)
   return vo_driver_mask_set(s->c, &s->mask, left, 3, mask, stride, on_device, s->prm.frame.width, s->prm.frame.height);
+}
+
+// The ZNCC gate (include/vo_hip.h, "ZNCC"): the state only — vo_frame_enqueue_impl launches, the BA launch's epilogue gates.
+extern "C" int vo_svo_set_zncc_gate(vo_svo *s, int pairs, int win, int pattern, float thres) {
+  if (!s) return VO_ERR_INVALID;
+  if (s->pending) VO_FAIL(s->c, VO_ERR_INVALID, "vo_svo_set_zncc_gate: a frame is in flight: call vo_svo_result first");
+  return vo_zncc_gate_set(s->c, &s->zncc, pairs, win, pattern, thres, true, s->cap);
+}
+
+extern "C" int vo_svo_get_zncc(vo_svo *s, float *zncc_t, float *zncc_s, int cap, int *n) {
+  if (!s || !n) return VO_ERR_INVALID;
+  if (s->pending) VO_FAIL(s->c, VO_ERR_INVALID, "call vo_svo_result first");
+  return vo_zncc_gate_get(s->c, &s->zncc, zncc_t, zncc_s, cap, n);
 }
 
 extern "C" int vo_svo_prefetch(vo_svo *s, const void *left, const void *right, int stride, int on_device) {
@@ -542,8 +556,10 @@ extern "C" int vo_svo_enqueue(vo_svo *s, const void *left, const void *right, in
     if (rc >= 0 && deferred) rc = vo_frame_set_deferred_detection(c, issued ? 1 : 0);
     if (rc < 0) return undo(rc);
   }
+  c->zncc_gate = s->zncc.pairs ? &s->zncc : nullptr;  // (the frame operator launches the gate's kernel in front of its BA launch)
   int rc = vo_frame_enqueue_impl(c, &s->prm.frame, s->slot[S_P], s->slot[S_CL], s->slot[S_CR], t.pts_l, t.pts_r, t.Xw, t.flags,
                                  s->n, s->dT01, nullptr, 0, 1, &s->prm.bins, s->tab_cur, T_pw, T_cw_prior);
+  c->zncc_gate = nullptr;
   if (rc < 0) return undo(rc);
   s->pending = true;
   s->pending_first = false;
@@ -660,7 +676,9 @@ extern "C" int vo_svo_result(vo_svo *s, vo_svo_frame_info *info) {
   // the BA launch's epilogue wrote the loop's counts (pinned block) in front of the frame's sequence word
   float dT[16];
   const double t_in = g_trace ? svo_now() : 0.0;
+  c->zncc_gate = s->zncc.pairs ? &s->zncc : nullptr;  // (a frame that is issued again computes its gate again)
   int rc = vo_stereo_frame_result(c, nullptr, nullptr, nullptr, dT, nullptr, nullptr, &I.counts, &I.gn);
+  c->zncc_gate = nullptr;
   if (rc < 0) return rc;
   const double t_seen = g_trace ? svo_now() : 0.0;
 #ifdef GN_STAMP  // measurement build: phases of the BA launch in the loop (10 ns ticks), averaged under VO_SVO_TRACE

@@ -53,6 +53,7 @@ struct vo_svo {
   // launch, in stream order
   VoPoseCovState cov;
   vo_driver_mask mask;  // vo_svo_set_mask (MonoVO: vo_mvo_set_mask): the ignore mask the pairs ingested from now on carry
+  vo_zncc_gate zncc;    // vo_svo_set_zncc_gate (MonoVO: vo_mvo_set_zncc_gate): the appearance gate of the steady-state frames
   int mono = 0;  // the keyframe storage serves a MonoVO (mono_vo.hip): one observation per keyframe entry, bundled flags
   // all_stkeyframes_ (stats_keyframe): every keyframe's current pose (host) and where its related landmarks' ids are kept
   // on the device (a pool that only grows)

@@ -125,6 +125,8 @@ struct vo_ctx {
   int eq_mode, eq_tiles_x, eq_tiles_y;
   double eq_clip;
   uint8_t *eq_op;  // vo_equalize_image's own storage: a staging plane in front of what a slot has
+  // the ZNCC gate of the driver whose frame is in flight (zncc.hip); null: none — the frame operators then launch nothing
+  struct vo_zncc_gate *zncc_gate;
 };
 
 static inline hipError_t vo_dev_malloc(vo_ctx *c, void **p, size_t bytes) {
@@ -220,6 +222,23 @@ int vo_driver_mask_bind(vo_ctx *c, const vo_driver_mask *m, int slot, int w, int
 void vo_driver_mask_free(vo_driver_mask *m);
 // a driver takes or gives up its image slots: none of them carries a mask any longer (the planes stay allocated)
 void vo_driver_mask_release_slots(vo_ctx *c, const int *slots, int n_slots);
+
+// The ZNCC gate of a driver (vo_svo_set_zncc_gate / vo_mvo_set_zncc_gate; zncc.hip). The driver points vo_ctx::zncc_gate at its
+// own state for the time its frame is in flight (enqueue .. result): the frame operators launch the kernel in front of the BA
+// launch and hand the BA launch the view. pairs == 0: off.
+struct vo_zncc_gate {
+  int pairs = 0, win = 15, pattern = 0;
+  float thres = 0.0f;
+  float *d = nullptr;  // [2][cap] floats: temporal values, stereo values — the option's only allocation, at the first enable
+  int cap = 0;
+  int last_n = 0, last_pairs = 0;  // the last frame the kernel ran for: its input count and pairs
+};
+int vo_zncc_gate_set(vo_ctx *c, vo_zncc_gate *g, int pairs, int win, int pattern, float thres, bool stereo, int cap);
+void vo_zncc_gate_free(vo_zncc_gate *g);
+int vo_zncc_gate_get(vo_ctx *c, const vo_zncc_gate *g, float *zncc_t, float *zncc_s, int cap, int *n);
+// the frame operators: the launch on c->stream (slot_r1 < 0 / pts_r1 == null: no stereo pair) and the BA launch's view
+int vo_zncc_gate_enqueue(vo_ctx *c, vo_zncc_gate *g, int slot_l0, int slot_l1, int slot_r1, const float *d_pts_l0, const float *d_pts_l1,
+                         const float *d_pts_r1, int n, vo_zncc_view *view);
 
 // Image ingestion (H2D + pyramid chain) enqueues on the side stream when vo_set_ingest_side_stream is on: launchers
 // use c->stream, which this scope points at the ingest stream and restores on exit.

@@ -33,6 +33,9 @@ struct vo_gn_frame {
   // stereo: the ignore mask of the current left image (p == null: none) — a feature is promoted to stage 4 only where the lookup
   // at its current left pixel is non-zero (the general form of the y > 660 gate). Mono: MonoGateArgs::ign.
   vo_mask_view ign;
+  // stereo: the ZNCC gate's values of this frame (vo_zncc_gate_enqueue; on == 0: none) — stage 4 also needs vo_zncc_pass at the
+  // feature's input index. Mono: MonoGateArgs::zn.
+  vo_zncc_view zn;
   // closed step [10] (stereo): updateWeightBin(lmtrack_final.pts_l1) + the emission of the bucketed candidates of the
   // bins left empty, from the speculative per-bin results of the frame kernel
   int np_bins;              // > 0: enabled; n_bins_u * n_bins_v

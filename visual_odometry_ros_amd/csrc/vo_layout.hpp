@@ -35,6 +35,18 @@ __host__ __device__ inline bool vo_mask_usable(const vo_mask_view &m, float x, f
   return m.p[(size_t)(int)fy * (size_t)m.stride + (size_t)(int)fx] != 0;
 }
 
+// The ZNCC gate of a frame (vo_svo_set_zncc_gate): the values the launch in front of the BA launch left, per input feature.
+// t: temporal pair, s: stereo pair; either may be null (both null: no gate — callers test `on` first, and without a gate
+// nothing of this runs). A feature passes where every value present is > thres; NaN fails.
+struct vo_zncc_view {
+  const float *t, *s;
+  float thres;
+  int on;
+};
+__host__ __device__ inline bool vo_zncc_pass(const vo_zncc_view &z, int i) {
+  return (!z.t || z.t[i] > z.thres) && (!z.s || z.s[i] > z.thres);
+}
+
 // i / d and i % d for 0 <= i * d < 2^32 by a multiplication (m = 2^32 / d rounded up): the tile kernels run over
 // rectangles of a few thousand elements whose width is only known at run time (a software division costs ~40 instructions)
 __host__ __device__ inline unsigned vo_magic(int d) { return d > 1 ? 0xFFFFFFFFu / (unsigned)d + 1u : 0u; }
