@@ -11,7 +11,9 @@ frame in flight). Output: the reference's trajectory format (`id` + the 12 numbe
 stereo_vo.cpp:62-80), one line per frame; optionally every keyframe's current pose after the last frame. --covariance FILE: the
 pose's covariance as a node would put it into nav_msgs::Odometry::pose.covariance (chained on the device behind every frame's
 pose-only BA), one line per frame: the id, the 36 values (row-major; x, y, z, rot x, rot y, rot z), `valid` and
-`n_unknown_steps` (frames whose pose did not come from the BA)."""
+`n_unknown_steps` (frames whose pose did not come from the BA). --semidense DIR [--semidense-every frame] [--semidense-depth Z_MIN
+[Z_MAX]]: semi-dense stereo depth of every keyframe's (every frame's) own pair, computed on the device behind the frame; one ASCII
+PLY per result in DIR (`semidense_<frame id>.ply`: x y z in the world frame and the standard deviation of the inverse depth)."""
 import argparse
 import os
 import sys
@@ -69,6 +71,31 @@ def zncc_options(args):
     return {"zncc_gate": {"thres": args.zncc, "win": win, "pattern": "centered", "pairs": ("temporal", "stereo") if args.zncc_stereo else ("temporal",)}}
 
 
+def semidense_options(args):
+    """--semidense DIR [--semidense-every frame] [--semidense-depth Z_MIN [Z_MAX]] as the `semidense` argument of from_yaml: semi-dense
+    stereo depth of every keyframe's (or every frame's) pair; bf comes from the configured camera"""
+    if args.semidense is None:
+        if args.semidense_every is not None or args.semidense_depth is not None:
+            raise SystemExit("--semidense-every / --semidense-depth need --semidense DIR")
+        return {}
+    z = args.semidense_depth or [3.0]
+    if len(z) > 2 or not (z[0] > 0 and (len(z) == 1 or z[1] >= z[0])):
+        raise SystemExit("--semidense-depth: Z_MIN [Z_MAX] in metres, 0 < Z_MIN <= Z_MAX")
+    sd = {"z_min": z[0], "every": args.semidense_every or "keyframe"}
+    if len(z) == 2:
+        sd["z_max"] = z[1]
+    return {"semidense": sd}
+
+
+def write_ply(path, xyz, sigma_invd):
+    """one ASCII PLY: x y z and the standard deviation of the inverse depth per point"""
+    with open(path, "w") as f:
+        f.write("ply\nformat ascii 1.0\n" + f"element vertex {len(xyz)}\n" +
+                "property float x\nproperty float y\nproperty float z\nproperty float sigma_invd\nend_header\n")
+        for (x, y, z), s in zip(xyz, sigma_invd):
+            f.write(f"{x:.6g} {y:.6g} {z:.6g} {s:.6g}\n")
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", required=True, help="a config/stereo/*.yaml file of the reference")
@@ -94,6 +121,11 @@ def parse_args(argv=None):
                     help="appearance gate: a track survives only where the ZNCC of its patches in the previous and the current image exceeds THRES")
     ap.add_argument("--zncc-win", type=int, default=None, metavar="N", help="patch size of --zncc (odd, 3..31; default 15)")
     ap.add_argument("--zncc-stereo", action="store_true", help="--zncc also between the current left and right image")
+    ap.add_argument("--semidense", default=None, metavar="DIR",
+                    help="semi-dense stereo depth of every keyframe's pair: one ASCII PLY per result (world frame) into DIR")
+    ap.add_argument("--semidense-every", choices=("keyframe", "frame"), default=None, help="a result per keyframe (default) or per frame")
+    ap.add_argument("--semidense-depth", nargs="+", type=float, default=None, metavar="Z",
+                    help="depth range Z_MIN [Z_MAX] in metres searched by --semidense (default 3, no upper end)")
     return ap.parse_args(argv)
 
 
@@ -108,7 +140,10 @@ def main():
         raise SystemExit("no image pairs found")
     svo = V.StereoVO.from_yaml(args.config, device=args.device, strict_border=args.strict_border, local_ba=not args.no_local_ba,
                                pose_covariance=bool(args.covariance), **mask_options(args), **clahe_options(args),
-                               **zncc_options(args))
+                               **zncc_options(args), **semidense_options(args))
+    if args.semidense:
+        os.makedirs(args.semidense, exist_ok=True)
+    sd_last = -1
     cov_file = open(args.covariance, "w") if args.covariance else None
     svo.ctx.sum_order = args.sum_order
     pair = lambda k: (load_grey(os.path.join(args.left, names_l[k])), load_grey(os.path.join(args.right, names_r[k])))  # noqa: E731
@@ -128,6 +163,12 @@ def main():
             cov = svo.getPoseCovariance()
             ros = V.pose_covariance_ros(cov.P, poses[-1])
             cov_file.write(f"{info.frame_id} " + " ".join(f"{v:.9e}" for v in ros) + f" {int(cov.valid)} {cov.n_unknown_steps}\n")
+        if args.semidense and (info.is_keyframe or args.semidense_every == "frame"):
+            # (fetched here for simplicity: this waits for the result's launch; a caller that wants it hidden fetches a frame later)
+            pts = svo.getSemiDensePoints(world=True)
+            if pts is not None and pts["frame_id"] != sd_last:
+                sd_last = pts["frame_id"]
+                write_ply(os.path.join(args.semidense, f"semidense_{sd_last:06d}.ply"), pts["xyz"], pts["sigma_invd"])
         if k % 100 == 0 or k == n - 1:
             t = poses[-1][:3, 3]
             print(f"frame {k:6d}: {info.n_tracks_out:5d} tracks, {n_kf:4d} keyframes, position ({t[0]:9.3f} {t[1]:9.3f} {t[2]:9.3f})", flush=True)

@@ -738,6 +738,71 @@ int vo_svo_set_zncc_gate(vo_svo *svo, int pairs, int win, int pattern, float thr
 int vo_svo_get_zncc(vo_svo *svo, float *zncc_t, float *zncc_s, int cap, int *n);
 /* (MonoVO: vo_mvo_set_zncc_gate / vo_mvo_get_zncc, below) */
 
+/* ---- Semi-dense stereo: depth of the high-gradient pixels by an epipolar ZNCC search -----------------------
+ * The static stereo part of the reference author's semi-dense prototype, as an operator on a rectified pair (epipolar lines
+ * are rows) and as an option of StereoVO. Inputs: the level-0 u8 planes L, R of two slots of one size W x H, the left slot's
+ * ignore mask where one is bound, and vo_semidense_params. All taps sit at integer pixels: the window sums are exact integers
+ * and no summation order enters the result.
+ *   params     hw 1..15, hh 0..3: the window is (2 hw + 1) x (2 hh + 1), n taps; 0 <= d_min <= d_max <= 1023; g_min 1..360;
+ *              thres_best, thres_peak; peak_px, edge_px >= 0; eps_edge, eps_epi >= 0; bf = focal length x baseline [pixel m] > 0.
+ *   candidate  (x, y) with m_x <= x <= W-1-m_x, m_y <= y <= H-1-m_y (m_x = max(hw, 1), m_y = max(hh, 1)); with the integers
+ *              gx = L(x+1,y) - L(x-1,y), gy = L(x,y+1) - L(x,y-1): gx^2 + gy^2 >= g_min^2 and 3 gx^2 >= gy^2 (the gradient lies
+ *              within 60 degrees of the epipolar line); not masked (mask byte != 0).
+ *   scores     for d = d_min .. d_last = min(d_max, x - hw), over |k| <= hw, |v| <= hh with l = L(x+k, y+v), r = R(x-d+k, y+v):
+ *              S_l, S_ll, S_r, S_rr, S_lr; A = n S_ll - S_l^2, B = n S_rr - S_r^2, num = n S_lr - S_l S_r as exact (64-bit)
+ *              integers; s(d) = -1 where A == 0 or B == 0, else (float)num / sqrtf((float)A * (float)B), every operation
+ *              rounded to float on its own (no FMA).
+ *   status     in this order: 0 no candidate; 5 fewer than 2 edge_px + 3 disparities in the range, or A == 0; with d_best the
+ *              disparity of the largest s (ties: the smallest d): 2 s(d_best) <= thres_best; 3 some d with s(d) > thres_peak has
+ *              |d - d_best| > peak_px; 4 not (d_min + edge_px < d_best < d_last - edge_px); 1 accepted.
+ *   accepted   s0 = s(d_best), sm = s(d_best - 1), sp = s(d_best + 1); den = (sm + sp) - (s0 + s0);
+ *              off = den != 0 ? (0.5f * (sm - sp)) / den : 0; disparity = (float)d_best + off;
+ *              g = sqrtf((float)(gx^2 + gy^2)); du = (float)gx / g; dv = (float)gy / g; e = eps_epi * dv;
+ *              sigma_invd = (sqrtf(eps_edge * eps_edge + e * e) / fabsf(du)) / bf — in this order, each operation rounded.
+ *   outputs    four W x H planes, tightly packed: disparity f32 (0 where status != 1), score f32 (s(d_best) for status 1..4,
+ *              else 0), sigma_invd f32 (standard deviation of the inverse depth; 0 where status != 1), status u8.
+ * vo_semidense_stereo: any output may be NULL; on_device: the outputs are device memory. Synchronous.
+ * vo_semidense_points: the accepted pixels of such planes (host, or device with planes_on_device) in raster order, by the
+ * library's stable compaction: z = bf / disparity, X = (((float)x - cx) / fx * z, ((float)y - cy) / fy * z, z) with K = fx, fy,
+ * cx, cy; with T (row-major 4 x 4, may be NULL) X' [r] = (T[r][0] X + (T[r][1] Y + T[r][2] Z)) + T[r][3]. Host outputs xyz [cap][3],
+ * sigma_out [cap] (may be NULL), pixel [cap][2] (x, y; may be NULL); *n = the true count, also with VO_ERR_CAPACITY (n > cap: the
+ * first cap entries are written). The planes may not exceed vo_config.max_width x max_height.
+ *
+ * StereoVO (off by default; with it off no launch, wait, allocation or result bit differs; with it on the odometry's results
+ * are the same bits): vo_svo_set_semidense(svo, prm, every) — prm NULL = off — makes the option's only allocations at the first
+ * enable. every = VO_SEMIDENSE_KEYFRAMES: a result per keyframe; VO_SEMIDENSE_FRAMES: per frame (the first pair included). The
+ * launch for a frame is enqueued by vo_svo_result, where the keyframe decision and the pose after the local BA are known, on the
+ * side stream behind a fork event of the main stream; it reads the frame's own left and right slots; vo_svo_result never waits
+ * for it. A later ingestion into a slot the launch reads is ordered behind the launch's event on the device. A frame that
+ * produces no result leaves the previous one in place. vo_svo_get_semidense: the last result's planes (any may be NULL), size,
+ * frame_id (-1 and 0 x 0 before any), T_wc and the number of accepted pixels; waits for that launch's event only.
+ * vo_svo_get_semidense_points: vo_semidense_points of the last result with the left camera's K, in the world frame (world != 0:
+ * T = the frame's T_wc) or the camera frame. All three: VO_ERR_INVALID while a frame is in flight; the getters also with the
+ * option off. Not for MonoVO or vo_batch streams. */
+typedef struct {
+  int hw, hh;          /* 8, 1 */
+  int d_min, d_max;    /* 0, 64 */
+  int g_min;           /* 20 */
+  float thres_best;    /* 0.95 */
+  float thres_peak;    /* 0.9 */
+  int peak_px;         /* 5 */
+  int edge_px;         /* 2 */
+  float eps_edge;      /* 0.5 */
+  float eps_epi;       /* 1.0 */
+  float bf;            /* 1.0: set it */
+} vo_semidense_params;
+enum { VO_SEMIDENSE_KEYFRAMES = 0, VO_SEMIDENSE_FRAMES = 1 };
+int vo_semidense_default_params(vo_semidense_params *prm);
+int vo_semidense_stereo(vo_ctx *ctx, int slot_l, int slot_r, const vo_semidense_params *prm, float *disparity, float *score,
+                        float *sigma_invd, uint8_t *status, int on_device);
+int vo_semidense_points(vo_ctx *ctx, const float *disparity, const float *sigma_invd, const uint8_t *status, int width, int height,
+                        int planes_on_device, const float K[4], float bf, const float *T, int cap, float *xyz, float *sigma_out,
+                        uint16_t *pixel, int *n);
+int vo_svo_set_semidense(vo_svo *svo, const vo_semidense_params *prm, int every);
+int vo_svo_get_semidense(vo_svo *svo, float *disparity, float *score, float *sigma_invd, uint8_t *status, int *width, int *height,
+                         int *frame_id, float T_wc[16], int *n_accepted);
+int vo_svo_get_semidense_points(vo_svo *svo, int world, int cap, float *xyz, float *sigma_invd, uint16_t *pixel, int *n, int *frame_id);
+
 /* ---- undistortion / stereo rectification in front of the trackers ----------
  * core/visual_odometry/camera.cpp. A context holds the maps of two cameras
  * (cam 0 = left or the mono camera, cam 1 = right), device-resident. */

@@ -102,6 +102,12 @@ class MvoFrameInfo(C.Structure):
                 ("lba_err_last", C.c_double), ("lba_landmarks", C.c_int), ("lba_observations", C.c_int)]
 
 
+class SemiDenseParams(C.Structure):  # vo_semidense_params
+    _fields_ = [("hw", C.c_int), ("hh", C.c_int), ("d_min", C.c_int), ("d_max", C.c_int), ("g_min", C.c_int), ("thres_best", C.c_float),
+                ("thres_peak", C.c_float), ("peak_px", C.c_int), ("edge_px", C.c_int), ("eps_edge", C.c_float), ("eps_epi", C.c_float),
+                ("bf", C.c_float)]
+
+
 class FivePointParams(C.Structure):
     _fields_ = [("thres_px", C.c_float), ("confidence", C.c_float), ("max_iters", C.c_int), ("seed", C.c_ulonglong)]
 
@@ -148,6 +154,8 @@ SYMBOLS = [
     "vo_set_slot_mask", "vo_slot_image_size", "vo_svo_set_mask", "vo_mvo_set_mask", "vo_rectify_validity_mask",
     "vo_set_equalize", "vo_get_equalize", "vo_equalize_image",
     "vo_zncc", "vo_svo_set_zncc_gate", "vo_svo_get_zncc", "vo_mvo_set_zncc_gate", "vo_mvo_get_zncc",
+    "vo_semidense_default_params", "vo_semidense_stereo", "vo_semidense_points",
+    "vo_svo_set_semidense", "vo_svo_get_semidense", "vo_svo_get_semidense_points",
 ]
 
 _lib = None
@@ -247,6 +255,12 @@ def load():
     lib.vo_svo_get_zncc.argtypes = [vp, vp, vp, ci, vp]
     lib.vo_mvo_set_zncc_gate.argtypes = [vp, ci, ci, ci, C.c_float]
     lib.vo_mvo_get_zncc.argtypes = [vp, vp, ci, vp]
+    lib.vo_semidense_default_params.argtypes = [vp]
+    lib.vo_semidense_stereo.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, ci]
+    lib.vo_semidense_points.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, C.c_float, vp, ci, vp, vp, vp, vp]
+    lib.vo_svo_set_semidense.argtypes = [vp, vp, ci]
+    lib.vo_svo_get_semidense.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.vo_svo_get_semidense_points.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp]
     lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_five_point_destroy.argtypes = [vp]
     lib.vo_five_point_destroy.restype = None

@@ -78,6 +78,42 @@ def _equalize_arg(equalize):
     raise ValueError(f'equalize must be None, "clahe" or dict(clip_limit=, tiles=), not {equalize!r}')
 
 
+class SemiDenseResult(collections.namedtuple("SemiDenseResult", "disparity score sigma_invd status frame_id T_wc n_accepted")):
+    """The planes of a semi-dense stereo result (include/vo_hip.h, "Semi-dense stereo"): disparity, score, sigma_invd float32
+    (height, width), status uint8; from a driver also the frame's id, its T_wc and the number of accepted pixels (status 1)."""
+    __slots__ = ()
+
+    @property
+    def accepted(self):
+        return self.status == 1
+
+
+def semidense_disparity_range(bf, z_min, z_max=float("inf")):
+    """(d_min, d_max) of a depth range [z_min, z_max] in metres with bf = focal length x baseline: floor(bf / z_max), ceil(bf / z_min)"""
+    import math
+    if not (bf > 0 and z_min > 0 and z_max >= z_min):
+        raise ValueError("semidense_disparity_range: bf > 0 and 0 < z_min <= z_max")
+    return (0 if math.isinf(z_max) else int(math.floor(bf / z_max))), int(math.ceil(bf / z_min))
+
+
+def _semidense_params(lib, params):
+    """keyword parameters -> vo_semidense_params: the C defaults, then the caller's fields; z_min / z_max (with bf) give d_min / d_max"""
+    p = _capi.SemiDenseParams()
+    lib.vo_semidense_default_params(C.byref(p))
+    params = dict(params)
+    z_min, z_max = params.pop("z_min", None), params.pop("z_max", None)
+    known = {f[0] for f in _capi.SemiDenseParams._fields_}
+    for k, v in params.items():
+        if k not in known:
+            raise ValueError(f"semi-dense: unknown parameter {k!r}; known: {sorted(known)} and z_min, z_max")
+        setattr(p, k, v)
+    if z_min is not None or z_max is not None:
+        if "d_min" in params or "d_max" in params or "bf" not in params or z_min is None:
+            raise ValueError("semi-dense: z_min (and z_max) need bf and replace d_min / d_max")
+        p.d_min, p.d_max = semidense_disparity_range(float(params["bf"]), float(z_min), float("inf") if z_max is None else float(z_max))
+    return p
+
+
 def _zncc_gate_arg(gate, stereo):
     """zncc_gate= / setZnccGate: None -> off; dict(thres=, win=15, pattern="centered", pairs=("temporal",)) -> the C call's
     (pairs, win, pattern, thres). pairs: names out of "temporal", "stereo" (StereoVO only)."""
@@ -242,6 +278,57 @@ class Context:
         self.check(self.lib.vo_zncc(self._h, int(slot0), int(slot1), p0.ctypes.data, p1.ctypes.data, len(p0), int(win),
                                     self.ZNCC_PATTERNS[pattern], out.ctypes.data))
         return out
+
+    # ---- semi-dense stereo depth (include/vo_hip.h, "Semi-dense stereo") --------------------------------------------------------
+    def semiDenseStereo(self, slot_l, slot_r, out=None, **params):
+        """Semi-dense depth of the rectified pair in slot_l / slot_r (level 0; the left slot's ignore mask applies): a
+        SemiDenseResult of (height, width) planes. params: the fields of vo_semidense_params (hw, hh, d_min, d_max, g_min,
+        thres_best, thres_peak, peak_px, edge_px, eps_edge, eps_epi, bf), or z_min / z_max [m] with bf in place of d_min / d_max.
+        out: dict(disparity=, score=, sigma_invd=, status=) of DEVICE addresses (any may be missing) — the planes are then written
+        there, tightly packed, and None is returned."""
+        p = _semidense_params(self.lib, params)
+        if out is not None:
+            ptr = [C.c_void_p(out.get(k)) if out.get(k) else None for k in ("disparity", "score", "sigma_invd", "status")]
+            self.check(self.lib.vo_semidense_stereo(self._h, int(slot_l), int(slot_r), C.byref(p), *ptr, 1))
+            return None
+        w, h = self.slot_image_size(slot_l)
+        if w <= 0:
+            raise VoError(-1, f"slot {slot_l} holds no image")
+        d, sc, sg = (np.zeros((h, w), np.float32) for _ in range(3))
+        st = np.zeros((h, w), np.uint8)
+        self.check(self.lib.vo_semidense_stereo(self._h, int(slot_l), int(slot_r), C.byref(p), d.ctypes.data, sc.ctypes.data, sg.ctypes.data,
+                                                st.ctypes.data, 0))
+        return SemiDenseResult(d, sc, sg, st, None, None, int((st == 1).sum()))
+
+    def semiDensePoints(self, disparity, sigma_invd, status, K, bf, T=None, capacity=None, on_device=None):
+        """The accepted pixels of semi-dense planes in raster order: (xyz float32 [n, 3], sigma_invd float32 [n], pixel uint16
+        [n, 2]) with z = bf / disparity, K = (fx, fy, cx, cy) and, with T (4 x 4), in T's target frame. The planes are arrays, or
+        DEVICE addresses with on_device=(width, height). capacity: room for that many points (default: every pixel); more accepted
+        pixels raise VoError(VO_ERR_CAPACITY) whose `n` attribute holds the true count."""
+        if on_device is not None:
+            w, h = on_device
+            pd, ps, pt = C.c_void_p(disparity), C.c_void_p(sigma_invd), C.c_void_p(status)
+        else:
+            d = np.ascontiguousarray(disparity, np.float32)
+            sg = np.ascontiguousarray(sigma_invd, np.float32)
+            st = np.ascontiguousarray(status, np.uint8)
+            if d.ndim != 2 or sg.shape != d.shape or st.shape != d.shape:
+                raise ValueError("disparity, sigma_invd and status are planes of one (height, width)")
+            h, w = d.shape
+            pd, ps, pt = d.ctypes.data, sg.ctypes.data, st.ctypes.data
+        cap = w * h if capacity is None else int(capacity)
+        Ka = np.ascontiguousarray(K, np.float32).reshape(4)
+        Ta = None if T is None else np.ascontiguousarray(T, np.float32).reshape(4, 4)
+        xyz, so, px = np.zeros((max(cap, 1), 3), np.float32), np.zeros(max(cap, 1), np.float32), np.zeros((max(cap, 1), 2), np.uint16)
+        n = C.c_int()
+        rc = self.lib.vo_semidense_points(self._h, pd, ps, pt, w, h, int(on_device is not None), Ka.ctypes.data, float(bf),
+                                          None if Ta is None else Ta.ctypes.data, cap, xyz.ctypes.data, so.ctypes.data, px.ctypes.data, C.byref(n))
+        try:
+            self.check(rc)
+        except VoError as e:
+            e.n = n.value
+            raise
+        return xyz[:n.value], so[:n.value], px[:n.value]
 
     def set_image_device(self, slot, dev_ptr, width, height, stride):
         self.check(self.lib.vo_set_image_device(self._h, slot, C.c_void_p(dev_ptr), width, height, stride))
@@ -1138,8 +1225,9 @@ class StereoVO:
     def __init__(self, ctx, width, height, Kl, Kr, T_lr, n_bins_u, n_bins_v, thres_fastscore=15, window_size=21, max_level=6,
                  thres_error=80.0, thres_bidirection=0.5, thres_poseba_error=3.0, thres_alive_ratio=0.6, thres_rotation=15.0,
                  thres_trans=10.0, n_max_keyframes_in_window=9, strict_border=4, local_ba=True, rectify=False, thres_sampson=60.0,
-                 debug_image=False, pose_covariance=False, sigma_px=0.0, mask=None, zncc_gate=None):
+                 debug_image=False, pose_covariance=False, sigma_px=0.0, mask=None, zncc_gate=None, semidense=None):
         """debug_image=True: every tracked frame draws the reference's img_debug_ on the device (getDebugImage).
+        semidense: dict of semi-dense stereo parameters (setSemiDense; "every": "keyframe" or "frame") — depth of the keyframes' pairs.
         mask: the ignore mask every pair carries from the first one on (setMask).
         zncc_gate: dict(thres=, win=15, pattern="centered", pairs=("temporal",)) — the appearance gate (setZnccGate).
         pose_covariance=True: every frame chains the covariance of its pose on the device (getPoseCovariance); sigma_px > 0
@@ -1169,12 +1257,15 @@ class StereoVO:
             self.setMask(mask)
         if zncc_gate is not None:
             self.setZnccGate(zncc_gate)
+        if semidense is not None:
+            sd = dict(semidense)
+            self.setSemiDense(sd, every=sd.pop("every", "keyframe"))
         self._info = SvoFrameInfo()
         self.stats_frame = []  # AlgorithmStatistics::FrameStatistics::Twc per frame (stereo_vo.cpp:979-980)
 
     @classmethod
     def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", mask=None, mask_erode=0, equalize=None, zncc_gate=None,
-                  **overrides):
+                  semidense=None, **overrides):
         """StereoVO(mode = "rosbag", directory_intrinsic = path) of the reference (stereo_vo.cpp:15-57, :118-280): the
         object configured by one of its config/stereo/*.yaml files. The context is created here (sized by the file) and
         closed with the object. With flagDoUndistortion the pairs go through the rectification maps and the loop runs on
@@ -1186,7 +1277,8 @@ class StereoVO:
         `mask`: an ignore mask (setMask), or "rectified": the left camera's validity mask (StereoCamera.validityMask(mask_erode):
         what cv::remap fills with 0 is not looked at), which needs flagDoUndistortion in the file.
         `equalize`: None, "clahe" (OpenCV's defaults) or dict(clip_limit=, tiles=): Context.set_equalize on the new context.
-        `zncc_gate`: the constructor's (setZnccGate)."""
+        `zncc_gate`: the constructor's (setZnccGate). `semidense`: the constructor's (setSemiDense); without "bf" the (rectified)
+        camera's focal length x baseline is filled in."""
         from . import config as _config
         cfg = _config.load_stereo_config(path)
         eq = _equalize_arg(equalize)
@@ -1213,6 +1305,10 @@ class StereoVO:
                 T_lr, rectify = cam.getRectifiedStereoPoseLeft2Right(), True
                 if isinstance(mask, str):
                     mask = cam.validityMask(mask_erode)
+            if semidense is not None:
+                semidense = dict(semidense)
+                semidense.setdefault("bf", float(np.asarray(Kl, np.float64).reshape(-1)[0] * np.linalg.norm(np.asarray(T_lr, np.float64).reshape(4, 4)[:3, 3])))
+                overrides = dict(overrides, semidense=semidense)
             obj = cls(ctx, W, H, Kl, Kr, T_lr, fe["n_bins_u"], fe["n_bins_v"], thres_fastscore=fe["thres_fastscore"],
                       window_size=ft["window_size"], max_level=ft["max_level"], thres_error=ft["thres_error"],
                       thres_sampson=ft["thres_sampson"],
@@ -1272,6 +1368,58 @@ class StereoVO:
         t, s = np.full(n.value, np.nan, np.float32), np.full(n.value, np.nan, np.float32)
         self.ctx.check(self.lib.vo_svo_get_zncc(self._h, t.ctypes.data, s.ctypes.data, n.value, C.byref(n)))
         return {"temporal": t if self._zncc_pairs & 1 else None, "stereo": s if self._zncc_pairs & 2 else None}
+
+    SEMIDENSE_EVERY = {"keyframe": 0, "frame": 1}  # VO_SEMIDENSE_*
+
+    def setSemiDense(self, params, every="keyframe"):
+        """Semi-dense stereo depth (include/vo_hip.h, "Semi-dense stereo") of every keyframe's — every="frame": every frame's —
+        own rectified pair, computed on the side stream behind the frame; the odometry's results do not change. params: dict of
+        Context.semiDenseStereo's parameters (bf is needed), None: off. Refused while a frame is in flight. StereoVO only."""
+        if params is None:
+            self.ctx.check(self.lib.vo_svo_set_semidense(self._h, None, 0))
+            return
+        if every not in self.SEMIDENSE_EVERY:
+            raise ValueError(f"every must be one of {sorted(self.SEMIDENSE_EVERY)}, not {every!r}")
+        if "bf" not in params:
+            raise ValueError("setSemiDense: bf (focal length x baseline) is needed")
+        p = _semidense_params(self.lib, params)
+        self.ctx.check(self.lib.vo_svo_set_semidense(self._h, C.byref(p), self.SEMIDENSE_EVERY[every]))
+
+    def getSemiDense(self):
+        """The last semi-dense result (a SemiDenseResult with frame_id, T_wc (4, 4) and n_accepted), None before any. Waits for
+        that result's launch only."""
+        w, h, fid, na = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        T = np.zeros((4, 4), np.float32)
+        self.ctx.check(self.lib.vo_svo_get_semidense(self._h, None, None, None, None, C.byref(w), C.byref(h), C.byref(fid), None, None))
+        if w.value <= 0:
+            return None
+        d, sc, sg = (np.zeros((h.value, w.value), np.float32) for _ in range(3))
+        st = np.zeros((h.value, w.value), np.uint8)
+        self.ctx.check(self.lib.vo_svo_get_semidense(self._h, d.ctypes.data, sc.ctypes.data, sg.ctypes.data, st.ctypes.data, C.byref(w), C.byref(h),
+                                                     C.byref(fid), T.ctypes.data, C.byref(na)))
+        return SemiDenseResult(d, sc, sg, st, fid.value, T, na.value)
+
+    def getSemiDensePoints(self, world=True, capacity=None):
+        """The accepted pixels of the last semi-dense result as points, raster order: dict(xyz float32 [n, 3] — in the world frame
+        (the frame's T_wc) or, world=False, the left camera's —, sigma_invd [n], pixel uint16 [n, 2], frame_id); None before any.
+        capacity: room for that many points (default: all); more raise VoError(VO_ERR_CAPACITY) whose `n` holds the true count."""
+        n, fid = C.c_int(), C.c_int()
+        rc = self.lib.vo_svo_get_semidense_points(self._h, int(bool(world)), 0, None, None, None, C.byref(n), C.byref(fid))
+        if rc < 0 and rc != -8:  # (VO_ERR_CAPACITY: the count is what was asked for)
+            self.ctx.check(rc)
+        if fid.value < 0:
+            return None
+        cap = n.value if capacity is None else int(capacity)
+        xyz, sg, px = np.zeros((max(cap, 1), 3), np.float32), np.zeros(max(cap, 1), np.float32), np.zeros((max(cap, 1), 2), np.uint16)
+        rc = self.lib.vo_svo_get_semidense_points(self._h, int(bool(world)), cap, xyz.ctypes.data, sg.ctypes.data, px.ctypes.data,
+                                                  C.byref(n), C.byref(fid))
+        try:
+            self.ctx.check(rc)
+        except VoError as e:  # (VO_ERR_CAPACITY: `n` holds the true count)
+            e.n = n.value
+            raise
+        m = min(n.value, cap)
+        return dict(xyz=xyz[:m], sigma_invd=sg[:m], pixel=px[:m], frame_id=fid.value)
 
     def _img(self, a):
         """a host image as the library reads it: a u8 plane, or — with rectify=True — an array of the context's input format"""

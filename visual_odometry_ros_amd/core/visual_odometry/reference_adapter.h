@@ -469,6 +469,16 @@ class StereoVO {
   void setZnccGate(int pairs, float thres = 0.5f, int win = 15, int pattern = VO_ZNCC_PATTERN_CENTERED) {
     impl_.setZnccGate(pairs, thres, win, pattern);
   }
+  // NOT in the reference's StereoVO (its author's semi-dense stereo prototype, as an option: vo::StereoVO::setSemiDense): depth of
+  // the high-gradient pixels of every keyframe's pair; getSemiDensePoints() is what convertPointVecToPointCloud2 of the node takes
+  void setSemiDense(const vo_semidense_params *prm, int every = VO_SEMIDENSE_KEYFRAMES) { impl_.setSemiDense(prm, every); }
+  PointVec getSemiDensePoints(bool world = true) {
+    vo::PointVec v;
+    impl_.getSemiDensePoints(v, nullptr, world);
+    PointVec o(v.size());
+    for (size_t i = 0; i < v.size(); ++i) o[i] = Point(v[i].x, v[i].y, v[i].z);
+    return o;
+  }
   // NOT in the reference: CLAHE equalisation of every image before the tracker (vo::StereoVO::setEqualize; VO_EQ_CLAHE / VO_EQ_OFF)
   void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) { impl_.setEqualize(mode, clip_limit, tiles_x, tiles_y); }
   vo::StereoVO &device() { return impl_; }

@@ -237,6 +237,31 @@ class StereoVO {
   void setZnccGate(int pairs, float thres = 0.5f, int win = 15, int pattern = VO_ZNCC_PATTERN_CENTERED) {
     ctx_->check(vo_svo_set_zncc_gate(svo_, pairs, win, pattern, thres));
   }
+  // The static stereo part of the reference author's semi-dense prototype (vo_svo_set_semidense; include/vo_hip.h, "Semi-dense
+  // stereo"): depth of the high-gradient pixels of every keyframe's (every = VO_SEMIDENSE_FRAMES: every frame's) own rectified
+  // pair, on the side stream behind the frame; the odometry does not change. prm = nullptr: off. defaultSemiDenseParams(bf)
+  // fills in the defaults for a focal length x baseline. Throws while a frame is in flight.
+  static vo_semidense_params defaultSemiDenseParams(float bf, int d_max = 64) {
+    vo_semidense_params p;
+    vo_semidense_default_params(&p);
+    p.bf = bf;
+    p.d_max = d_max;
+    return p;
+  }
+  void setSemiDense(const vo_semidense_params *prm, int every = VO_SEMIDENSE_KEYFRAMES) { ctx_->check(vo_svo_set_semidense(svo_, prm, every)); }
+  // the accepted pixels of the last result as points in the world frame (its frame's T_wc) or the left camera's, raster order;
+  // waits for that result's launch only. false (and empty vectors) before the first result.
+  bool getSemiDensePoints(PointVec &xyz, std::vector<float> *sigma_invd = nullptr, bool world = true, int *frame_id = nullptr) {
+    int n = 0, fid = -1;
+    const int rc = vo_svo_get_semidense_points(svo_, world ? 1 : 0, 0, nullptr, nullptr, nullptr, &n, &fid);
+    if (rc != VO_ERR_CAPACITY) ctx_->check(rc);  // (room for none: the count is what was asked for)
+    xyz.resize((size_t)n);
+    if (sigma_invd) sigma_invd->resize((size_t)n);
+    if (frame_id) *frame_id = fid;
+    if (n) ctx_->check(vo_svo_get_semidense_points(svo_, world ? 1 : 0, n, reinterpret_cast<float *>(xyz.data()),
+                                                   sigma_invd ? sigma_invd->data() : nullptr, nullptr, &n, &fid));
+    return fid >= 0;
+  }
   // NOT in the reference: CLAHE on every image before the tracker (vo::Context::setEqualize on this driver's context): legal
   // between frames, applies to the images handed over from now on
   void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) { ctx_->setEqualize(mode, clip_limit, tiles_x, tiles_y); }

@@ -277,6 +277,7 @@ extern "C" void vo_svo_destroy(vo_svo *s) {
   if (s->c && !s->mono) vo_driver_mask_release_slots(s->c, s->slot, 5);  // (operator calls on these slots no longer see this driver's mask)
   vo_driver_mask_free(&s->mask);
   vo_zncc_gate_free(&s->zncc);
+  vo_svo_semidense_free(s);
   vo_svo_lba_free(s);
   delete s;
 }
@@ -356,6 +357,7 @@ extern "C" int vo_svo_prefetch(vo_svo *s, const void *left, const void *right, i
   const double t_in = g_trace ? svo_now() : 0.0;
   VO_CHECK_HIP(s->c, hipSetDevice(s->c->device));
   s->prefetched = false;  // (whatever was handed over before is overwritten from here on, also if this fails half-way)
+  RC(vo_svo_semidense_guard(s, s->slot[S_NL], s->slot[S_NR]));
   RC(svo_bind_mask(s));
   RC(svo_ingest(s, left, right, stride, on_device, true, true));
   if (g_trace) s->ht.acc[2] += svo_now() - t_in;
@@ -462,6 +464,7 @@ extern "C" int vo_svo_enqueue(vo_svo *s, const void *left, const void *right, in
     // a pair handed over early that is not this one: its candidates' launch may still read the slots this pair goes into, and
     // the synchronous call builds its pyramids on the MAIN stream — behind that launch, then (one event; nothing in the loop)
     RC(vo_frame_candidates_abandon(c, s->tab_next));
+    RC(vo_svo_semidense_guard(s, s->slot[S_NL], s->slot[S_NR]));
     RC(svo_bind_mask(s));
     deferred = !s->first && s->c->ingest_side;
     if (deferred && !s->prm.rectify && s->n > 0 && vo_orb_cand_table(c, s->tab_next)) {
@@ -671,6 +674,7 @@ extern "C" int vo_svo_result(vo_svo *s, vo_svo_frame_info *info) {
     for (int i = 0; i < 16; ++i) I.dT[i] = (i % 5 == 0) ? 1.0f : 0.0f;
     vo_pose_cov_state_accept(&s->cov);
     if (info) *info = I;
+    if (s->sd.on && s->sd.every == VO_SEMIDENSE_FRAMES) RC(vo_svo_semidense_enqueue(s, s->slot[S_CL], s->slot[S_CR], I.frame_id, I.T_wc));
     return VO_OK;
   }
   // the BA launch's epilogue wrote the loop's counts (pinned block) in front of the frame's sequence word
@@ -757,6 +761,10 @@ extern "C" int vo_svo_result(vo_svo *s, vo_svo_frame_info *info) {
   memcpy(s->T_wp, T_wc, sizeof(T_wc));
   memcpy(I.T_wc, T_wc, sizeof(T_wc));
   if (info) *info = I;
+  // the semi-dense depth of this frame's own pair (vo_svo_set_semidense): enqueued here, where the keyframe decision and the pose
+  // after the local BA are known; nothing waits for it (the frame's result stands whatever this returns)
+  if (s->sd.on && (I.is_keyframe || s->sd.every == VO_SEMIDENSE_FRAMES))
+    RC(vo_svo_semidense_enqueue(s, s->slot[S_CL], s->slot[S_CR], I.frame_id, T_wc));
   if (g_trace) {
     s->ht.t_ret = svo_now();
     ++s->ht.n_all;

@@ -18,6 +18,19 @@ struct SvoKeyframe {
   int global = 0;                   // index among all keyframes of the stream (stats_keyframe)
 };
 
+// vo_svo_set_semidense (semidense.hip): the option's state. One result at most is in flight: `done` is recorded behind its launch on
+// the side stream; an ingestion that reuses a slot the launch reads is ordered behind `done` on the device (guard).
+struct vo_svo_semidense {
+  bool on = false, have = false;
+  unsigned busy = 0;  // slots (bits) a launch has read since the last guard wait
+  int every = 0;
+  vo_semidense_params prm = {};
+  vo_sd_buffers buf;
+  hipEvent_t fork = nullptr, done = nullptr;
+  int slot_l = -1, slot_r = -1, w = 0, h = 0, frame_id = -1;
+  float T_wc[16] = {};
+};
+
 struct vo_svo {
   vo_ctx *c = nullptr;
   vo_svo_params prm;
@@ -54,6 +67,7 @@ struct vo_svo {
   VoPoseCovState cov;
   vo_driver_mask mask;  // vo_svo_set_mask (MonoVO: vo_mvo_set_mask): the ignore mask the pairs ingested from now on carry
   vo_zncc_gate zncc;    // vo_svo_set_zncc_gate (MonoVO: vo_mvo_set_zncc_gate): the appearance gate of the steady-state frames
+  vo_svo_semidense sd;  // vo_svo_set_semidense: semi-dense stereo depth of the keyframes' (or every frame's) own pair
   int mono = 0;  // the keyframe storage serves a MonoVO (mono_vo.hip): one observation per keyframe entry, bundled flags
   // all_stkeyframes_ (stats_keyframe): every keyframe's current pose (host) and where its related landmarks' ids are kept
   // on the device (a pool that only grows)
@@ -79,6 +93,10 @@ int vo_svo_local_ba(vo_svo *s, vo_svo_frame_info *info, int id_min);
 void vo_svo_lba_free(vo_svo *s);
 size_t vo_svo_lba_bytes(const vo_svo *s);
 int vo_svo_lba_update_points(vo_svo *s, const SvoTrackSet &ts, int n);  // a landmark got its 3-D point outside a keyframe
+
+int vo_svo_semidense_enqueue(vo_svo *s, int slot_l, int slot_r, int frame_id, const float T_wc[16]);  // semidense.hip
+int vo_svo_semidense_guard(vo_svo *s, int a, int b);
+void vo_svo_semidense_free(vo_svo *s);
 
 void svo_mul44(const float A[16], const float B[16], float C[16]);
 void svo_inv_se3(const float T[16], float Ti[16]);

@@ -148,6 +148,7 @@ extern "C" void vo_destroy(vo_ctx *c) {
   vo_rectify_free(c);
   vo_equalize_free(c);
   vo_draw_free(c);
+  vo_semidense_free(c);
   vo_sba_free(c);
   vo_orb_describe_free(c);
   vo_orb_free(c);

@@ -127,6 +127,7 @@ struct vo_ctx {
   uint8_t *eq_op;  // vo_equalize_image's own storage: a staging plane in front of what a slot has
   // the ZNCC gate of the driver whose frame is in flight (zncc.hip); null: none — the frame operators then launch nothing
   struct vo_zncc_gate *zncc_gate;
+  struct vo_semidense_state *semidense;  // vo_semidense_stereo / vo_semidense_points: their planes and scratch (semidense.hip), made on first use
 };
 
 static inline hipError_t vo_dev_malloc(vo_ctx *c, void **p, size_t bytes) {
@@ -239,6 +240,24 @@ int vo_zncc_gate_get(vo_ctx *c, const vo_zncc_gate *g, float *zncc_t, float *znc
 // the frame operators: the launch on c->stream (slot_r1 < 0 / pts_r1 == null: no stereo pair) and the BA launch's view
 int vo_zncc_gate_enqueue(vo_ctx *c, vo_zncc_gate *g, int slot_l0, int slot_l1, int slot_r1, const float *d_pts_l0, const float *d_pts_l1,
                          const float *d_pts_r1, int n, vo_zncc_view *view);
+
+// Semi-dense stereo depth (semidense.hip; include/vo_hip.h, "Semi-dense stereo"): the four planes of one result, the points
+// list's scratch (key, idx, cnt[1]) and, from the first points call, its device outputs (pts); sized by vo_config.max_width x
+// max_height. cnt[1]: the compaction's count; cnt[2 ..]: the kernel's workgroups' counts of accepted pixels (n_wg of them).
+struct vo_sd_buffers {
+  float *disp = nullptr, *score = nullptr, *sigma = nullptr;
+  int32_t *idx = nullptr;
+  uint8_t *status = nullptr, *key = nullptr;
+  int *cnt = nullptr;
+  float *pts = nullptr;
+  size_t npix = 0, n_wg = 0;
+};
+int vo_sd_buffers_alloc(vo_ctx *c, vo_sd_buffers *b);
+void vo_sd_buffers_free(vo_sd_buffers *b);
+void vo_semidense_free(vo_ctx *c);
+// the launch on c->stream, into device planes (any may be null); wg_accepted (device, may be null): a count per workgroup
+int vo_sd_enqueue(vo_ctx *c, int slot_l, int slot_r, const vo_semidense_params *p, float *disp, float *score, float *sigma, uint8_t *status,
+                  int *wg_accepted, int *W_out, int *H_out);
 
 // Image ingestion (H2D + pyramid chain) enqueues on the side stream when vo_set_ingest_side_stream is on: launchers
 // use c->stream, which this scope points at the ingest stream and restores on exit.
