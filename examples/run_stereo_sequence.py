@@ -13,7 +13,11 @@ pose's covariance as a node would put it into nav_msgs::Odometry::pose.covarianc
 pose-only BA), one line per frame: the id, the 36 values (row-major; x, y, z, rot x, rot y, rot z), `valid` and
 `n_unknown_steps` (frames whose pose did not come from the BA). --semidense DIR [--semidense-every frame] [--semidense-depth Z_MIN
 [Z_MAX]]: semi-dense stereo depth of every keyframe's (every frame's) own pair, computed on the device behind the frame; one ASCII
-PLY per result in DIR (`semidense_<frame id>.ply`: x y z in the world frame and the standard deviation of the inverse depth)."""
+PLY per result in DIR (`semidense_<frame id>.ply`: x y z in the world frame and the standard deviation of the inverse depth).
+--semidense-temporal [--semidense-min-obs N]: with --semidense, every keyframe's result seeds a map that the following frames
+update (the temporal search and fusion); `semidense_fused_<keyframe's frame id>.ply` holds the map's pixels with at least N (default
+2) observations (N = 1 keeps what the static result alone gave), written when the next keyframe replaces the map and at the end
+of the run."""
 import argparse
 import os
 import sys
@@ -77,13 +81,19 @@ def semidense_options(args):
     if args.semidense is None:
         if args.semidense_every is not None or args.semidense_depth is not None:
             raise SystemExit("--semidense-every / --semidense-depth need --semidense DIR")
+        if args.semidense_temporal or args.semidense_min_obs is not None:
+            raise SystemExit("--semidense-temporal / --semidense-min-obs need --semidense DIR")
         return {}
+    if args.semidense_min_obs is not None and (not args.semidense_temporal or not 1 <= args.semidense_min_obs <= 255):
+        raise SystemExit("--semidense-min-obs N: 1..255, with --semidense-temporal")
     z = args.semidense_depth or [3.0]
     if len(z) > 2 or not (z[0] > 0 and (len(z) == 1 or z[1] >= z[0])):
         raise SystemExit("--semidense-depth: Z_MIN [Z_MAX] in metres, 0 < Z_MIN <= Z_MAX")
     sd = {"z_min": z[0], "every": args.semidense_every or "keyframe"}
     if len(z) == 2:
         sd["z_max"] = z[1]
+    if args.semidense_temporal:
+        sd["temporal"] = True
     return {"semidense": sd}
 
 
@@ -126,6 +136,9 @@ def parse_args(argv=None):
     ap.add_argument("--semidense-every", choices=("keyframe", "frame"), default=None, help="a result per keyframe (default) or per frame")
     ap.add_argument("--semidense-depth", nargs="+", type=float, default=None, metavar="Z",
                     help="depth range Z_MIN [Z_MAX] in metres searched by --semidense (default 3, no upper end)")
+    ap.add_argument("--semidense-temporal", action="store_true",
+                    help="--semidense: fuse every keyframe's depth with the following frames; semidense_fused_<id>.ply per keyframe")
+    ap.add_argument("--semidense-min-obs", type=int, default=None, metavar="N", help="observations a fused pixel needs (default 2)")
     return ap.parse_args(argv)
 
 
@@ -143,7 +156,12 @@ def main():
                                **zncc_options(args), **semidense_options(args))
     if args.semidense:
         os.makedirs(args.semidense, exist_ok=True)
-    sd_last = -1
+    sd_last, fused = -1, None  # (fused: the current keyframe's map as points, as of the last frame)
+    min_obs = args.semidense_min_obs or 2
+
+    def write_fused():
+        if fused is not None:
+            write_ply(os.path.join(args.semidense, f"semidense_fused_{fused['frame_id']:06d}.ply"), fused["xyz"], fused["sigma_invd"])
     cov_file = open(args.covariance, "w") if args.covariance else None
     svo.ctx.sum_order = args.sum_order
     pair = lambda k: (load_grey(os.path.join(args.left, names_l[k])), load_grey(os.path.join(args.right, names_r[k])))  # noqa: E731
@@ -169,11 +187,20 @@ def main():
             if pts is not None and pts["frame_id"] != sd_last:
                 sd_last = pts["frame_id"]
                 write_ply(os.path.join(args.semidense, f"semidense_{sd_last:06d}.ply"), pts["xyz"], pts["sigma_invd"])
+        if args.semidense and args.semidense_temporal:
+            # (a keyframe has replaced the map by the time its result is here, so the map is taken after every frame — after a
+            # keyframe it is the freshly seeded one, which is what gets written if the next frame is a keyframe again — and
+            # written when the next keyframe comes: simple, at the price of a wait for the side stream per frame)
+            if info.is_keyframe:
+                write_fused()
+            fused = svo.getSemiDensePoints(world=True, fused=True, min_obs=min_obs)
         if k % 100 == 0 or k == n - 1:
             t = poses[-1][:3, 3]
             print(f"frame {k:6d}: {info.n_tracks_out:5d} tracks, {n_kf:4d} keyframes, position ({t[0]:9.3f} {t[1]:9.3f} {t[2]:9.3f})", flush=True)
         cur = nxt
     dt = time.perf_counter() - t0
+    if args.semidense and args.semidense_temporal:
+        write_fused()
     V.write_trajectory(args.trajectory, ids, np.stack(poses))
     if args.keyframes:
         kfs = svo.getKeyframes()

@@ -803,6 +803,105 @@ int vo_svo_get_semidense(vo_svo *svo, float *disparity, float *score, float *sig
                          int *frame_id, float T_wc[16], int *n_accepted);
 int vo_svo_get_semidense_points(vo_svo *svo, int world, int cap, float *xyz, float *sigma_invd, uint16_t *pixel, int *n, int *frame_id);
 
+/* ---- Semi-dense temporal: the keyframe's pixels searched in the following left images, fused per keyframe ----
+ * The second half of the reference author's semi-dense prototype, read for intent only: a pixel of the keyframe's left image is
+ * searched in a later left image along the epipolar line the odometry's pose gives, and the inverse depths are fused as
+ * Gaussians. Only + - x / sqrtf floorf fabsf in float32, every operation rounded on its own (no FMA), in the order written here;
+ * the samples and the five sums are integers, so no summation order enters. tests/semidense_temporal_restatement.py restates it.
+ *   inputs     Lk: the keyframe's left level-0 u8 plane; Lc: the current left plane (a slot's level 0), both W x H, 3 <= W, H <=
+ *              65535; an ignore mask over the key pixels (the operator, which has no key slot, takes the one bound to slot_cur;
+ *              the driver takes the keyframe left slot's, copied when the map is seeded); K = fx, fy, cx, cy; T_ck row-major 4 x 4, X_c = R X_k + t; the map: four W x H
+ *              planes invd f32, sigma f32 (both 0 where there is nothing yet), n_obs u8, tstatus u8 (the last launch's decision).
+ *   params     hw 1..15, hh 0..3; g_min 1..360; thres_best, thres_peak; peak_px, edge_px 0..512; eps_edge, eps_epi, eps_scale >= 0;
+ *              0 < z_min < z_max [m]; 2 edge_px + 3 <= max_search <= 512; j_min > 0 [pixel per 1/m].
+ *              r_min = 1.0f / z_max, r_max = 1.0f / z_min. C[i] = -((R[0][i] t0 + R[1][i] t1) + R[2][i] t2).
+ *   candidate  (x, y) with 1 <= x <= W-2, 1 <= y <= H-2; gx, gy as in the static block, gx^2 + gy^2 >= g_min^2; not masked. Then
+ *              xc = (float)x - cx, yc = (float)y - cy, u = xc / fx, v = yc / fy, a_i = (R[i][0] u + R[i][1] v) + R[i][2];
+ *              d_k = (fx C0 - xc C2, fy C1 - yc C2), dk2 = d_kx^2 + d_ky^2. dk2 < 1e-6: the pixel sits on the epipole, status 7
+ *              (so that an identity pose gives every candidate that status). dot = (float)gx d_kx + (float)gy d_ky,
+ *              g2 = (float)(gx^2 + gy^2): (4 dot) dot < g2 dk2 (the gradient lies more than 60 degrees off the key epipolar
+ *              line): no candidate. (ux, uy) = d_k / sqrtf(dk2). A key tap (below) outside the image: no candidate.
+ *   range      prior (sigma > 0): lo = max(invd - 2 sigma, r_min), hi = min(invd + 2 sigma, r_max); else lo = r_min, hi = r_max.
+ *              D(rho) = a2 + rho t2; p(rho) = (fx ((a0 + rho t0) / D(rho)) + cx, fy ((a1 + rho t1) / D(rho)) + cy).
+ *              not (lo < hi), or D(lo) <= 0.1 or D(hi) <= 0.1 (an end not in front of the current camera): status 8.
+ *              P0 = p(lo), e = p(hi) - P0, len = sqrtf(ex^2 + ey^2), J = len / (hi - lo). not (J >= j_min): status 7 (no
+ *              parallax: the depth is not observable, the pixel must not enter the map). l = e / len.
+ *              npos = (int)floorf(len + 0.5f) + 2 edge_px + 3 positions p_j = P0 + (float)j l, j = j0 .. j0 + npos - 1 with
+ *              j0 = -(edge_px + 1). npos > max_search: status 6 (range too long), nothing is searched.
+ *   taps       t = (v, k), v = -hh..hh outer, k = -hw..hw inner. The key direction d = +-(ux, uy), + where
+ *              lx (fx (b0 D(lo) - N0 b2)) + ly (fy (b1 D(lo) - N1 b2)) >= 0 with b_i = R[i][0] (ux / fx) + R[i][1] (uy / fy),
+ *              N_i = a_i + lo t_i (the derivative of p(lo) along the key direction, times D(lo)^2: the key direction that
+ *              corresponds to l). Key tap: ((float)x + (float)k dx) + (float)v (-dy), ((float)y + (float)k dy) + (float)v dx.
+ *              Current tap of position j: (p_jx + (float)k lx) + (float)v (-ly), (p_jy + (float)k ly) + (float)v lx.
+ *              A coordinate c becomes X = (int)floorf(32 c + 0.5f) where that lies in [-2^20, 2^22], else -2^20; cell X >> 5,
+ *              weight X & 31. The tap is inside where 0 <= cell_x <= W-2 and 0 <= cell_y <= H-2 — decided on the integers
+ *              before any load. Value: ((32-wy) ((32-wx) I00 + wx I10) + wy ((32-wx) I01 + wx I11) + 32) >> 6, 0 .. 4080.
+ *   scores     S_k, S_kk, S_c, S_cc, S_kc over the n taps (n <= 217: they fit 32 bits unsigned); A = n S_kk - S_k^2,
+ *              B = n S_cc - S_c^2, num = n S_kc - S_k S_c (64-bit); s(j) = -1 where A == 0 or B == 0, else
+ *              (float)num / sqrtf((float)A * (float)B). A position with a tap outside has no score.
+ *   run        the positions searched: the maximal run of inside positions that contains the prior's position
+ *              jp = (int)floorf(((p(invd)_x - P0x) lx + (p(invd)_y - P0y) ly) + 0.5f) (a prior with D(invd) > 0.1 and jp among
+ *              the positions), or else the first maximal run.
+ *   status     0 no candidate; 7, 8, 6 as above; then 5: no run, fewer than 2 edge_px + 3 positions in it, or A == 0; with j_best
+ *              the run's largest s (ties: the smallest j): 2 s(j_best) <= thres_best; 3 some j of the run with s(j) > thres_peak
+ *              has |j - j_best| > peak_px; 4 not (first + edge_px < j_best < last - edge_px); else the parabola offset off of the
+ *              static block on s(j_best - 1), s(j_best), s(j_best + 1), j* = (float)j_best + off, and with |lx| >= |ly|:
+ *              w = ((P0x + j* lx) - cx) / fx, rho* = (a0 - w a2) / (w t2 - t0); else w = ((P0y + j* ly) - cy) / fy,
+ *              rho* = (a1 - w a2) / (w t2 - t1). not (r_min <= rho* <= r_max) or D(rho*) <= 0.1: status 8. Else 1, accepted.
+ *   sigma*     cs = dot / (sqrtf(g2) sqrtf(dk2)); sn2 = max(1 - cs cs, 0); st = (eps_scale (float)hw) fabsf(1 - 1 / D(rho*));
+ *              sigma* = (sqrtf((eps_edge^2 + (eps_epi^2) sn2) + st^2) / fabsf(cs)) / J: the static formula with bf replaced by the
+ *              local J, plus st: the patch is not rescaled, and 1 / D(rho*) is the factor by which a fronto-parallel surface is
+ *              magnified in the current image (DESIGN.md §18 has the measurement that asked for this term).
+ *   fusion     by the same lane, in the same launch. Without a prior: invd = rho*, sigma = sigma*, n_obs = 1. With one:
+ *              s2 = sigma^2, m2 = sigma*^2: invd = (invd m2 + rho* s2) / (s2 + m2), sigma = sqrtf((s2 m2) / (s2 + m2)), n_obs
+ *              saturates at 255. A pixel that is not accepted keeps its map entry; tstatus is written for every pixel.
+ *   score      (diagnostic, may be NULL) s(j_best) wherever a best was taken (status 1..4, and 8 after the search), else 0.
+ * vo_semidense_map_seed: a map from a static result (host planes, or all device with on_device): where status == 1
+ * invd = disparity / bf, sigma = sigma_invd, n_obs = 1; elsewhere 0; tstatus = 0. Synchronous.
+ * vo_semidense_temporal: one launch; key_plane (host, or device with key_on_device) has key_stride bytes per row; the map is
+ * updated in place (host planes, or all device with on_device). Synchronous.
+ * vo_semidense_map_points: vo_semidense_points of a map: the pixels with n_obs >= min_obs (1..255) in raster order, z = 1 / invd.
+ *
+ * StereoVO: vo_svo_set_semidense_temporal(svo, prm) — NULL = off — needs vo_svo_set_semidense on (any `every`) and makes its only
+ * allocation (the key plane, the keyframe's mask and the map) at the first enable; with it off nothing changes, with it on the odometry's results are
+ * the same bits. At a keyframe, behind the static launch on the side stream: the left level-0 plane is copied into the key
+ * plane and the left slot's mask next to it, the map is seeded, the keyframe's T_wc and frame_id are kept. At every later frame until the next keyframe
+ * vo_svo_result enqueues one launch on the side stream behind a fork event, with T_ck = inverseSE3(T_wc) * T_wk formed on the host
+ * in float (inverseSE3: t' = ((-r0) t0 + (-r1) t1) + (-r2) t2 per row of R^T; the product: r = a0 b0, r = a_k b_k + r) from the
+ * poses vo_svo_result returns; it never waits for it. The launch reads that frame's left slot, which a later ingestion is
+ * ordered behind on the device. vo_svo_get_semidense_map: the planes (any may be NULL), size (0 x 0 before a keyframe), the
+ * keyframe's frame_id and T_wc, n_fused = the launches since the keyframe. vo_svo_get_semidense_map_points: the map's points with
+ * the left camera's K, world != 0: in the world frame. Both wait for the side stream's last launch only; VO_ERR_INVALID while a
+ * frame is in flight or with the option off. Not for MonoVO or vo_batch streams. */
+typedef struct {
+  int hw, hh;          /* 4, 1 */
+  int g_min;           /* 20 */
+  float thres_best;    /* 0.95 */
+  float thres_peak;    /* 0.9 */
+  int peak_px;         /* 5 */
+  int edge_px;         /* 2 */
+  float eps_edge;      /* 0.5 */
+  float eps_epi;       /* 1.0 */
+  float eps_scale;     /* 3.0 */
+  float z_min, z_max;  /* 3, 100 [m] */
+  int max_search;      /* 128 */
+  float j_min;         /* 16 */
+} vo_semidense_temporal_params;
+int vo_semidense_temporal_default_params(vo_semidense_temporal_params *prm);
+int vo_semidense_map_seed(vo_ctx *ctx, const float *disparity, const float *sigma_invd, const uint8_t *status, int width, int height,
+                          float bf, float *invd, float *sigma, uint8_t *n_obs, uint8_t *tstatus, int on_device);
+int vo_semidense_temporal(vo_ctx *ctx, const uint8_t *key_plane, int key_stride, int key_on_device, int slot_cur, const float K[4],
+                          const float T_ck[16], const vo_semidense_temporal_params *prm, float *invd, float *sigma, uint8_t *n_obs,
+                          uint8_t *tstatus, float *score, int on_device);
+int vo_semidense_map_points(vo_ctx *ctx, const float *invd, const float *sigma, const uint8_t *n_obs, int width, int height,
+                            int planes_on_device, const float K[4], const float *T, int min_obs, int cap, float *xyz, float *sigma_out,
+                            uint16_t *pixel, int *n);
+int vo_svo_set_semidense_temporal(vo_svo *svo, const vo_semidense_temporal_params *prm);
+int vo_svo_get_semidense_map(vo_svo *svo, float *invd, float *sigma, uint8_t *n_obs, uint8_t *tstatus, int *width, int *height,
+                             int *frame_id, float T_wc[16], int *n_fused);
+int vo_svo_get_semidense_map_points(vo_svo *svo, int world, int min_obs, int cap, float *xyz, float *sigma, uint16_t *pixel, int *n,
+                                    int *frame_id);
+
 /* ---- undistortion / stereo rectification in front of the trackers ----------
  * core/visual_odometry/camera.cpp. A context holds the maps of two cameras
  * (cam 0 = left or the mono camera, cam 1 = right), device-resident. */

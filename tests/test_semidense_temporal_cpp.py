@@ -1,0 +1,36 @@
+"""The C++ side of the temporal semi-dense option (setSemiDenseTemporal / getSemiDenseMapPoints on vo::StereoVO and the
+reference-typed adapter) type-checks against the stand-in headers; the sequence example's options. No GPU."""
+import os
+import subprocess
+import sys
+
+import pytest
+
+from test_zncc import ROOT, STUBS
+
+
+def test_adapter_semidense_temporal_type_checks():
+    src = os.path.join(ROOT, "tests", "cpp", "semidense_temporal_typecheck.cpp")
+    r = subprocess.run(["g++", "-std=c++17", "-Wall", "-Wextra", "-Werror", "-I", ROOT, "-I", os.path.join(STUBS, "thirdparty"),
+                        "-I", os.path.join(STUBS, "reference"), "-fsyntax-only", src], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr[-4000:]
+
+
+def test_example_semidense_temporal_options():
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    try:
+        import run_stereo_sequence as ex
+    finally:
+        sys.path.pop(0)
+    base = ["--config", "c.yaml", "--left", "l", "--right", "r"]
+    assert ex.semidense_options(ex.parse_args(base + ["--semidense", "out"])) == {"semidense": {"z_min": 3.0, "every": "keyframe"}}
+    got = ex.semidense_options(ex.parse_args(base + ["--semidense", "out", "--semidense-temporal"]))
+    assert got == {"semidense": {"z_min": 3.0, "every": "keyframe", "temporal": True}}
+    got = ex.semidense_options(ex.parse_args(base + ["--semidense", "out", "--semidense-temporal", "--semidense-min-obs", "3",
+                                                      "--semidense-every", "frame"]))
+    assert got == {"semidense": {"z_min": 3.0, "every": "frame", "temporal": True}}
+    for bad in (["--semidense-temporal"], ["--semidense-min-obs", "2"], ["--semidense", "o", "--semidense-min-obs", "2"],
+                ["--semidense", "o", "--semidense-temporal", "--semidense-min-obs", "0"],
+                ["--semidense", "o", "--semidense-temporal", "--semidense-min-obs", "256"]):
+        with pytest.raises(SystemExit):
+            ex.semidense_options(ex.parse_args(base + bad))

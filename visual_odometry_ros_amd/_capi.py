@@ -108,6 +108,12 @@ class SemiDenseParams(C.Structure):  # vo_semidense_params
                 ("bf", C.c_float)]
 
 
+class SemiDenseTemporalParams(C.Structure):  # vo_semidense_temporal_params
+    _fields_ = [("hw", C.c_int), ("hh", C.c_int), ("g_min", C.c_int), ("thres_best", C.c_float), ("thres_peak", C.c_float),
+                ("peak_px", C.c_int), ("edge_px", C.c_int), ("eps_edge", C.c_float), ("eps_epi", C.c_float), ("eps_scale", C.c_float),
+                ("z_min", C.c_float), ("z_max", C.c_float), ("max_search", C.c_int), ("j_min", C.c_float)]
+
+
 class FivePointParams(C.Structure):
     _fields_ = [("thres_px", C.c_float), ("confidence", C.c_float), ("max_iters", C.c_int), ("seed", C.c_ulonglong)]
 
@@ -156,6 +162,8 @@ SYMBOLS = [
     "vo_zncc", "vo_svo_set_zncc_gate", "vo_svo_get_zncc", "vo_mvo_set_zncc_gate", "vo_mvo_get_zncc",
     "vo_semidense_default_params", "vo_semidense_stereo", "vo_semidense_points",
     "vo_svo_set_semidense", "vo_svo_get_semidense", "vo_svo_get_semidense_points",
+    "vo_semidense_temporal_default_params", "vo_semidense_map_seed", "vo_semidense_temporal", "vo_semidense_map_points",
+    "vo_svo_set_semidense_temporal", "vo_svo_get_semidense_map", "vo_svo_get_semidense_map_points",
 ]
 
 _lib = None
@@ -261,6 +269,13 @@ def load():
     lib.vo_svo_set_semidense.argtypes = [vp, vp, ci]
     lib.vo_svo_get_semidense.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.vo_svo_get_semidense_points.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp]
+    lib.vo_semidense_temporal_default_params.argtypes = [vp]
+    lib.vo_semidense_map_seed.argtypes = [vp, vp, vp, vp, ci, ci, C.c_float, vp, vp, vp, vp, ci]
+    lib.vo_semidense_temporal.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci]
+    lib.vo_semidense_map_points.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, ci, ci, vp, vp, vp, vp]
+    lib.vo_svo_set_semidense_temporal.argtypes = [vp, vp]
+    lib.vo_svo_get_semidense_map.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.vo_svo_get_semidense_map_points.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp]
     lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_five_point_destroy.argtypes = [vp]
     lib.vo_five_point_destroy.restype = None

@@ -114,6 +114,25 @@ def _semidense_params(lib, params):
     return p
 
 
+class SemiDenseMap(collections.namedtuple("SemiDenseMap", "invd sigma n_obs tstatus score frame_id T_wc n_fused")):
+    """A keyframe's semi-dense map (include/vo_hip.h, "Semi-dense temporal"): invd, sigma float32 (height, width) — both 0 where
+    there is nothing yet —, n_obs, tstatus uint8; score float32 (the operator's diagnostic plane, None from a driver); from a driver
+    also the keyframe's frame id, its T_wc and the number of frames fused so far."""
+    __slots__ = ()
+
+
+def _semidense_temporal_params(lib, params):
+    """keyword parameters -> vo_semidense_temporal_params: the C defaults, then the caller's fields"""
+    p = _capi.SemiDenseTemporalParams()
+    lib.vo_semidense_temporal_default_params(C.byref(p))
+    known = {f[0] for f in _capi.SemiDenseTemporalParams._fields_}
+    for k, v in dict(params).items():
+        if k not in known:
+            raise ValueError(f"semi-dense temporal: unknown parameter {k!r}; known: {sorted(known)}")
+        setattr(p, k, v)
+    return p
+
+
 def _zncc_gate_arg(gate, stereo):
     """zncc_gate= / setZnccGate: None -> off; dict(thres=, win=15, pattern="centered", pairs=("temporal",)) -> the C call's
     (pairs, win, pattern, thres). pairs: names out of "temporal", "stereo" (StereoVO only)."""
@@ -329,6 +348,84 @@ class Context:
             e.n = n.value
             raise
         return xyz[:n.value], so[:n.value], px[:n.value]
+
+    # ---- semi-dense temporal search and fusion (include/vo_hip.h, "Semi-dense temporal") ---------------------------------------
+    def semiDenseMapSeed(self, disparity, sigma_invd, status, bf, out=None, on_device=None):
+        """The map of a static result: a SemiDenseMap (invd = disparity / bf, sigma = sigma_invd, n_obs = 1 where status == 1, else
+        0). The planes are arrays, or DEVICE addresses with on_device=(width, height) and out=dict(invd=, sigma=, n_obs=, tstatus=)
+        of DEVICE addresses (None is returned then)."""
+        if on_device is not None:
+            w, h = on_device
+            self.check(self.lib.vo_semidense_map_seed(self._h, C.c_void_p(disparity), C.c_void_p(sigma_invd), C.c_void_p(status), int(w), int(h),
+                                                      float(bf), *(C.c_void_p(out[k]) for k in ("invd", "sigma", "n_obs", "tstatus")), 1))
+            return None
+        d, sg, st = np.ascontiguousarray(disparity, np.float32), np.ascontiguousarray(sigma_invd, np.float32), np.ascontiguousarray(status, np.uint8)
+        if d.ndim != 2 or sg.shape != d.shape or st.shape != d.shape:
+            raise ValueError("disparity, sigma_invd and status are planes of one (height, width)")
+        invd, sigma = np.zeros(d.shape, np.float32), np.zeros(d.shape, np.float32)
+        n_obs, ts = np.zeros(d.shape, np.uint8), np.zeros(d.shape, np.uint8)
+        self.check(self.lib.vo_semidense_map_seed(self._h, d.ctypes.data, sg.ctypes.data, st.ctypes.data, d.shape[1], d.shape[0], float(bf),
+                                                  invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data, ts.ctypes.data, 0))
+        return SemiDenseMap(invd, sigma, n_obs, ts, None, None, None, None)
+
+    def semiDenseTemporal(self, key, slot_cur, K, T_ck, map, key_on_device=None, map_on_device=False, **params):
+        """One temporal launch: the key plane's pixels searched in slot_cur's level-0 plane along the epipolar lines of T_ck (4 x 4,
+        X_c = R X_k + t) with K = (fx, fy, cx, cy); the slot's ignore mask applies to the key pixels. key: a u8 array, or a DEVICE
+        address with key_on_device=stride. map: a SemiDenseMap / dict(invd=, sigma=, n_obs=) of arrays — a new SemiDenseMap is
+        returned, the arguments stay —, or with map_on_device dict(invd=, sigma=, n_obs=, tstatus=[, score=]) of DEVICE addresses,
+        updated in place (None is returned). params: the fields of vo_semidense_temporal_params."""
+        p = _semidense_temporal_params(self.lib, params)
+        Ka = np.ascontiguousarray(K, np.float32).reshape(4)
+        Ta = np.ascontiguousarray(T_ck, np.float32).reshape(4, 4)
+        if key_on_device is not None:
+            pk, stride = C.c_void_p(key), int(key_on_device)
+        else:
+            ka = _u8(key)
+            pk, stride = ka.ctypes.data, ka.strides[0]
+        if map_on_device:
+            sc = map.get("score")
+            self.check(self.lib.vo_semidense_temporal(self._h, pk, stride, int(key_on_device is not None), int(slot_cur), Ka.ctypes.data, Ta.ctypes.data,
+                                                      C.byref(p), *(C.c_void_p(map[k]) for k in ("invd", "sigma", "n_obs", "tstatus")),
+                                                      C.c_void_p(sc) if sc else None, 1))
+            return None
+        get = (lambda k: getattr(map, k)) if isinstance(map, SemiDenseMap) else (lambda k: map[k])
+        invd, sigma = np.array(get("invd"), np.float32, order="C"), np.array(get("sigma"), np.float32, order="C")
+        n_obs = np.array(get("n_obs"), np.uint8, order="C")
+        w, h = self.slot_image_size(slot_cur)
+        if invd.shape != (h, w) or sigma.shape != (h, w) or n_obs.shape != (h, w):
+            raise ValueError(f"the map's planes must be ({h}, {w}) like slot {slot_cur}'s image")
+        ts, score = np.zeros((h, w), np.uint8), np.zeros((h, w), np.float32)
+        self.check(self.lib.vo_semidense_temporal(self._h, pk, stride, int(key_on_device is not None), int(slot_cur), Ka.ctypes.data, Ta.ctypes.data,
+                                                  C.byref(p), invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data, ts.ctypes.data, score.ctypes.data, 0))
+        return SemiDenseMap(invd, sigma, n_obs, ts, score, None, None, None)
+
+    def semiDenseMapPoints(self, invd, sigma, n_obs, K, T=None, min_obs=1, capacity=None, on_device=None):
+        """The map's pixels with n_obs >= min_obs in raster order: (xyz float32 [n, 3], sigma float32 [n], pixel uint16 [n, 2]) with
+        z = 1 / invd; the rest as semiDensePoints."""
+        if on_device is not None:
+            w, h = on_device
+            pi, ps, pn = C.c_void_p(invd), C.c_void_p(sigma), C.c_void_p(n_obs)
+        else:
+            a, sg, no = np.ascontiguousarray(invd, np.float32), np.ascontiguousarray(sigma, np.float32), np.ascontiguousarray(n_obs, np.uint8)
+            if a.ndim != 2 or sg.shape != a.shape or no.shape != a.shape:
+                raise ValueError("invd, sigma and n_obs are planes of one (height, width)")
+            h, w = a.shape
+            pi, ps, pn = a.ctypes.data, sg.ctypes.data, no.ctypes.data
+        cap = w * h if capacity is None else int(capacity)
+        Ka = np.ascontiguousarray(K, np.float32).reshape(4)
+        Ta = None if T is None else np.ascontiguousarray(T, np.float32).reshape(4, 4)
+        xyz, so, px = np.zeros((max(cap, 1), 3), np.float32), np.zeros(max(cap, 1), np.float32), np.zeros((max(cap, 1), 2), np.uint16)
+        n = C.c_int()
+        rc = self.lib.vo_semidense_map_points(self._h, pi, ps, pn, w, h, int(on_device is not None), Ka.ctypes.data,
+                                              None if Ta is None else Ta.ctypes.data, int(min_obs), cap, xyz.ctypes.data, so.ctypes.data,
+                                              px.ctypes.data, C.byref(n))
+        try:
+            self.check(rc)
+        except VoError as e:
+            e.n = n.value
+            raise
+        m = min(n.value, cap)
+        return xyz[:m], so[:m], px[:m]
 
     def set_image_device(self, slot, dev_ptr, width, height, stride):
         self.check(self.lib.vo_set_image_device(self._h, slot, C.c_void_p(dev_ptr), width, height, stride))
@@ -1227,7 +1324,8 @@ class StereoVO:
                  thres_trans=10.0, n_max_keyframes_in_window=9, strict_border=4, local_ba=True, rectify=False, thres_sampson=60.0,
                  debug_image=False, pose_covariance=False, sigma_px=0.0, mask=None, zncc_gate=None, semidense=None):
         """debug_image=True: every tracked frame draws the reference's img_debug_ on the device (getDebugImage).
-        semidense: dict of semi-dense stereo parameters (setSemiDense; "every": "keyframe" or "frame") — depth of the keyframes' pairs.
+        semidense: dict of semi-dense stereo parameters (setSemiDense; "every": "keyframe" or "frame") — depth of the keyframes' pairs;
+        its "temporal": True or dict(z_max=..., max_search=...) also switches setSemiDenseTemporal on.
         mask: the ignore mask every pair carries from the first one on (setMask).
         zncc_gate: dict(thres=, win=15, pattern="centered", pairs=("temporal",)) — the appearance gate (setZnccGate).
         pose_covariance=True: every frame chains the covariance of its pose on the device (getPoseCovariance); sigma_px > 0
@@ -1259,7 +1357,10 @@ class StereoVO:
             self.setZnccGate(zncc_gate)
         if semidense is not None:
             sd = dict(semidense)
+            temporal = sd.pop("temporal", None)
             self.setSemiDense(sd, every=sd.pop("every", "keyframe"))
+            if temporal:
+                self.setSemiDenseTemporal({} if temporal is True else temporal)
         self._info = SvoFrameInfo()
         self.stats_frame = []  # AlgorithmStatistics::FrameStatistics::Twc per frame (stereo_vo.cpp:979-980)
 
@@ -1399,20 +1500,51 @@ class StereoVO:
                                                      C.byref(fid), T.ctypes.data, C.byref(na)))
         return SemiDenseResult(d, sc, sg, st, fid.value, T, na.value)
 
-    def getSemiDensePoints(self, world=True, capacity=None):
+    def setSemiDenseTemporal(self, params):
+        """The temporal search and fusion (include/vo_hip.h, "Semi-dense temporal"): every keyframe's static result seeds a map that
+        each later frame until the next keyframe updates, on the side stream; the odometry's results do not change. params: dict
+        of Context.semiDenseTemporal's parameters ({}: the defaults), None: off. Needs setSemiDense. Refused while a frame is in flight."""
+        if params is None:
+            self.ctx.check(self.lib.vo_svo_set_semidense_temporal(self._h, None))
+            return
+        p = _semidense_temporal_params(self.lib, params)
+        self.ctx.check(self.lib.vo_svo_set_semidense_temporal(self._h, C.byref(p)))
+
+    def getSemiDenseMap(self):
+        """The last keyframe's map (a SemiDenseMap with frame_id, T_wc (4, 4) and n_fused), None before a keyframe. Waits for the side
+        stream's last launch only."""
+        w, h, fid, nf = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        T = np.zeros((4, 4), np.float32)
+        self.ctx.check(self.lib.vo_svo_get_semidense_map(self._h, None, None, None, None, C.byref(w), C.byref(h), C.byref(fid), None, None))
+        if w.value <= 0:
+            return None
+        invd, sg = np.zeros((h.value, w.value), np.float32), np.zeros((h.value, w.value), np.float32)
+        no, ts = np.zeros((h.value, w.value), np.uint8), np.zeros((h.value, w.value), np.uint8)
+        self.ctx.check(self.lib.vo_svo_get_semidense_map(self._h, invd.ctypes.data, sg.ctypes.data, no.ctypes.data, ts.ctypes.data, C.byref(w),
+                                                         C.byref(h), C.byref(fid), T.ctypes.data, C.byref(nf)))
+        return SemiDenseMap(invd, sg, no, ts, None, fid.value, T, nf.value)
+
+    def getSemiDensePoints(self, world=True, capacity=None, fused=False, min_obs=2):
         """The accepted pixels of the last semi-dense result as points, raster order: dict(xyz float32 [n, 3] — in the world frame
         (the frame's T_wc) or, world=False, the left camera's —, sigma_invd [n], pixel uint16 [n, 2], frame_id); None before any.
-        capacity: room for that many points (default: all); more raise VoError(VO_ERR_CAPACITY) whose `n` holds the true count."""
+        capacity: room for that many points (default: all); more raise VoError(VO_ERR_CAPACITY) whose `n` holds the true count.
+        fused=True (setSemiDenseTemporal): the last keyframe's map instead — its pixels with n_obs >= min_obs, z = 1 / invd."""
+        if fused:
+            get = lambda *a: self.lib.vo_svo_get_semidense_map_points(self._h, int(bool(world)), int(min_obs), *a)
+        else:
+            get = lambda *a: self.lib.vo_svo_get_semidense_points(self._h, int(bool(world)), *a)
+        return self._semidense_points(get, capacity)
+
+    def _semidense_points(self, get, capacity):
         n, fid = C.c_int(), C.c_int()
-        rc = self.lib.vo_svo_get_semidense_points(self._h, int(bool(world)), 0, None, None, None, C.byref(n), C.byref(fid))
+        rc = get(0, None, None, None, C.byref(n), C.byref(fid))
         if rc < 0 and rc != -8:  # (VO_ERR_CAPACITY: the count is what was asked for)
             self.ctx.check(rc)
         if fid.value < 0:
             return None
         cap = n.value if capacity is None else int(capacity)
         xyz, sg, px = np.zeros((max(cap, 1), 3), np.float32), np.zeros(max(cap, 1), np.float32), np.zeros((max(cap, 1), 2), np.uint16)
-        rc = self.lib.vo_svo_get_semidense_points(self._h, int(bool(world)), cap, xyz.ctypes.data, sg.ctypes.data, px.ctypes.data,
-                                                  C.byref(n), C.byref(fid))
+        rc = get(cap, xyz.ctypes.data, sg.ctypes.data, px.ctypes.data, C.byref(n), C.byref(fid))
         try:
             self.ctx.check(rc)
         except VoError as e:  # (VO_ERR_CAPACITY: `n` holds the true count)

@@ -479,6 +479,16 @@ class StereoVO {
     for (size_t i = 0; i < v.size(); ++i) o[i] = Point(v[i].x, v[i].y, v[i].z);
     return o;
   }
+  // the temporal half of that prototype (vo::StereoVO::setSemiDenseTemporal): the keyframe's depth fused with the following frames;
+  // getSemiDenseMapPoints() is the last keyframe's map, the pixels seen at least min_obs times
+  void setSemiDenseTemporal(const vo_semidense_temporal_params *prm) { impl_.setSemiDenseTemporal(prm); }
+  PointVec getSemiDenseMapPoints(bool world = true, int min_obs = 2) {
+    vo::PointVec v;
+    impl_.getSemiDenseMapPoints(v, nullptr, world, min_obs);
+    PointVec o(v.size());
+    for (size_t i = 0; i < v.size(); ++i) o[i] = Point(v[i].x, v[i].y, v[i].z);
+    return o;
+  }
   // NOT in the reference: CLAHE equalisation of every image before the tracker (vo::StereoVO::setEqualize; VO_EQ_CLAHE / VO_EQ_OFF)
   void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) { impl_.setEqualize(mode, clip_limit, tiles_x, tiles_y); }
   vo::StereoVO &device() { return impl_; }

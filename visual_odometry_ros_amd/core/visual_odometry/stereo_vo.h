@@ -262,6 +262,28 @@ class StereoVO {
                                                    sigma_invd ? sigma_invd->data() : nullptr, nullptr, &n, &fid));
     return fid >= 0;
   }
+  // The temporal half of that prototype (vo_svo_set_semidense_temporal; include/vo_hip.h, "Semi-dense temporal"): every keyframe's
+  // static result seeds a map that each later frame until the next keyframe updates on the side stream (an epipolar search along
+  // the odometry's pose, Gaussian fusion of the inverse depths). Needs setSemiDense. prm = nullptr: off. Throws while a frame is in flight.
+  static vo_semidense_temporal_params defaultSemiDenseTemporalParams() {
+    vo_semidense_temporal_params p;
+    vo_semidense_temporal_default_params(&p);
+    return p;
+  }
+  void setSemiDenseTemporal(const vo_semidense_temporal_params *prm) { ctx_->check(vo_svo_set_semidense_temporal(svo_, prm)); }
+  // the last keyframe's map as points (the pixels with n_obs >= min_obs, z = 1 / invd) in the world frame (the keyframe's T_wc) or
+  // the left camera's, raster order; waits for the side stream's last launch only. false (and empty vectors) before a keyframe.
+  bool getSemiDenseMapPoints(PointVec &xyz, std::vector<float> *sigma = nullptr, bool world = true, int min_obs = 2, int *frame_id = nullptr) {
+    int n = 0, fid = -1;
+    const int rc = vo_svo_get_semidense_map_points(svo_, world ? 1 : 0, min_obs, 0, nullptr, nullptr, nullptr, &n, &fid);
+    if (rc != VO_ERR_CAPACITY) ctx_->check(rc);  // (room for none: the count is what was asked for)
+    xyz.resize((size_t)n);
+    if (sigma) sigma->resize((size_t)n);
+    if (frame_id) *frame_id = fid;
+    if (n) ctx_->check(vo_svo_get_semidense_map_points(svo_, world ? 1 : 0, min_obs, n, reinterpret_cast<float *>(xyz.data()),
+                                                       sigma ? sigma->data() : nullptr, nullptr, &n, &fid));
+    return fid >= 0;
+  }
   // NOT in the reference: CLAHE on every image before the tracker (vo::Context::setEqualize on this driver's context): legal
   // between frames, applies to the images handed over from now on
   void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) { ctx_->setEqualize(mode, clip_limit, tiles_x, tiles_y); }

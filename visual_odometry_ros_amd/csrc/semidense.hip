@@ -96,6 +96,7 @@ struct vo_semidense_state {
   vo_sd_buffers buf;
 };
 void vo_semidense_free(vo_ctx *c) {
+  vo_semidense_temporal_free(c);
   if (!c->semidense) return;
   vo_sd_buffers_free(&c->semidense->buf);
   delete c->semidense;
@@ -106,6 +107,7 @@ static int sd_ctx_buffers(vo_ctx *c, vo_sd_buffers **b) {
   *b = &c->semidense->buf;
   return vo_sd_buffers_alloc(c, *b);
 }
+int vo_sd_ctx_buffers(vo_ctx *c, vo_sd_buffers **b) { return sd_ctx_buffers(c, b); }
 
 // the launch on c->stream: the slots' level-0 planes and the left slot's mask, ordered behind their last writers
 int vo_sd_enqueue(vo_ctx *c, int slot_l, int slot_r, const vo_semidense_params *p, float *disp, float *score, float *sigma, uint8_t *status,
@@ -192,11 +194,18 @@ extern "C" int vo_semidense_stereo(vo_ctx *c, int slot_l, int slot_r, const vo_s
 int vo_sd_points(vo_ctx *c, vo_sd_buffers *b, const float *d_disp, const float *d_sigma, const uint8_t *d_status, int W, int H,
                  const float K[4], float bf, const float *T, int cap, float *xyz, float *sigma_out, uint16_t *pixel, int *n) {
   const size_t np = (size_t)W * (size_t)H;
+  hipLaunchKernelGGL(semidense_key_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->stream, d_status, b->key, (int)np);
+  VO_CHECK_HIP(c, hipGetLastError());
+  return vo_sd_points_keyed(c, b, d_disp, d_sigma, W, H, K, bf, T, cap, xyz, sigma_out, pixel, n);
+}
+
+// the same with b->key already written on c->stream (semidense_temporal.hip: the fused map's pixels, disp = invd and bf = 1)
+int vo_sd_points_keyed(vo_ctx *c, vo_sd_buffers *b, const float *d_disp, const float *d_sigma, int W, int H, const float K[4], float bf,
+                       const float *T, int cap, float *xyz, float *sigma_out, uint16_t *pixel, int *n) {
+  const size_t np = (size_t)W * (size_t)H;
   int rc = sd_points_alloc(c, b);
   if (rc) return rc;
   hipStream_t s = c->stream;
-  hipLaunchKernelGGL(semidense_key_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, d_status, b->key, (int)np);
-  VO_CHECK_HIP(c, hipGetLastError());
   CompactArgsHost h;  // the stable compaction: the accepted pixels' indices in raster order
   h.mask = b->key;
   h.n = (int)np;
@@ -307,6 +316,7 @@ int vo_svo_semidense_guard(vo_svo *s, int a, int b) {
 void vo_svo_semidense_free(vo_svo *s) {
   vo_svo_semidense &d = s->sd;
   if (d.have) (void)hipEventSynchronize(d.done);
+  vo_svo_semidense_temporal_free(s);
   vo_sd_buffers_free(&d.buf);
   if (d.fork) (void)hipEventDestroy(d.fork);
   if (d.done) (void)hipEventDestroy(d.done);
@@ -321,6 +331,7 @@ extern "C" int vo_svo_set_semidense(vo_svo *s, const vo_semidense_params *prm, i
   vo_svo_semidense &d = s->sd;
   if (!prm) {
     d.on = false;
+    s->sdt.have = false;  // (the temporal option's map belongs to a keyframe of this option's results)
     return VO_OK;
   }
   if (every != VO_SEMIDENSE_KEYFRAMES && every != VO_SEMIDENSE_FRAMES)

@@ -765,6 +765,8 @@ extern "C" int vo_svo_result(vo_svo *s, vo_svo_frame_info *info) {
   // after the local BA are known; nothing waits for it (the frame's result stands whatever this returns)
   if (s->sd.on && (I.is_keyframe || s->sd.every == VO_SEMIDENSE_FRAMES))
     RC(vo_svo_semidense_enqueue(s, s->slot[S_CL], s->slot[S_CR], I.frame_id, T_wc));
+  // the keyframe's map (vo_svo_set_semidense_temporal): seeded behind a keyframe's static launch, fused with every later frame
+  if (s->sd.on && s->sdt.on) RC(vo_svo_semidense_temporal_enqueue(s, s->slot[S_CL], I.is_keyframe, I.frame_id, T_wc));
   if (g_trace) {
     s->ht.t_ret = svo_now();
     ++s->ht.n_all;

@@ -31,6 +31,17 @@ struct vo_svo_semidense {
   float T_wc[16] = {};
 };
 
+// vo_svo_set_semidense_temporal (semidense_temporal.hip): the last keyframe's left plane and its map. The launches run on the side
+// stream behind the static option's, one after the other (the map needs no second copy), and share its events: `sd.done` is
+// recorded behind each, `sd.busy` takes the current left slot.
+struct vo_svo_semidense_temporal {
+  bool on = false, have = false, mask_on = false;  // switched on; a keyframe has seeded the map; that keyframe carried a mask (buf.mask)
+  vo_semidense_temporal_params prm = {};
+  vo_sdt_buffers buf;
+  int w = 0, h = 0, frame_id = -1, n_fused = 0;
+  float T_wk[16] = {};
+};
+
 struct vo_svo {
   vo_ctx *c = nullptr;
   vo_svo_params prm;
@@ -68,6 +79,7 @@ struct vo_svo {
   vo_driver_mask mask;  // vo_svo_set_mask (MonoVO: vo_mvo_set_mask): the ignore mask the pairs ingested from now on carry
   vo_zncc_gate zncc;    // vo_svo_set_zncc_gate (MonoVO: vo_mvo_set_zncc_gate): the appearance gate of the steady-state frames
   vo_svo_semidense sd;  // vo_svo_set_semidense: semi-dense stereo depth of the keyframes' (or every frame's) own pair
+  vo_svo_semidense_temporal sdt;  // vo_svo_set_semidense_temporal: the keyframe's map, fused with every later frame
   int mono = 0;  // the keyframe storage serves a MonoVO (mono_vo.hip): one observation per keyframe entry, bundled flags
   // all_stkeyframes_ (stats_keyframe): every keyframe's current pose (host) and where its related landmarks' ids are kept
   // on the device (a pool that only grows)
@@ -97,6 +109,8 @@ int vo_svo_lba_update_points(vo_svo *s, const SvoTrackSet &ts, int n);  // a lan
 int vo_svo_semidense_enqueue(vo_svo *s, int slot_l, int slot_r, int frame_id, const float T_wc[16]);  // semidense.hip
 int vo_svo_semidense_guard(vo_svo *s, int a, int b);
 void vo_svo_semidense_free(vo_svo *s);
+int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, int frame_id, const float T_wc[16]);  // semidense_temporal.hip
+void vo_svo_semidense_temporal_free(vo_svo *s);
 
 void svo_mul44(const float A[16], const float B[16], float C[16]);
 void svo_inv_se3(const float T[16], float Ti[16]);

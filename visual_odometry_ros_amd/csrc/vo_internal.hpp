@@ -127,6 +127,7 @@ struct vo_ctx {
   uint8_t *eq_op;  // vo_equalize_image's own storage: a staging plane in front of what a slot has
   // the ZNCC gate of the driver whose frame is in flight (zncc.hip); null: none — the frame operators then launch nothing
   struct vo_zncc_gate *zncc_gate;
+  struct vo_semidense_temporal_state *semidense_t;  // vo_semidense_temporal / vo_semidense_map_seed with host planes: their device copies
   struct vo_semidense_state *semidense;  // vo_semidense_stereo / vo_semidense_points: their planes and scratch (semidense.hip), made on first use
 };
 
@@ -258,6 +259,30 @@ void vo_semidense_free(vo_ctx *c);
 // the launch on c->stream, into device planes (any may be null); wg_accepted (device, may be null): a count per workgroup
 int vo_sd_enqueue(vo_ctx *c, int slot_l, int slot_r, const vo_semidense_params *p, float *disp, float *score, float *sigma, uint8_t *status,
                   int *wg_accepted, int *W_out, int *H_out);
+
+int vo_sd_ctx_buffers(vo_ctx *c, vo_sd_buffers **b);  // the context's own buffers, made on first use
+// the points of DEVICE planes (host outputs), synchronous on c->stream; vo_sd_points_keyed: b->key is written already (the caller's rule)
+int vo_sd_points(vo_ctx *c, vo_sd_buffers *b, const float *d_disp, const float *d_sigma, const uint8_t *d_status, int W, int H,
+                 const float K[4], float bf, const float *T, int cap, float *xyz, float *sigma_out, uint16_t *pixel, int *n);
+int vo_sd_points_keyed(vo_ctx *c, vo_sd_buffers *b, const float *d_disp, const float *d_sigma, int W, int H, const float K[4], float bf,
+                       const float *T, int cap, float *xyz, float *sigma_out, uint16_t *pixel, int *n);
+
+// The temporal semi-dense search (semidense_temporal.hip; include/vo_hip.h, "Semi-dense temporal"): a key plane, the four planes of a
+// map and — the context's operator — the score plane or — a driver's option — the keyframe's ignore mask: one allocation sized by
+// vo_config.max_width x max_height.
+struct vo_sdt_buffers {
+  float *invd = nullptr, *sigma = nullptr, *score = nullptr;
+  uint8_t *n_obs = nullptr, *tstatus = nullptr, *key = nullptr, *mask = nullptr;
+  size_t npix = 0;
+};
+int vo_sdt_buffers_alloc(vo_ctx *c, vo_sdt_buffers *b, bool driver);
+void vo_sdt_buffers_free(vo_sdt_buffers *b);
+void vo_semidense_temporal_free(vo_ctx *c);
+// the launch on c->stream: a DEVICE key plane against the slot's level-0 plane, the map's DEVICE planes updated in place; key_mask:
+// the key pixels' ignore mask (p == null: none), null: the one bound to slot_cur
+int vo_sdt_enqueue(vo_ctx *c, const uint8_t *d_key, int key_stride, const vo_mask_view *key_mask, int slot_cur, const float K[4],
+                   const float T_ck[16], const vo_semidense_temporal_params *p, float *invd, float *sigma, uint8_t *n_obs, uint8_t *tstatus,
+                   float *score);
 
 // Image ingestion (H2D + pyramid chain) enqueues on the side stream when vo_set_ingest_side_stream is on: launchers
 // use c->stream, which this scope points at the ingest stream and restores on exit.
