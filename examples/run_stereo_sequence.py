@@ -17,7 +17,9 @@ PLY per result in DIR (`semidense_<frame id>.ply`: x y z in the world frame and 
 --semidense-temporal [--semidense-min-obs N]: with --semidense, every keyframe's result seeds a map that the following frames
 update (the temporal search and fusion); `semidense_fused_<keyframe's frame id>.ply` holds the map's pixels with at least N (default
 2) observations (N = 1 keeps what the static result alone gave), written when the next keyframe replaces the map and at the end
-of the run."""
+of the run. --semidense-propagate: with --semidense-temporal, a keyframe's map is carried over to the next keyframe (warped under
+the odometry's pose, fused with the new static result) instead of being seeded afresh, so a keyframe's file also holds what earlier
+keyframes observed."""
 import argparse
 import os
 import sys
@@ -81,9 +83,11 @@ def semidense_options(args):
     if args.semidense is None:
         if args.semidense_every is not None or args.semidense_depth is not None:
             raise SystemExit("--semidense-every / --semidense-depth need --semidense DIR")
-        if args.semidense_temporal or args.semidense_min_obs is not None:
-            raise SystemExit("--semidense-temporal / --semidense-min-obs need --semidense DIR")
+        if args.semidense_temporal or args.semidense_min_obs is not None or args.semidense_propagate:
+            raise SystemExit("--semidense-temporal / --semidense-min-obs / --semidense-propagate need --semidense DIR")
         return {}
+    if args.semidense_propagate and not args.semidense_temporal:
+        raise SystemExit("--semidense-propagate needs --semidense-temporal")
     if args.semidense_min_obs is not None and (not args.semidense_temporal or not 1 <= args.semidense_min_obs <= 255):
         raise SystemExit("--semidense-min-obs N: 1..255, with --semidense-temporal")
     z = args.semidense_depth or [3.0]
@@ -94,6 +98,8 @@ def semidense_options(args):
         sd["z_max"] = z[1]
     if args.semidense_temporal:
         sd["temporal"] = True
+    if args.semidense_propagate:
+        sd["propagate"] = True
     return {"semidense": sd}
 
 
@@ -138,6 +144,8 @@ def parse_args(argv=None):
                     help="depth range Z_MIN [Z_MAX] in metres searched by --semidense (default 3, no upper end)")
     ap.add_argument("--semidense-temporal", action="store_true",
                     help="--semidense: fuse every keyframe's depth with the following frames; semidense_fused_<id>.ply per keyframe")
+    ap.add_argument("--semidense-propagate", action="store_true",
+                    help="--semidense-temporal: carry a keyframe's fused map over to the next keyframe instead of seeding it afresh")
     ap.add_argument("--semidense-min-obs", type=int, default=None, metavar="N", help="observations a fused pixel needs (default 2)")
     return ap.parse_args(argv)
 

@@ -437,10 +437,12 @@ int vo_stereo_frame_recoveries(const vo_ctx *ctx);
  *   VO_DBG_SBA_SPLIT      0: the local BA's steady-state iteration runs its dense solve inside the point-update launch (two
  *                         launches per iteration); 1: three launches per iteration (solve and point update apart) — the same
  *                         results, bit for bit (tests compare the two; the A/B lever of the measurement); >= 2: the fused launch
- *                         with at most that many workgroups (tests: every workgroup strides over several landmark groups) */
+ *                         with at most that many workgroups (tests: every workgroup strides over several landmark groups)
+ *   VO_DBG_SDP_STAGE      vo_semidense_map_propagate launches 1: its scatter only (the plane of keys stays as the launch leaves
+ *                         it), 2: its resolve only (on the keys an earlier call left) — what each launch costs (measurement) */
 enum { VO_DBG_FAIL_JOIN = 0, VO_DBG_CONC_GRID = 1, VO_DBG_SBA_LDS_SOLVE = 2, VO_DBG_SKIP_DETECT = 3, VO_OPT_POLL_YIELD = 4,
        VO_DBG_MVO_HOST_ADVANCE = 5, VO_DBG_STAGED_DETECT = 6, VO_DBG_CANDS_IN_FRAME = 7, VO_DBG_SBA_SPLIT = 8,
-       VO_DBG_COUNT = 9 };
+       VO_DBG_SDP_STAGE = 9, VO_DBG_COUNT = 10 };
 int vo_debug_set(vo_ctx *ctx, int key, int value);
 /* Device and pinned-host allocations made on behalf of this context so far (vo_create included). A steady-state frame —
  * keyframes and their local BA included — makes none: tests/test_stereo_vo_gpu.py asserts it. */
@@ -901,6 +903,68 @@ int vo_svo_get_semidense_map(vo_svo *svo, float *invd, float *sigma, uint8_t *n_
                              int *frame_id, float T_wc[16], int *n_fused);
 int vo_svo_get_semidense_map_points(vo_svo *svo, int world, int min_obs, int cap, float *xyz, float *sigma, uint16_t *pixel, int *n,
                                     int *frame_id);
+
+/* ---- Semi-dense propagation: the old keyframe's fused map carried over to the new keyframe ---------------------
+ * A forward warp of the map's pixels into the new keyframe's left image under the odometry's pose, with an occlusion rule, and
+ * a fusion with the new pair's static result. What it gains is coverage and continuity — pixels static refuses, n_obs >= 2 and
+ * narrowed variances survive the keyframe change — not precision on the pixels static measures itself (§19 has the figures).
+ * Only + - x / sqrtf floorf fabsf in float32, every operation rounded on its own (no FMA), in the order written here.
+ * tests/semidense_propagate_restatement.py restates it.
+ *   inputs     the old map: three W x H planes invd f32, sigma f32, n_obs u8, and the old keyframe's left level-0 u8 plane La;
+ *              the new keyframe's left plane Lb (a slot's level 0), 3 <= W, H <= 65535, W H < 2^31, and the ignore mask bound to
+ *              that slot, if any; the new pair's static planes disparity, sigma_invd, status and bf > 0; K = fx, fy, cx, cy;
+ *              T_ba row-major 4 x 4, X_b = R X_a + t.
+ *   params     min_obs 1..255; max_diff 0..255 (255: no gate); chi > 0; sigma_add >= 0 [1/m], all finite.
+ *   source     every pixel (x, y) of the old map, raster index i = y W + x, with n_obs >= min_obs, sigma > 0 and invd > 0. With
+ *              xc, yc, u, v, a_i as in the temporal block: D = a2 + invd t2. not (D > 0.1): dropped. invd_b = invd / D;
+ *              p = (fx ((a0 + invd t0) / D) + cx, fy ((a1 + invd t1) / D) + cy); sigma_w = (sigma fabsf(a2)) / (D D) (the
+ *              derivative of invd / (a2 + invd t2)); sigma_b = sqrtf(sigma_w sigma_w + sigma_add sigma_add). A source whose invd_b
+ *              or sigma_b is not in (0, FLT_MAX] is dropped (so that the new map's entries are sources again, and NaN never
+ *              enters it).
+ *   target     X = (int)floorf(p_x + 0.5f) where that value lies in [-2^20, 2^22], else -2^20; Y likewise. The source is kept
+ *              where, tested in this order, 1 <= X <= W-2 and 1 <= Y <= H-2; the mask byte at (X, Y) is not 0;
+ *              |La(x, y) - Lb(X, Y)| <= max_diff as integers.
+ *   occlusion  among the sources kept for one target the largest invd_b (the nearest) wins; on equal bits the smallest i. This
+ *              is a property of the set of sources, not of any order of arrival.
+ *   resolve    per pixel j of the new map, static where status == 1 with rho_s = disparity / bf, sig_s = sigma_invd (as
+ *              vo_semidense_map_seed forms them):
+ *                neither            invd = sigma = 0, n_obs = 0, origin 0
+ *                static only        rho_s, sig_s, n_obs = 1, origin 1
+ *                winner only        invd_b, sigma_b, the source's n_obs, origin 2
+ *                both               dd = invd_b - rho_s, s2 = sigma_b sigma_b, m2 = sig_s sig_s, sum = s2 + m2. Consistent where
+ *                                   sum > 0 and dd dd <= (chi chi) sum: the temporal block's product with the winner as the prior,
+ *                                   invd = (invd_b m2 + rho_s s2) / sum, sigma = sqrtf((s2 m2) / sum), n_obs = min(n_obs + 1, 255),
+ *                                   origin 3. Else the fresh measurement replaces the stale one: rho_s, sig_s, n_obs = 1, origin 4.
+ *              tstatus = 0 everywhere. origin u8 and src i32 (the winner's i, -1 where there is none) are diagnostic planes.
+ * vo_semidense_map_propagate: the operator, synchronous. old_* and key_plane (key_stride bytes per row), the static planes and
+ * the outputs are host planes, or all device planes with on_device; the new planes may not be the old ones (resolve reads the
+ * old map while it writes the new one). origin and src may be NULL. The planes may not exceed vo_config.max_width x max_height.
+ *
+ * StereoVO: vo_svo_set_semidense_propagate(svo, prm) — NULL = off — needs vo_svo_set_semidense_temporal on and makes its only
+ * allocation (the plane of keys, a second set of map planes, origin) at the first enable; VO_ERR_INVALID while a frame is in
+ * flight or on a mono driver. With it off nothing changes; with it on the odometry's results are the same bits. At a keyframe
+ * that has a predecessor since the option was switched on, T_ba = inverseSE3(T_wc_new) * T_wk_old is formed on the host as the
+ * temporal block forms T_ck, and on the side stream behind the static launch: the scatter (old map, old key plane, the new left
+ * slot's level 0 and mask), the key-plane and mask copies, the resolve in place of the seed; then the map sets are swapped. The
+ * first keyframe, and the first after the option (or the temporal one) was off, seed the map from the static result alone — the
+ * same values as without the option, origin 0 / 1. The map is not re-anchored when the local BA moves a keyframe.
+ * vo_svo_get_semidense_origin: the map's origin plane (may be NULL), size (0 x 0 before the first keyframe since the option was
+ * switched on), from_frame_id = the frame_id
+ * of the keyframe the map was propagated from, -1 where it was seeded without a predecessor; waits for the side stream's last
+ * launch only; VO_ERR_INVALID while a frame is in flight or with the option off. Not for MonoVO or vo_batch streams. */
+typedef struct {
+  int min_obs;      /* 1 */
+  int max_diff;     /* 30 */
+  float chi;        /* 3.0 */
+  float sigma_add;  /* 0.01 */
+} vo_semidense_propagate_params;
+int vo_semidense_propagate_default_params(vo_semidense_propagate_params *prm);
+int vo_semidense_map_propagate(vo_ctx *ctx, const float *old_invd, const float *old_sigma, const uint8_t *old_n_obs, const uint8_t *key_plane,
+                               int key_stride, int slot_new, const float *disparity, const float *sigma_invd, const uint8_t *status, float bf,
+                               const float K[4], const float T_ba[16], const vo_semidense_propagate_params *prm, float *invd, float *sigma,
+                               uint8_t *n_obs, uint8_t *tstatus, uint8_t *origin, int32_t *src, int on_device);
+int vo_svo_set_semidense_propagate(vo_svo *svo, const vo_semidense_propagate_params *prm);
+int vo_svo_get_semidense_origin(vo_svo *svo, uint8_t *origin, int *width, int *height, int *from_frame_id);
 
 /* ---- undistortion / stereo rectification in front of the trackers ----------
  * core/visual_odometry/camera.cpp. A context holds the maps of two cameras

@@ -114,6 +114,10 @@ class SemiDenseTemporalParams(C.Structure):  # vo_semidense_temporal_params
                 ("z_min", C.c_float), ("z_max", C.c_float), ("max_search", C.c_int), ("j_min", C.c_float)]
 
 
+class SemiDensePropagateParams(C.Structure):  # vo_semidense_propagate_params
+    _fields_ = [("min_obs", C.c_int), ("max_diff", C.c_int), ("chi", C.c_float), ("sigma_add", C.c_float)]
+
+
 class FivePointParams(C.Structure):
     _fields_ = [("thres_px", C.c_float), ("confidence", C.c_float), ("max_iters", C.c_int), ("seed", C.c_ulonglong)]
 
@@ -164,6 +168,7 @@ SYMBOLS = [
     "vo_svo_set_semidense", "vo_svo_get_semidense", "vo_svo_get_semidense_points",
     "vo_semidense_temporal_default_params", "vo_semidense_map_seed", "vo_semidense_temporal", "vo_semidense_map_points",
     "vo_svo_set_semidense_temporal", "vo_svo_get_semidense_map", "vo_svo_get_semidense_map_points",
+    "vo_semidense_propagate_default_params", "vo_semidense_map_propagate", "vo_svo_set_semidense_propagate", "vo_svo_get_semidense_origin",
 ]
 
 _lib = None
@@ -276,6 +281,10 @@ def load():
     lib.vo_svo_set_semidense_temporal.argtypes = [vp, vp]
     lib.vo_svo_get_semidense_map.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.vo_svo_get_semidense_map_points.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp]
+    lib.vo_semidense_propagate_default_params.argtypes = [vp]
+    lib.vo_semidense_map_propagate.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci]
+    lib.vo_svo_set_semidense_propagate.argtypes = [vp, vp]
+    lib.vo_svo_get_semidense_origin.argtypes = [vp, vp, vp, vp, vp]
     lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_five_point_destroy.argtypes = [vp]
     lib.vo_five_point_destroy.restype = None

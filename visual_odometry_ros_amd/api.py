@@ -133,6 +133,25 @@ def _semidense_temporal_params(lib, params):
     return p
 
 
+class SemiDensePropagated(collections.namedtuple("SemiDensePropagated", "invd sigma n_obs tstatus origin src")):
+    """A map carried over to a new keyframe (include/vo_hip.h, "Semi-dense propagation"): the map's four planes, origin uint8
+    (0 nothing, 1 static only, 2 propagated only, 3 fused, 4 static replaced an inconsistent propagated value) and src int32 (the
+    winning source's raster index in the old map, -1 where none)."""
+    __slots__ = ()
+
+
+def _semidense_propagate_params(lib, params):
+    """keyword parameters -> vo_semidense_propagate_params: the C defaults, then the caller's fields"""
+    p = _capi.SemiDensePropagateParams()
+    lib.vo_semidense_propagate_default_params(C.byref(p))
+    known = {f[0] for f in _capi.SemiDensePropagateParams._fields_}
+    for k, v in dict(params).items():
+        if k not in known:
+            raise ValueError(f"semi-dense propagation: unknown parameter {k!r}; known: {sorted(known)}")
+        setattr(p, k, v)
+    return p
+
+
 def _zncc_gate_arg(gate, stereo):
     """zncc_gate= / setZnccGate: None -> off; dict(thres=, win=15, pattern="centered", pairs=("temporal",)) -> the C call's
     (pairs, win, pattern, thres). pairs: names out of "temporal", "stereo" (StereoVO only)."""
@@ -194,6 +213,7 @@ class Context:
 
     DBG_FAIL_JOIN, DBG_CONC_GRID, DBG_SBA_LDS_SOLVE, DBG_SKIP_DETECT, OPT_POLL_YIELD, DBG_MVO_HOST_ADVANCE, DBG_STAGED_DETECT, DBG_CANDS_IN_FRAME = 0, 1, 2, 3, 4, 5, 6, 7
     DBG_SBA_SPLIT = 8
+    DBG_SDP_STAGE = 9
 
     @property
     def sum_order(self):
@@ -398,6 +418,44 @@ class Context:
         self.check(self.lib.vo_semidense_temporal(self._h, pk, stride, int(key_on_device is not None), int(slot_cur), Ka.ctypes.data, Ta.ctypes.data,
                                                   C.byref(p), invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data, ts.ctypes.data, score.ctypes.data, 0))
         return SemiDenseMap(invd, sigma, n_obs, ts, score, None, None, None)
+
+    def semiDenseMapPropagate(self, old_map, key, slot_new, static, bf, K, T_ba, out=None, key_on_device=None, **params):
+        """The old keyframe's map carried over to the keyframe whose left image is in slot_new (include/vo_hip.h, "Semi-dense
+        propagation"): old_map a SemiDenseMap / dict(invd=, sigma=, n_obs=), key the old keyframe's left u8 plane, static a
+        SemiDenseResult / dict(disparity=, sigma_invd=, status=) of the new pair, T_ba 4 x 4 (X_b = R X_a + t); slot_new's ignore
+        mask applies to the targets. Returns a SemiDensePropagated. With out=dict(invd=, sigma=, n_obs=, tstatus=[, origin=, src=])
+        of DEVICE addresses every plane is a DEVICE address (key with key_on_device=stride) and None is returned. params: the
+        fields of vo_semidense_propagate_params."""
+        p = _semidense_propagate_params(self.lib, params)
+        Ka = np.ascontiguousarray(K, np.float32).reshape(4)
+        Ta = np.ascontiguousarray(T_ba, np.float32).reshape(4, 4)
+        gm = (lambda k: getattr(old_map, k)) if isinstance(old_map, tuple) else (lambda k: old_map[k])
+        gs = (lambda k: getattr(static, k)) if isinstance(static, tuple) else (lambda k: static[k])
+        if out is not None:
+            if key_on_device is None:
+                raise ValueError("semiDenseMapPropagate: with out= every plane is a device address: key_on_device=stride")
+            opt = lambda k: C.c_void_p(out[k]) if out.get(k) else None
+            self.check(self.lib.vo_semidense_map_propagate(
+                self._h, *(C.c_void_p(gm(k)) for k in ("invd", "sigma", "n_obs")), C.c_void_p(key), int(key_on_device), int(slot_new),
+                *(C.c_void_p(gs(k)) for k in ("disparity", "sigma_invd", "status")), float(bf), Ka.ctypes.data, Ta.ctypes.data, C.byref(p),
+                *(C.c_void_p(out[k]) for k in ("invd", "sigma", "n_obs", "tstatus")), opt("origin"), opt("src"), 1))
+            return None
+        w, h = self.slot_image_size(slot_new)
+        ka = _u8(key)
+        o_invd, o_sigma = np.ascontiguousarray(gm("invd"), np.float32), np.ascontiguousarray(gm("sigma"), np.float32)
+        o_no = np.ascontiguousarray(gm("n_obs"), np.uint8)
+        d, sg = np.ascontiguousarray(gs("disparity"), np.float32), np.ascontiguousarray(gs("sigma_invd"), np.float32)
+        st = np.ascontiguousarray(gs("status"), np.uint8)
+        for a in (ka, o_invd, o_sigma, o_no, d, sg, st):
+            if a.shape != (h, w):
+                raise ValueError(f"every plane must be ({h}, {w}) like slot {slot_new}'s image")
+        invd, sigma = np.zeros((h, w), np.float32), np.zeros((h, w), np.float32)
+        n_obs, ts, origin, src = np.zeros((h, w), np.uint8), np.zeros((h, w), np.uint8), np.zeros((h, w), np.uint8), np.zeros((h, w), np.int32)
+        self.check(self.lib.vo_semidense_map_propagate(
+            self._h, o_invd.ctypes.data, o_sigma.ctypes.data, o_no.ctypes.data, ka.ctypes.data, ka.strides[0], int(slot_new), d.ctypes.data,
+            sg.ctypes.data, st.ctypes.data, float(bf), Ka.ctypes.data, Ta.ctypes.data, C.byref(p), invd.ctypes.data, sigma.ctypes.data,
+            n_obs.ctypes.data, ts.ctypes.data, origin.ctypes.data, src.ctypes.data, 0))
+        return SemiDensePropagated(invd, sigma, n_obs, ts, origin, src)
 
     def semiDenseMapPoints(self, invd, sigma, n_obs, K, T=None, min_obs=1, capacity=None, on_device=None):
         """The map's pixels with n_obs >= min_obs in raster order: (xyz float32 [n, 3], sigma float32 [n], pixel uint16 [n, 2]) with
@@ -1325,7 +1383,8 @@ class StereoVO:
                  debug_image=False, pose_covariance=False, sigma_px=0.0, mask=None, zncc_gate=None, semidense=None):
         """debug_image=True: every tracked frame draws the reference's img_debug_ on the device (getDebugImage).
         semidense: dict of semi-dense stereo parameters (setSemiDense; "every": "keyframe" or "frame") — depth of the keyframes' pairs;
-        its "temporal": True or dict(z_max=..., max_search=...) also switches setSemiDenseTemporal on.
+        its "temporal": True or dict(z_max=..., max_search=...) also switches setSemiDenseTemporal on, and with it
+        "propagate": True or dict(min_obs=, max_diff=, chi=, sigma_add=) setSemiDensePropagate.
         mask: the ignore mask every pair carries from the first one on (setMask).
         zncc_gate: dict(thres=, win=15, pattern="centered", pairs=("temporal",)) — the appearance gate (setZnccGate).
         pose_covariance=True: every frame chains the covariance of its pose on the device (getPoseCovariance); sigma_px > 0
@@ -1357,10 +1416,14 @@ class StereoVO:
             self.setZnccGate(zncc_gate)
         if semidense is not None:
             sd = dict(semidense)
-            temporal = sd.pop("temporal", None)
+            temporal, propagate = sd.pop("temporal", None), sd.pop("propagate", None)
+            if propagate and not temporal:
+                raise ValueError('semidense: "propagate" needs "temporal"')
             self.setSemiDense(sd, every=sd.pop("every", "keyframe"))
             if temporal:
                 self.setSemiDenseTemporal({} if temporal is True else temporal)
+            if propagate:
+                self.setSemiDensePropagate({} if propagate is True else propagate)
         self._info = SvoFrameInfo()
         self.stats_frame = []  # AlgorithmStatistics::FrameStatistics::Twc per frame (stereo_vo.cpp:979-980)
 
@@ -1523,6 +1586,30 @@ class StereoVO:
         self.ctx.check(self.lib.vo_svo_get_semidense_map(self._h, invd.ctypes.data, sg.ctypes.data, no.ctypes.data, ts.ctypes.data, C.byref(w),
                                                          C.byref(h), C.byref(fid), T.ctypes.data, C.byref(nf)))
         return SemiDenseMap(invd, sg, no, ts, None, fid.value, T, nf.value)
+
+    def setSemiDensePropagate(self, params):
+        """The map carried over to the next keyframe (include/vo_hip.h, "Semi-dense propagation"): at a keyframe the old map is
+        warped into the new keyframe under the odometry's pose and fused with its static result instead of being thrown away, so
+        getSemiDensePoints(fused=True, min_obs=2) has points on a keyframe frame too; the odometry's results do not change. params:
+        dict(min_obs=, max_diff=, chi=, sigma_add=) ({}: the defaults), None: off. Needs setSemiDenseTemporal. Refused while a
+        frame is in flight."""
+        if params is None:
+            self.ctx.check(self.lib.vo_svo_set_semidense_propagate(self._h, None))
+            return
+        p = _semidense_propagate_params(self.lib, params)
+        self.ctx.check(self.lib.vo_svo_set_semidense_propagate(self._h, C.byref(p)))
+
+    def getSemiDenseOrigin(self):
+        """(origin uint8 (height, width), from_frame_id) of the last keyframe's map — 0 nothing, 1 static only, 2 propagated only,
+        3 fused, 4 static replaced an inconsistent propagated value; from_frame_id: the keyframe the map was propagated from, -1
+        where it was seeded without a predecessor. None before a keyframe. Waits for the side stream's last launch only."""
+        w, h, fid = C.c_int(), C.c_int(), C.c_int()
+        self.ctx.check(self.lib.vo_svo_get_semidense_origin(self._h, None, C.byref(w), C.byref(h), C.byref(fid)))
+        if w.value <= 0:
+            return None
+        origin = np.zeros((h.value, w.value), np.uint8)
+        self.ctx.check(self.lib.vo_svo_get_semidense_origin(self._h, origin.ctypes.data, C.byref(w), C.byref(h), C.byref(fid)))
+        return origin, fid.value
 
     def getSemiDensePoints(self, world=True, capacity=None, fused=False, min_obs=2):
         """The accepted pixels of the last semi-dense result as points, raster order: dict(xyz float32 [n, 3] — in the world frame

@@ -482,6 +482,9 @@ class StereoVO {
   // the temporal half of that prototype (vo::StereoVO::setSemiDenseTemporal): the keyframe's depth fused with the following frames;
   // getSemiDenseMapPoints() is the last keyframe's map, the pixels seen at least min_obs times
   void setSemiDenseTemporal(const vo_semidense_temporal_params *prm) { impl_.setSemiDenseTemporal(prm); }
+  // the map carried over to the next keyframe instead of being seeded afresh (vo::StereoVO::setSemiDensePropagate): with it
+  // getSemiDenseMapPoints() has points on a keyframe frame too
+  void setSemiDensePropagate(const vo_semidense_propagate_params *prm) { impl_.setSemiDensePropagate(prm); }
   PointVec getSemiDenseMapPoints(bool world = true, int min_obs = 2) {
     vo::PointVec v;
     impl_.getSemiDenseMapPoints(v, nullptr, world, min_obs);

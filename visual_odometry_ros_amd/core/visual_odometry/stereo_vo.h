@@ -284,6 +284,28 @@ class StereoVO {
                                                        sigma ? sigma->data() : nullptr, nullptr, &n, &fid));
     return fid >= 0;
   }
+  // The map carried over to the next keyframe (vo_svo_set_semidense_propagate; include/vo_hip.h, "Semi-dense propagation"): at a
+  // keyframe the old map is warped into the new one under the odometry's pose and fused with its static result, so that
+  // getSemiDenseMapPoints has points on a keyframe frame too. Needs setSemiDenseTemporal. prm = nullptr: off. Throws while a frame
+  // is in flight.
+  static vo_semidense_propagate_params defaultSemiDensePropagateParams() {
+    vo_semidense_propagate_params p;
+    vo_semidense_propagate_default_params(&p);
+    return p;
+  }
+  void setSemiDensePropagate(const vo_semidense_propagate_params *prm) { ctx_->check(vo_svo_set_semidense_propagate(svo_, prm)); }
+  // the map's origin plane (0 nothing, 1 static, 2 propagated, 3 fused, 4 static replaced a propagated value), width x height;
+  // from_frame_id: the keyframe the map was propagated from, -1: seeded without a predecessor. false (and empty) before a keyframe.
+  bool getSemiDenseOrigin(std::vector<uint8_t> &origin, int *width = nullptr, int *height = nullptr, int *from_frame_id = nullptr) {
+    int w = 0, h = 0, from = -1;
+    ctx_->check(vo_svo_get_semidense_origin(svo_, nullptr, &w, &h, &from));
+    origin.resize((size_t)w * (size_t)h);
+    if (w > 0) ctx_->check(vo_svo_get_semidense_origin(svo_, origin.data(), &w, &h, &from));
+    if (width) *width = w;
+    if (height) *height = h;
+    if (from_frame_id) *from_frame_id = from;
+    return w > 0;
+  }
   // NOT in the reference: CLAHE on every image before the tracker (vo::Context::setEqualize on this driver's context): legal
   // between frames, applies to the images handed over from now on
   void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) { ctx_->setEqualize(mode, clip_limit, tiles_x, tiles_y); }

@@ -57,6 +57,7 @@ int vo_sdt_buffers_alloc(vo_ctx *c, vo_sdt_buffers *b, bool driver) {
   const size_t n = (size_t)c->cfg.max_width * (size_t)c->cfg.max_height;
   VO_CHECK_HIP(c, hipSetDevice(c->device));
   VO_CHECK_HIP(c, vo_dev_malloc(c, (void **)&b->invd, n * ((driver ? 2 : 3) * sizeof(float) + (driver ? 4 : 3)) + 64));
+  b->base = b->invd;
   b->sigma = b->invd + n;
   float *end = b->sigma + n;
   if (!driver) b->score = end, end += n;
@@ -68,7 +69,7 @@ int vo_sdt_buffers_alloc(vo_ctx *c, vo_sdt_buffers *b, bool driver) {
   return VO_OK;
 }
 void vo_sdt_buffers_free(vo_sdt_buffers *b) {
-  if (b->invd) (void)hipFree(b->invd);
+  if (b->base) (void)hipFree(b->base);
   *b = vo_sdt_buffers();
 }
 
@@ -81,7 +82,7 @@ void vo_semidense_temporal_free(vo_ctx *c) {
   delete c->semidense_t;
   c->semidense_t = nullptr;
 }
-static int sdt_ctx_buffers(vo_ctx *c, vo_sdt_buffers **b) {
+int vo_sdt_ctx_buffers(vo_ctx *c, vo_sdt_buffers **b) {
   if (!c->semidense_t) c->semidense_t = new vo_semidense_temporal_state();
   *b = &c->semidense_t->buf;
   return vo_sdt_buffers_alloc(c, *b, false);
@@ -172,7 +173,7 @@ extern "C" int vo_semidense_map_seed(vo_ctx *c, const float *disparity, const fl
   vo_sd_buffers *in;
   vo_sdt_buffers *b;
   int rc = vo_sd_ctx_buffers(c, &in);
-  if (rc >= 0) rc = sdt_ctx_buffers(c, &b);
+  if (rc >= 0) rc = vo_sdt_ctx_buffers(c, &b);
   if (rc) return rc;
   VO_CHECK_HIP(c, hipMemcpyAsync(in->disp, disparity, np * sizeof(float), hipMemcpyHostToDevice, s));
   VO_CHECK_HIP(c, hipMemcpyAsync(in->sigma, sigma_invd, np * sizeof(float), hipMemcpyHostToDevice, s));
@@ -199,7 +200,7 @@ extern "C" int vo_semidense_temporal(vo_ctx *c, const uint8_t *key_plane, int ke
   const size_t np = (size_t)W * (size_t)H;
   vo_sdt_buffers *b = nullptr;
   if (!key_on_device || !on_device) {
-    const int rc = sdt_ctx_buffers(c, &b);
+    const int rc = vo_sdt_ctx_buffers(c, &b);
     if (rc) return rc;
   }
   const uint8_t *d_key = key_plane;
@@ -272,6 +273,9 @@ extern "C" int vo_semidense_map_points(vo_ctx *c, const float *invd, const float
 // the side stream: the left level-0 plane is copied into the option's key plane and the map is seeded from the static planes behind
 // it. At any later frame one launch reads that frame's left slot and the key plane, behind a fork event of the main stream. `sd.done`
 // is recorded again behind either, so that the guard and the getters of both options wait for the side stream's last launch.
+// With vo_svo_set_semidense_propagate on, a keyframe with a predecessor runs the propagation's scatter in front of the copies and
+// its resolve in place of the seed (semidense_propagate.hip); a keyframe without one runs the resolve alone, which then writes the
+// seed's values.
 int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, int frame_id, const float T_wc[16]) {
   vo_ctx *c = s->c;
   vo_svo_semidense &d = s->sd;
@@ -281,6 +285,12 @@ int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, in
   if (is_keyframe) {
     const vo_pyramid &P = c->slots[slot_l];
     const size_t np = (size_t)d.w * (size_t)d.h;
+    // vo_svo_set_semidense_propagate: the old map is warped into this keyframe before its key plane is overwritten
+    const bool propagate = s->sdp.on, chain = propagate && t.have && s->sdp.chain && t.w == d.w && t.h == d.h;
+    if (chain) {
+      const int rc = vo_svo_semidense_propagate_scatter(s, slot_l, T_wc);
+      if (rc) return rc;
+    }
     VO_CHECK_HIP(c, hipMemcpy2DAsync(t.buf.key, (size_t)d.w, P.lv[0].origin(), (size_t)P.lv[0].stride, (size_t)d.w, (size_t)d.h,
                                      hipMemcpyDeviceToDevice, side));
     // the keyframe's own ignore mask goes with its plane: vo_svo_set_mask may change what later pairs carry
@@ -293,11 +303,16 @@ int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, in
     t.mask_on = mv.p != nullptr && mv.w == d.w && mv.h == d.h;
     if (t.mask_on)
       VO_CHECK_HIP(c, hipMemcpy2DAsync(t.buf.mask, (size_t)d.w, mv.p, (size_t)mv.stride, (size_t)d.w, (size_t)d.h, hipMemcpyDeviceToDevice, side));
-    sdt_seed_launch(side, d.buf.disp, d.buf.sigma, d.buf.status, d.prm.bf, t.buf.invd, t.buf.sigma, t.buf.n_obs, t.buf.tstatus, np);
-    VO_CHECK_HIP(c, hipGetLastError());
-    t.have = true;
     t.w = d.w;
     t.h = d.h;
+    if (propagate) {
+      const int rc2 = vo_svo_semidense_propagate_resolve(s, chain);
+      if (rc2) return rc2;
+    } else {
+      sdt_seed_launch(side, d.buf.disp, d.buf.sigma, d.buf.status, d.prm.bf, t.buf.invd, t.buf.sigma, t.buf.n_obs, t.buf.tstatus, np);
+      VO_CHECK_HIP(c, hipGetLastError());
+    }
+    t.have = true;
     t.frame_id = frame_id;
     t.n_fused = 0;
     memcpy(t.T_wk, T_wc, sizeof(t.T_wk));
@@ -325,6 +340,7 @@ int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, in
 }
 
 void vo_svo_semidense_temporal_free(vo_svo *s) {
+  vo_svo_semidense_propagate_free(s);
   vo_sdt_buffers_free(&s->sdt.buf);
   s->sdt = vo_svo_semidense_temporal();
 }

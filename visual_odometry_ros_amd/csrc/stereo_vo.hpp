@@ -42,6 +42,18 @@ struct vo_svo_semidense_temporal {
   float T_wk[16] = {};
 };
 
+// vo_svo_set_semidense_propagate (semidense_propagate.hip): at a keyframe the temporal option's map is warped into the new keyframe
+// and fused with its static result instead of being seeded afresh. `buf` holds the keys, the map's other set of planes (resolve
+// reads the old map while it writes the new one; the sets are swapped behind it) and origin. chain: the map on the device has been
+// written by a keyframe since the option was switched on, so the next keyframe has a predecessor.
+struct vo_svo_semidense_propagate {
+  bool on = false, chain = false;
+  vo_semidense_propagate_params prm = {};
+  vo_sdp_buffers buf;
+  int from_frame_id = -1;
+  float T_ba[16] = {};
+};
+
 struct vo_svo {
   vo_ctx *c = nullptr;
   vo_svo_params prm;
@@ -80,6 +92,7 @@ struct vo_svo {
   vo_zncc_gate zncc;    // vo_svo_set_zncc_gate (MonoVO: vo_mvo_set_zncc_gate): the appearance gate of the steady-state frames
   vo_svo_semidense sd;  // vo_svo_set_semidense: semi-dense stereo depth of the keyframes' (or every frame's) own pair
   vo_svo_semidense_temporal sdt;  // vo_svo_set_semidense_temporal: the keyframe's map, fused with every later frame
+  vo_svo_semidense_propagate sdp;  // vo_svo_set_semidense_propagate: that map carried over to the next keyframe
   int mono = 0;  // the keyframe storage serves a MonoVO (mono_vo.hip): one observation per keyframe entry, bundled flags
   // all_stkeyframes_ (stats_keyframe): every keyframe's current pose (host) and where its related landmarks' ids are kept
   // on the device (a pool that only grows)
@@ -111,6 +124,11 @@ int vo_svo_semidense_guard(vo_svo *s, int a, int b);
 void vo_svo_semidense_free(vo_svo *s);
 int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, int frame_id, const float T_wc[16]);  // semidense_temporal.hip
 void vo_svo_semidense_temporal_free(vo_svo *s);
+// semidense_propagate.hip, both on the side stream at a keyframe with the option on: the scatter in front of the key-plane copy
+// (chain only; it reads the old map and key plane), the resolve in place of the seed (it swaps the map sets)
+int vo_svo_semidense_propagate_scatter(vo_svo *s, int slot_l, const float T_wc[16]);
+int vo_svo_semidense_propagate_resolve(vo_svo *s, bool chain);
+void vo_svo_semidense_propagate_free(vo_svo *s);
 
 void svo_mul44(const float A[16], const float B[16], float C[16]);
 void svo_inv_se3(const float T[16], float Ti[16]);

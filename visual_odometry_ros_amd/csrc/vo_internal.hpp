@@ -129,6 +129,7 @@ struct vo_ctx {
   struct vo_zncc_gate *zncc_gate;
   struct vo_semidense_temporal_state *semidense_t;  // vo_semidense_temporal / vo_semidense_map_seed with host planes: their device copies
   struct vo_semidense_state *semidense;  // vo_semidense_stereo / vo_semidense_points: their planes and scratch (semidense.hip), made on first use
+  struct vo_semidense_propagate_state *semidense_p;  // vo_semidense_map_propagate: its keys and, for host planes, the new map's device copies
 };
 
 static inline hipError_t vo_dev_malloc(vo_ctx *c, void **p, size_t bytes) {
@@ -274,15 +275,32 @@ struct vo_sdt_buffers {
   float *invd = nullptr, *sigma = nullptr, *score = nullptr;
   uint8_t *n_obs = nullptr, *tstatus = nullptr, *key = nullptr, *mask = nullptr;
   size_t npix = 0;
+  void *base = nullptr;  // the allocation (a driver's propagation swaps the map's four planes with those of its own set)
 };
 int vo_sdt_buffers_alloc(vo_ctx *c, vo_sdt_buffers *b, bool driver);
 void vo_sdt_buffers_free(vo_sdt_buffers *b);
 void vo_semidense_temporal_free(vo_ctx *c);
+int vo_sdt_ctx_buffers(vo_ctx *c, vo_sdt_buffers **b);  // the context's own buffers, made on first use
 // the launch on c->stream: a DEVICE key plane against the slot's level-0 plane, the map's DEVICE planes updated in place; key_mask:
 // the key pixels' ignore mask (p == null: none), null: the one bound to slot_cur
 int vo_sdt_enqueue(vo_ctx *c, const uint8_t *d_key, int key_stride, const vo_mask_view *key_mask, int slot_cur, const float K[4],
                    const float T_ck[16], const vo_semidense_temporal_params *p, float *invd, float *sigma, uint8_t *n_obs, uint8_t *tstatus,
                    float *score);
+
+// The semi-dense propagation (semidense_propagate.hip; include/vo_hip.h, "Semi-dense propagation"): the plane of keys (all 0 between
+// calls: zeroed at allocation, every resolve launch stores 0 back), a set of map planes, origin and — the context's operator — src:
+// one allocation sized by vo_config.max_width x max_height.
+struct vo_sdp_buffers {
+  void *base = nullptr;
+  unsigned long long *keys = nullptr;
+  float *invd = nullptr, *sigma = nullptr;
+  int32_t *src = nullptr;
+  uint8_t *n_obs = nullptr, *tstatus = nullptr, *origin = nullptr;
+  size_t npix = 0;
+};
+int vo_sdp_buffers_alloc(vo_ctx *c, vo_sdp_buffers *b, bool driver);
+void vo_sdp_buffers_free(vo_sdp_buffers *b);
+void vo_semidense_propagate_free(vo_ctx *c);
 
 // Image ingestion (H2D + pyramid chain) enqueues on the side stream when vo_set_ingest_side_stream is on: launchers
 // use c->stream, which this scope points at the ingest stream and restores on exit.
