@@ -19,7 +19,11 @@ update (the temporal search and fusion); `semidense_fused_<keyframe's frame id>.
 2) observations (N = 1 keeps what the static result alone gave), written when the next keyframe replaces the map and at the end
 of the run. --semidense-propagate: with --semidense-temporal, a keyframe's map is carried over to the next keyframe (warped under
 the odometry's pose, fused with the new static result) instead of being seeded afresh, so a keyframe's file also holds what earlier
-keyframes observed."""
+keyframes observed. --semidense-align FILE: with --semidense-temporal, every frame that is not a keyframe aligns its left image
+photometrically against the keyframe's map, from the odometry's pose (a second pose estimate; nothing uses it); one line per frame:
+frame id, keyframe's frame id (-1 at a keyframe frame), status (0 converged, 1 max_iters, 2 too few pixels, 3 singular, 4 none),
+iterations, pixel count, rms in grey levels, the 12 numbers of the aligned [R|t] of T_wc, and its translation [m] and rotation
+[degrees] distance to the odometry's pose."""
 import argparse
 import os
 import sys
@@ -83,11 +87,13 @@ def semidense_options(args):
     if args.semidense is None:
         if args.semidense_every is not None or args.semidense_depth is not None:
             raise SystemExit("--semidense-every / --semidense-depth need --semidense DIR")
-        if args.semidense_temporal or args.semidense_min_obs is not None or args.semidense_propagate:
-            raise SystemExit("--semidense-temporal / --semidense-min-obs / --semidense-propagate need --semidense DIR")
+        if args.semidense_temporal or args.semidense_min_obs is not None or args.semidense_propagate or args.semidense_align:
+            raise SystemExit("--semidense-temporal / --semidense-min-obs / --semidense-propagate / --semidense-align need --semidense DIR")
         return {}
     if args.semidense_propagate and not args.semidense_temporal:
         raise SystemExit("--semidense-propagate needs --semidense-temporal")
+    if args.semidense_align and not args.semidense_temporal:
+        raise SystemExit("--semidense-align needs --semidense-temporal")
     if args.semidense_min_obs is not None and (not args.semidense_temporal or not 1 <= args.semidense_min_obs <= 255):
         raise SystemExit("--semidense-min-obs N: 1..255, with --semidense-temporal")
     z = args.semidense_depth or [3.0]
@@ -100,7 +106,19 @@ def semidense_options(args):
         sd["temporal"] = True
     if args.semidense_propagate:
         sd["propagate"] = True
+    if args.semidense_align:
+        sd["align"] = True
     return {"semidense": sd}
+
+
+def align_line(a, T_wc):
+    """one line of --semidense-align: a = getSemiDenseAlign() of the frame whose odometry pose is T_wc"""
+    E = np.linalg.inv(np.asarray(T_wc, np.float64)) @ a.T_wc.astype(np.float64)
+    R = E[:3, :3]
+    s = 0.5 * np.linalg.norm([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    dt, dr = (float(np.linalg.norm(E[:3, 3])), float(np.degrees(np.arcsin(min(s, 1.0))))) if a.status != 4 else (0.0, 0.0)
+    return (f"{a.frame_id} {a.key_frame_id} {a.status} {a.iters} {a.count} {a.rms:.4f} " + " ".join(f"{v:.6f}" for v in a.T_wc[:3].reshape(-1)) +
+            f" {dt:.6f} {dr:.6f}\n")
 
 
 def write_ply(path, xyz, sigma_invd):
@@ -146,6 +164,8 @@ def parse_args(argv=None):
                     help="--semidense: fuse every keyframe's depth with the following frames; semidense_fused_<id>.ply per keyframe")
     ap.add_argument("--semidense-propagate", action="store_true",
                     help="--semidense-temporal: carry a keyframe's fused map over to the next keyframe instead of seeding it afresh")
+    ap.add_argument("--semidense-align", default=None, metavar="FILE",
+                    help="--semidense-temporal: align every later frame's left image against the keyframe's map; one line per frame into FILE")
     ap.add_argument("--semidense-min-obs", type=int, default=None, metavar="N", help="observations a fused pixel needs (default 2)")
     return ap.parse_args(argv)
 
@@ -171,6 +191,7 @@ def main():
         if fused is not None:
             write_ply(os.path.join(args.semidense, f"semidense_fused_{fused['frame_id']:06d}.ply"), fused["xyz"], fused["sigma_invd"])
     cov_file = open(args.covariance, "w") if args.covariance else None
+    align_file = open(args.semidense_align, "w") if args.semidense_align else None
     svo.ctx.sum_order = args.sum_order
     pair = lambda k: (load_grey(os.path.join(args.left, names_l[k])), load_grey(os.path.join(args.right, names_r[k])))  # noqa: E731
     ids, poses, n_kf = [], [], 0
@@ -189,6 +210,8 @@ def main():
             cov = svo.getPoseCovariance()
             ros = V.pose_covariance_ros(cov.P, poses[-1])
             cov_file.write(f"{info.frame_id} " + " ".join(f"{v:.9e}" for v in ros) + f" {int(cov.valid)} {cov.n_unknown_steps}\n")
+        if align_file:  # (this waits for the side stream: a caller that wants it hidden fetches a frame later)
+            align_file.write(align_line(svo.getSemiDenseAlign(), poses[-1]))
         if args.semidense and (info.is_keyframe or args.semidense_every == "frame"):
             # (fetched here for simplicity: this waits for the result's launch; a caller that wants it hidden fetches a frame later)
             pts = svo.getSemiDensePoints(world=True)
@@ -215,6 +238,8 @@ def main():
         V.write_trajectory(args.keyframes, list(range(len(kfs))), np.stack([T for T, _ in kfs]) if kfs else np.zeros((0, 4, 4), np.float32))
     if cov_file:
         cov_file.close()
+    if align_file:
+        align_file.close()
     svo.close()
     print(f"{n} frames in {dt:.2f} s ({n / dt:.1f} frames/s incl. image decoding); trajectory -> {args.trajectory}")
 

@@ -966,6 +966,89 @@ int vo_semidense_map_propagate(vo_ctx *ctx, const float *old_invd, const float *
 int vo_svo_set_semidense_propagate(vo_svo *svo, const vo_semidense_propagate_params *prm);
 int vo_svo_get_semidense_origin(vo_svo *svo, uint8_t *origin, int *width, int *height, int *from_frame_id);
 
+/* ---- Semi-dense alignment: a left image aligned photometrically against the keyframe's semi-dense map ----------
+ * The step LSD-SLAM and SVO take: inverse compositional Gauss-Newton on level 0 over the map's pixels, from a start that is already
+ * close (the odometry's pose); no pyramid, so the basin is a few pixels wide. It yields a second pose estimate, independent of the
+ * feature tracks, with its residual statistic and 6 x 6 normal matrix. float32 + - x / floorf sqrtf, every operation rounded on its
+ * own (no FMA), in the order written here; the Jacobian entries, weights and residuals are integers and their sums exact, the
+ * solve is float64 in a written order. tests/semidense_align_restatement.py restates it.
+ *   inputs     Lk: the keyframe's left level-0 u8 plane; Lc: the current left plane (a slot's level 0), both W x H, 3 <= W, H <=
+ *              65535, W H < 2^31; the map's planes invd f32, sigma f32, n_obs u8; K = fx, fy, cx, cy; the start T_ck row-major
+ *              4 x 4, X_c = R X_k + t (rows 0..2 are read; row 3 is 0 0 0 1).
+ *   params     min_obs 1..255; 0 < huber <= 255 [grey levels]; max_iters 1..32; eps >= 0; min_pixels >= 6.
+ *   pixel set  (x, y), raster index i = y W + x, with n_obs >= min_obs, sigma > 0, invd > 0, 1 <= x <= W-2, 1 <= y <= H-2. No mask is
+ *              consulted: the map respects the keyframe's.
+ *   constants  gx = Lk(x+1, y) - Lk(x-1, y), gy = Lk(x, y+1) - Lk(x, y-1) (integers, as the static block forms them); Z = 1 / invd,
+ *              u = ((float)x - cx) / fx, v = ((float)y - cy) / fy, X = u Z, Y = v Z; fu = fx u, fv = fy v;
+ *                Ju = (fx invd, 0, -(fu invd), -(fu v), fx + fu u, -(fx v))    (the derivative of the pixel column by xi = (v, omega),
+ *                Jv = (0, fy invd, -(fv invd), -(fy + fv v), fv u, fy u)        the order of se3Exp_f, at xi = 0)
+ *              J_i = 0.5 ((float)gx Ju_i + (float)gy Jv_i) — 0.5: the central difference spans two pixels;
+ *              q_i = (int)floorf(16 J_i + 0.5f). A pixel with a non-finite X, Y, Z or 16 J_i, or any |16 J_i| >= 2^22, is dropped.
+ *   iteration  with R, t of the current T: X_c = ((R[i][0] X + R[i][1] Y) + R[i][2] Z) + t_i. not (Z_c > 0.1): the pixel is out for
+ *              this iteration. p = (fx (X_c / Z_c) + cx, fy (Y_c / Z_c) + cy), sampled as the temporal block samples a tap (1/32
+ *              pixel, the integer inside test before any load, the 12-bit value 0..4080); not inside: out. r = sample - 16 Lk(x, y),
+ *              an integer in 1/16 grey level. kq = (int)floorf(16 huber + 0.5f); w = 256 where |r| <= kq, else (256 kq) / |r| by
+ *              integer division (Huber's weight in 1/256).
+ *   sums       30 integers held in int64: the 21 sums of w q_i q_j (i <= j, row by row), the 6 of w q_i r, sum w r^2, sum w and
+ *              the count of pixels that are not out — per block of 1024 consecutive raster indices, a constant of the definition
+ *              and not of any launch. Bound: w <= 2^8, |q_i| <= 2^22, |r| < 2^12, 2^10 pixels: a block's sum stays below
+ *              2^8 2^44 2^10 = 2^62. (With the 2^23 of a 24-bit mantissa the bound would be 2^64: hence 2^22.) Inside a block
+ *              the sums are exact, so their order is free. The blocks' sums are converted to f64 and added in block order,
+ *              block 0 first, then scaled by exact powers of two: H = 2^-16 sum w q_i q_j, b = 2^-16 sum w q_i r.
+ *   solve      count < min_pixels: status 2. H xi = b by LDL^T in f64, for j = 0..5: d_j = H_jj - sum_k<j (L_jk L_jk) d_k (k
+ *              ascending, one subtraction per k); not (0 < d_j <= DBL_MAX) or not (d_j > 2^-20 H_jj): status 3;
+ *              L_ij = (H_ij - sum_k<j (L_ik L_jk) d_k) / d_j. (d_j / H_jj is the share of column j the columns before it do not
+ *              explain. A map of one image row at one depth leaves 1e-9 .. 4e-8 of the rotation about x next to the translation
+ *              along y, passes a test on the sign alone and walks metres away; the test stream's maps, crops of 31 x 29 included,
+ *              stay above 2e-4. 2^-20 is also where the entries' own rounding to 1/16 ends: |q| <= 2^22 with an error of 1/2.)
+ *              y_i = b_i - sum_k<i L_ik y_k; x_i = y_i / d_i - sum_k>i L_ki x_k (k ascending), i = 5..0. A non-finite x: status 3.
+ *   update     T <- T exp(-xi), xi = (float)x: the exponential is geometry::se3Exp_f as the pose-only BA's kernel evaluates it
+ *              (float32; the three coefficients through float64, below 0.25 rad by the Taylor series written in
+ *              csrc/semidense_align_device.hpp), the product in the temporal block's order (r = a0 b0, r = a_k b_k + r). Then stop
+ *              with status 0 where ((((x0^2 + x1^2) + x2^2) + x3^2) + x4^2) + x5^2 < (double)eps (double)eps, in f64 (the square of
+ *              a float is exact); with status 1 after max_iters iterations. After status 2 or 3 T is the pose they were met at.
+ *              The samples sit on a 1/32 pixel grid, so the cost is piecewise constant in T: the iteration ends in a fixed point
+ *              or in a small cycle (steps of 1e-6 .. 2e-5 on the 640 x 240 test stream). eps = 1e-4 (0.1 mm, 0.006 degrees) lies
+ *              above that floor and below the quantum itself: 1/32 pixel of a point 3 m away is 0.25 mm at fx = 370.
+ *   result     T_ck, status, iters; from the last evaluated system: count, rms = sqrt(sum w r^2 / sum w) / 16 [grey levels] (0
+ *              where sum w = 0), H (21 entries, the upper triangle row by row) and b. H is what a caller turns into an
+ *              information matrix (divide by a residual variance in grey levels squared).
+ * vo_semidense_align: the operator, synchronous: at most max_iters launches, back to back without a host turn. key_plane (host,
+ * or device with key_on_device) has key_stride bytes per row; the map's planes are host planes, or all device planes with
+ * on_device; they are not modified. The planes may not exceed vo_config.max_width x max_height.
+ *
+ * StereoVO: vo_svo_set_semidense_align(svo, prm) — NULL = off — needs vo_svo_set_semidense_temporal on and makes its only allocation
+ * (the state block and the blocks' partial sums) at the first enable; VO_ERR_INVALID while a frame is in flight or on a mono driver.
+ * With it off nothing changes; with it on the odometry's results, the semi-dense results and the map are the same bits. At every
+ * frame that is not a keyframe and has a keyframe map, vo_svo_result enqueues the launches on the side stream IN FRONT OF that
+ * frame's temporal launch, with the T_ck the temporal launch gets as the start: the alignment reads the map fused through the
+ * previous frame. It never waits for them. vo_svo_get_semidense_align: the last frame's result, T_wc = T_wk inverseSE3(T_ck) formed
+ * on the host in float (may be NULL), that frame's id and the keyframe's; at a keyframe frame (and before the first frame)
+ * status = VO_SEMIDENSE_ALIGN_NONE, key_frame_id = -1, the poses are the identity. It waits for the side stream's last launch only;
+ * VO_ERR_INVALID while a frame is in flight or with the option off. The aligned pose is not fed back anywhere. Not for MonoVO or
+ * vo_batch streams. */
+enum { VO_SEMIDENSE_ALIGN_CONVERGED = 0, VO_SEMIDENSE_ALIGN_MAX_ITERS = 1, VO_SEMIDENSE_ALIGN_FEW_PIXELS = 2, VO_SEMIDENSE_ALIGN_SINGULAR = 3,
+       VO_SEMIDENSE_ALIGN_NONE = 4 };
+typedef struct {
+  int min_obs;     /* 1 */
+  float huber;     /* 10.0 [grey levels] */
+  int max_iters;   /* 10 */
+  float eps;       /* 1e-4 */
+  int min_pixels;  /* 100 */
+} vo_semidense_align_params;
+typedef struct {
+  float T_ck[16];
+  int status, iters, count;
+  double rms;
+  double H[21], b[6];
+} vo_semidense_align_result;
+int vo_semidense_align_default_params(vo_semidense_align_params *prm);
+int vo_semidense_align(vo_ctx *ctx, const uint8_t *key_plane, int key_stride, int key_on_device, int slot_cur, const float K[4],
+                       const float T_ck[16], const vo_semidense_align_params *prm, const float *invd, const float *sigma, const uint8_t *n_obs,
+                       int on_device, vo_semidense_align_result *result);
+int vo_svo_set_semidense_align(vo_svo *svo, const vo_semidense_align_params *prm);
+int vo_svo_get_semidense_align(vo_svo *svo, vo_semidense_align_result *result, float T_wc[16], int *frame_id, int *key_frame_id);
+
 /* ---- undistortion / stereo rectification in front of the trackers ----------
  * core/visual_odometry/camera.cpp. A context holds the maps of two cameras
  * (cam 0 = left or the mono camera, cam 1 = right), device-resident. */

@@ -118,6 +118,15 @@ class SemiDensePropagateParams(C.Structure):  # vo_semidense_propagate_params
     _fields_ = [("min_obs", C.c_int), ("max_diff", C.c_int), ("chi", C.c_float), ("sigma_add", C.c_float)]
 
 
+class SemiDenseAlignParams(C.Structure):  # vo_semidense_align_params
+    _fields_ = [("min_obs", C.c_int), ("huber", C.c_float), ("max_iters", C.c_int), ("eps", C.c_float), ("min_pixels", C.c_int)]
+
+
+class SemiDenseAlignResult(C.Structure):  # vo_semidense_align_result
+    _fields_ = [("T_ck", C.c_float * 16), ("status", C.c_int), ("iters", C.c_int), ("count", C.c_int), ("rms", C.c_double),
+                ("H", C.c_double * 21), ("b", C.c_double * 6)]
+
+
 class FivePointParams(C.Structure):
     _fields_ = [("thres_px", C.c_float), ("confidence", C.c_float), ("max_iters", C.c_int), ("seed", C.c_ulonglong)]
 
@@ -169,6 +178,7 @@ SYMBOLS = [
     "vo_semidense_temporal_default_params", "vo_semidense_map_seed", "vo_semidense_temporal", "vo_semidense_map_points",
     "vo_svo_set_semidense_temporal", "vo_svo_get_semidense_map", "vo_svo_get_semidense_map_points",
     "vo_semidense_propagate_default_params", "vo_semidense_map_propagate", "vo_svo_set_semidense_propagate", "vo_svo_get_semidense_origin",
+    "vo_semidense_align_default_params", "vo_semidense_align", "vo_svo_set_semidense_align", "vo_svo_get_semidense_align",
 ]
 
 _lib = None
@@ -285,6 +295,10 @@ def load():
     lib.vo_semidense_map_propagate.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, vp, vp, C.c_float, vp, vp, vp, vp, vp, vp, vp, vp, vp, ci]
     lib.vo_svo_set_semidense_propagate.argtypes = [vp, vp]
     lib.vo_svo_get_semidense_origin.argtypes = [vp, vp, vp, vp, vp]
+    lib.vo_semidense_align_default_params.argtypes = [vp]
+    lib.vo_semidense_align.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp]
+    lib.vo_svo_set_semidense_align.argtypes = [vp, vp]
+    lib.vo_svo_get_semidense_align.argtypes = [vp, vp, vp, vp, vp]
     lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_five_point_destroy.argtypes = [vp]
     lib.vo_five_point_destroy.restype = None

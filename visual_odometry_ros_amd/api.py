@@ -152,6 +152,41 @@ def _semidense_propagate_params(lib, params):
     return p
 
 
+SEMIDENSE_ALIGN_STATUS = {0: "converged", 1: "max_iters reached", 2: "too few pixels", 3: "singular system", 4: "no result"}
+
+
+class SemiDenseAligned(collections.namedtuple("SemiDenseAligned", "T_ck status iters count rms H b T_wc frame_id key_frame_id")):
+    """An alignment against a semi-dense map (include/vo_hip.h, "Semi-dense alignment"): T_ck float32 (4, 4); status (the keys of
+    SEMIDENSE_ALIGN_STATUS), iters; from the last evaluated system count, rms [grey levels], H float64 (6, 6) and b float64 (6,),
+    in the order xi = (v, omega) of se3Exp_f. From a driver also T_wc float32 (4, 4) = the keyframe's T_wc times inverseSE3(T_ck),
+    the frame's id and the keyframe's (-1 with status 4: a keyframe frame has no result)."""
+    __slots__ = ()
+
+
+def _semidense_align_params(lib, params):
+    """keyword parameters -> vo_semidense_align_params: the C defaults, then the caller's fields"""
+    p = _capi.SemiDenseAlignParams()
+    lib.vo_semidense_align_default_params(C.byref(p))
+    known = {f[0] for f in _capi.SemiDenseAlignParams._fields_}
+    for k, v in dict(params).items():
+        if k not in known:
+            raise ValueError(f"semi-dense alignment: unknown parameter {k!r}; known: {sorted(known)}")
+        setattr(p, k, v)
+    return p
+
+
+def _semidense_aligned(r, T_wc=None, frame_id=None, key_frame_id=None):
+    """vo_semidense_align_result -> SemiDenseAligned (H as the full symmetric matrix)"""
+    H = np.zeros((6, 6), np.float64)
+    n = 0
+    for i in range(6):
+        for j in range(i, 6):
+            H[i, j] = H[j, i] = r.H[n]
+            n += 1
+    return SemiDenseAligned(np.array(r.T_ck, np.float32).reshape(4, 4), int(r.status), int(r.iters), int(r.count), float(r.rms), H,
+                            np.array(r.b, np.float64), T_wc, frame_id, key_frame_id)
+
+
 def _zncc_gate_arg(gate, stereo):
     """zncc_gate= / setZnccGate: None -> off; dict(thres=, win=15, pattern="centered", pairs=("temporal",)) -> the C call's
     (pairs, win, pattern, thres). pairs: names out of "temporal", "stereo" (StereoVO only)."""
@@ -418,6 +453,35 @@ class Context:
         self.check(self.lib.vo_semidense_temporal(self._h, pk, stride, int(key_on_device is not None), int(slot_cur), Ka.ctypes.data, Ta.ctypes.data,
                                                   C.byref(p), invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data, ts.ctypes.data, score.ctypes.data, 0))
         return SemiDenseMap(invd, sigma, n_obs, ts, score, None, None, None)
+
+    def semiDenseAlign(self, key, slot_cur, K, T_ck, map, key_on_device=None, map_on_device=False, **params):
+        """slot_cur's level-0 plane aligned photometrically against the key plane's semi-dense map (include/vo_hip.h, "Semi-dense
+        alignment"), from the start T_ck (4 x 4, X_c = R X_k + t) with K = (fx, fy, cx, cy): at most max_iters launches, one call.
+        key: a u8 array, or a DEVICE address with key_on_device=stride. map: a SemiDenseMap / dict(invd=, sigma=, n_obs=) of
+        arrays, or with map_on_device of DEVICE addresses; it is not modified. Returns a SemiDenseAligned. params: the fields of
+        vo_semidense_align_params."""
+        p = _semidense_align_params(self.lib, params)
+        Ka = np.ascontiguousarray(K, np.float32).reshape(4)
+        Ta = np.ascontiguousarray(T_ck, np.float32).reshape(4, 4)
+        if key_on_device is not None:
+            pk, stride = C.c_void_p(key), int(key_on_device)
+        else:
+            ka = _u8(key)
+            pk, stride = ka.ctypes.data, ka.strides[0]
+        get = (lambda k: getattr(map, k)) if isinstance(map, tuple) else (lambda k: map[k])
+        res = _capi.SemiDenseAlignResult()
+        if map_on_device:
+            planes = [C.c_void_p(get(k)) for k in ("invd", "sigma", "n_obs")]
+        else:
+            invd, sigma = np.ascontiguousarray(get("invd"), np.float32), np.ascontiguousarray(get("sigma"), np.float32)
+            n_obs = np.ascontiguousarray(get("n_obs"), np.uint8)
+            w, h = self.slot_image_size(slot_cur)
+            if invd.shape != (h, w) or sigma.shape != (h, w) or n_obs.shape != (h, w):
+                raise ValueError(f"the map's planes must be ({h}, {w}) like slot {slot_cur}'s image")
+            planes = [invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data]
+        self.check(self.lib.vo_semidense_align(self._h, pk, stride, int(key_on_device is not None), int(slot_cur), Ka.ctypes.data, Ta.ctypes.data,
+                                               C.byref(p), *planes, int(bool(map_on_device)), C.byref(res)))
+        return _semidense_aligned(res)
 
     def semiDenseMapPropagate(self, old_map, key, slot_new, static, bf, K, T_ba, out=None, key_on_device=None, **params):
         """The old keyframe's map carried over to the keyframe whose left image is in slot_new (include/vo_hip.h, "Semi-dense
@@ -1384,7 +1448,8 @@ class StereoVO:
         """debug_image=True: every tracked frame draws the reference's img_debug_ on the device (getDebugImage).
         semidense: dict of semi-dense stereo parameters (setSemiDense; "every": "keyframe" or "frame") — depth of the keyframes' pairs;
         its "temporal": True or dict(z_max=..., max_search=...) also switches setSemiDenseTemporal on, and with it
-        "propagate": True or dict(min_obs=, max_diff=, chi=, sigma_add=) setSemiDensePropagate.
+        "propagate": True or dict(min_obs=, max_diff=, chi=, sigma_add=) setSemiDensePropagate,
+        "align": True or dict(min_obs=, huber=, max_iters=, eps=, min_pixels=) setSemiDenseAlign.
         mask: the ignore mask every pair carries from the first one on (setMask).
         zncc_gate: dict(thres=, win=15, pattern="centered", pairs=("temporal",)) — the appearance gate (setZnccGate).
         pose_covariance=True: every frame chains the covariance of its pose on the device (getPoseCovariance); sigma_px > 0
@@ -1416,14 +1481,18 @@ class StereoVO:
             self.setZnccGate(zncc_gate)
         if semidense is not None:
             sd = dict(semidense)
-            temporal, propagate = sd.pop("temporal", None), sd.pop("propagate", None)
+            temporal, propagate, align = sd.pop("temporal", None), sd.pop("propagate", None), sd.pop("align", None)
             if propagate and not temporal:
                 raise ValueError('semidense: "propagate" needs "temporal"')
+            if align and not temporal:
+                raise ValueError('semidense: "align" needs "temporal"')
             self.setSemiDense(sd, every=sd.pop("every", "keyframe"))
             if temporal:
                 self.setSemiDenseTemporal({} if temporal is True else temporal)
             if propagate:
                 self.setSemiDensePropagate({} if propagate is True else propagate)
+            if align:
+                self.setSemiDenseAlign({} if align is True else align)
         self._info = SvoFrameInfo()
         self.stats_frame = []  # AlgorithmStatistics::FrameStatistics::Twc per frame (stereo_vo.cpp:979-980)
 
@@ -1598,6 +1667,27 @@ class StereoVO:
             return
         p = _semidense_propagate_params(self.lib, params)
         self.ctx.check(self.lib.vo_svo_set_semidense_propagate(self._h, C.byref(p)))
+
+    def setSemiDenseAlign(self, params):
+        """Direct image alignment on the keyframe's map (include/vo_hip.h, "Semi-dense alignment"): every frame that is not a
+        keyframe aligns its left image against the map as the previous frames left it, from the odometry's pose, on the side stream
+        in front of the frame's temporal launch; the odometry's results, the semi-dense results and the map do not change. params:
+        dict(min_obs=, huber=, max_iters=, eps=, min_pixels=) ({}: the defaults), None: off. Needs setSemiDenseTemporal. Refused
+        while a frame is in flight."""
+        if params is None:
+            self.ctx.check(self.lib.vo_svo_set_semidense_align(self._h, None))
+            return
+        p = _semidense_align_params(self.lib, params)
+        self.ctx.check(self.lib.vo_svo_set_semidense_align(self._h, C.byref(p)))
+
+    def getSemiDenseAlign(self):
+        """The last frame's alignment (a SemiDenseAligned with T_wc, frame_id and key_frame_id); status 4 and key_frame_id -1 at a
+        keyframe frame, which has none. Waits for the side stream's last launch only."""
+        res = _capi.SemiDenseAlignResult()
+        T = np.zeros((4, 4), np.float32)
+        fid, kid = C.c_int(), C.c_int()
+        self.ctx.check(self.lib.vo_svo_get_semidense_align(self._h, C.byref(res), T.ctypes.data, C.byref(fid), C.byref(kid)))
+        return _semidense_aligned(res, T, fid.value, kid.value)
 
     def getSemiDenseOrigin(self):
         """(origin uint8 (height, width), from_frame_id) of the last keyframe's map — 0 nothing, 1 static only, 2 propagated only,

@@ -485,6 +485,12 @@ class StereoVO {
   // the map carried over to the next keyframe instead of being seeded afresh (vo::StereoVO::setSemiDensePropagate): with it
   // getSemiDenseMapPoints() has points on a keyframe frame too
   void setSemiDensePropagate(const vo_semidense_propagate_params *prm) { impl_.setSemiDensePropagate(prm); }
+  // every later frame's left image aligned photometrically against the keyframe's map (vo::StereoVO::setSemiDenseAlign): a second
+  // pose estimate next to the odometry's; getSemiDenseAlign() is the last frame's (false at a keyframe frame)
+  void setSemiDenseAlign(const vo_semidense_align_params *prm) { impl_.setSemiDenseAlign(prm); }
+  bool getSemiDenseAlign(vo_semidense_align_result &result, float *T_wc = nullptr, int *frame_id = nullptr, int *key_frame_id = nullptr) {
+    return impl_.getSemiDenseAlign(result, T_wc, frame_id, key_frame_id);
+  }
   PointVec getSemiDenseMapPoints(bool world = true, int min_obs = 2) {
     vo::PointVec v;
     impl_.getSemiDenseMapPoints(v, nullptr, world, min_obs);

@@ -306,6 +306,23 @@ class StereoVO {
     if (from_frame_id) *from_frame_id = from;
     return w > 0;
   }
+  // Direct image alignment on the keyframe's map (vo_svo_set_semidense_align; include/vo_hip.h, "Semi-dense alignment"): every frame
+  // that is not a keyframe aligns its left image against the map from the odometry's pose, on the side stream in front of the
+  // frame's temporal launch; nothing uses the aligned pose. Needs setSemiDenseTemporal. prm = nullptr: off. Throws while a frame is
+  // in flight.
+  static vo_semidense_align_params defaultSemiDenseAlignParams() {
+    vo_semidense_align_params p;
+    vo_semidense_align_default_params(&p);
+    return p;
+  }
+  void setSemiDenseAlign(const vo_semidense_align_params *prm) { ctx_->check(vo_svo_set_semidense_align(svo_, prm)); }
+  // the last frame's alignment: result (T_ck, status, iters, count, rms, H, b), T_wc = the keyframe's pose times inverseSE3(T_ck)
+  // (row-major 4 x 4, may be nullptr), the frame's id and the keyframe's. false at a keyframe frame, which has none (status
+  // VO_SEMIDENSE_ALIGN_NONE). Waits for the side stream's last launch only.
+  bool getSemiDenseAlign(vo_semidense_align_result &result, float *T_wc = nullptr, int *frame_id = nullptr, int *key_frame_id = nullptr) {
+    ctx_->check(vo_svo_get_semidense_align(svo_, &result, T_wc, frame_id, key_frame_id));
+    return result.status != VO_SEMIDENSE_ALIGN_NONE;
+  }
   // NOT in the reference: CLAHE on every image before the tracker (vo::Context::setEqualize on this driver's context): legal
   // between frames, applies to the images handed over from now on
   void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) { ctx_->setEqualize(mode, clip_limit, tiles_x, tiles_y); }

@@ -280,6 +280,7 @@ int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, in
   vo_ctx *c = s->c;
   vo_svo_semidense &d = s->sd;
   vo_svo_semidense_temporal &t = s->sdt;
+  if (s->sda.on) s->sda.have = false, s->sda.frame_id = frame_id;  // (vo_svo_set_semidense_align: no result unless one is enqueued below)
   if (!is_keyframe && !t.have) return VO_OK;
   hipStream_t side = c->stream2;
   if (is_keyframe) {
@@ -328,8 +329,11 @@ int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, in
     mv.p = t.mask_on ? t.buf.mask : nullptr;
     mv.stride = mv.w = t.w;
     mv.h = t.h;
-    const int rc = vo_sdt_enqueue(c, t.buf.key, t.w, &mv, slot_l, s->prm.frame.Kl, T_ck, &t.prm, t.buf.invd, t.buf.sigma, t.buf.n_obs, t.buf.tstatus,
-                                  nullptr);
+    // vo_svo_set_semidense_align: in front of the temporal launch, so that it reads the map fused through the previous frame
+    int rc = s->sda.on ? vo_svo_semidense_align_enqueue(s, slot_l, frame_id, T_ck) : VO_OK;
+    if (rc >= 0)
+      rc = vo_sdt_enqueue(c, t.buf.key, t.w, &mv, slot_l, s->prm.frame.Kl, T_ck, &t.prm, t.buf.invd, t.buf.sigma, t.buf.n_obs, t.buf.tstatus,
+                          nullptr);
     c->stream = keep;
     if (rc) return rc;
     ++t.n_fused;
@@ -341,6 +345,7 @@ int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, in
 
 void vo_svo_semidense_temporal_free(vo_svo *s) {
   vo_svo_semidense_propagate_free(s);
+  vo_svo_semidense_align_free(s);
   vo_sdt_buffers_free(&s->sdt.buf);
   s->sdt = vo_svo_semidense_temporal();
 }

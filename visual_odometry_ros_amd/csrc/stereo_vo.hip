@@ -674,6 +674,7 @@ extern "C" int vo_svo_result(vo_svo *s, vo_svo_frame_info *info) {
     for (int i = 0; i < 16; ++i) I.dT[i] = (i % 5 == 0) ? 1.0f : 0.0f;
     vo_pose_cov_state_accept(&s->cov);
     if (info) *info = I;
+    if (s->sda.on) s->sda.have = false, s->sda.frame_id = I.frame_id;  // (vo_svo_set_semidense_align: the first frame has no result)
     if (s->sd.on && s->sd.every == VO_SEMIDENSE_FRAMES) RC(vo_svo_semidense_enqueue(s, s->slot[S_CL], s->slot[S_CR], I.frame_id, I.T_wc));
     return VO_OK;
   }

@@ -54,6 +54,16 @@ struct vo_svo_semidense_propagate {
   float T_ba[16] = {};
 };
 
+// vo_svo_set_semidense_align (semidense_align.hip): at every frame that is not a keyframe the frame's left image is aligned against
+// the keyframe's map, on the side stream in front of the frame's temporal launch. `have`: the last frame has a result in `buf`.
+struct vo_svo_semidense_align {
+  bool on = false, have = false;
+  vo_semidense_align_params prm = {};
+  vo_sda_buffers buf;
+  int frame_id = -1, key_frame_id = -1;
+  float T_wk[16] = {};
+};
+
 struct vo_svo {
   vo_ctx *c = nullptr;
   vo_svo_params prm;
@@ -93,6 +103,7 @@ struct vo_svo {
   vo_svo_semidense sd;  // vo_svo_set_semidense: semi-dense stereo depth of the keyframes' (or every frame's) own pair
   vo_svo_semidense_temporal sdt;  // vo_svo_set_semidense_temporal: the keyframe's map, fused with every later frame
   vo_svo_semidense_propagate sdp;  // vo_svo_set_semidense_propagate: that map carried over to the next keyframe
+  vo_svo_semidense_align sda;  // vo_svo_set_semidense_align: every later frame's left image aligned against that map
   int mono = 0;  // the keyframe storage serves a MonoVO (mono_vo.hip): one observation per keyframe entry, bundled flags
   // all_stkeyframes_ (stats_keyframe): every keyframe's current pose (host) and where its related landmarks' ids are kept
   // on the device (a pool that only grows)
@@ -129,6 +140,9 @@ void vo_svo_semidense_temporal_free(vo_svo *s);
 int vo_svo_semidense_propagate_scatter(vo_svo *s, int slot_l, const float T_wc[16]);
 int vo_svo_semidense_propagate_resolve(vo_svo *s, bool chain);
 void vo_svo_semidense_propagate_free(vo_svo *s);
+// semidense_align.hip: on the side stream (c->stream points at it) in front of a non-keyframe frame's temporal launch
+int vo_svo_semidense_align_enqueue(vo_svo *s, int slot_l, int frame_id, const float T_ck[16]);
+void vo_svo_semidense_align_free(vo_svo *s);
 
 void svo_mul44(const float A[16], const float B[16], float C[16]);
 void svo_inv_se3(const float T[16], float Ti[16]);

@@ -130,6 +130,7 @@ struct vo_ctx {
   struct vo_semidense_temporal_state *semidense_t;  // vo_semidense_temporal / vo_semidense_map_seed with host planes: their device copies
   struct vo_semidense_state *semidense;  // vo_semidense_stereo / vo_semidense_points: their planes and scratch (semidense.hip), made on first use
   struct vo_semidense_propagate_state *semidense_p;  // vo_semidense_map_propagate: its keys and, for host planes, the new map's device copies
+  struct vo_semidense_align_state *semidense_a;  // vo_semidense_align: its state block and partial sums
 };
 
 static inline hipError_t vo_dev_malloc(vo_ctx *c, void **p, size_t bytes) {
@@ -301,6 +302,21 @@ struct vo_sdp_buffers {
 int vo_sdp_buffers_alloc(vo_ctx *c, vo_sdp_buffers *b, bool driver);
 void vo_sdp_buffers_free(vo_sdp_buffers *b);
 void vo_semidense_propagate_free(vo_ctx *c);
+
+// The semi-dense alignment (semidense_align.hip; include/vo_hip.h, "Semi-dense alignment"): the small state block (pose, status, the
+// "done" word and the ticket, zero between launches; the last evaluated system) and a row of 30 integer sums per block of 1024
+// raster indices: one allocation sized by vo_config.max_width x max_height.
+struct vo_sda_buffers {
+  void *base = nullptr, *state = nullptr;
+  long long *partial = nullptr;
+  size_t n_blocks = 0;
+};
+int vo_sda_buffers_alloc(vo_ctx *c, vo_sda_buffers *b);
+void vo_sda_buffers_free(vo_sda_buffers *b);
+void vo_semidense_align_free(vo_ctx *c);
+// max_iters launches on c->stream, back to back: a DEVICE key plane and the map's DEVICE planes against the slot's level-0 plane
+int vo_sda_enqueue(vo_ctx *c, vo_sda_buffers *b, const uint8_t *d_key, int key_stride, int slot_cur, const float K[4], const float T_ck[16],
+                   const vo_semidense_align_params *p, const float *invd, const float *sigma, const uint8_t *n_obs);
 
 // Image ingestion (H2D + pyramid chain) enqueues on the side stream when vo_set_ingest_side_stream is on: launchers
 // use c->stream, which this scope points at the ingest stream and restores on exit.
