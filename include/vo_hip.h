@@ -1049,6 +1049,79 @@ int vo_semidense_align(vo_ctx *ctx, const uint8_t *key_plane, int key_stride, in
 int vo_svo_set_semidense_align(vo_svo *svo, const vo_semidense_align_params *prm);
 int vo_svo_get_semidense_align(vo_svo *svo, vo_semidense_align_result *result, float T_wc[16], int *frame_id, int *key_frame_id);
 
+/* ---- Semi-dense alignment on a map pyramid: the block above, coarse to fine ----------
+ * The level-0 block converges from a few pixels; run level by level on the images' pyrDown pyramids and a pyramid of the map it
+ * converges from a frame's motion and more (from the identity, 0.8 - 2.4 m off on the 640 x 240 test stream) and ends where the
+ * level-0 block ends from a close start. tests/semidense_align_pyr_restatement.py restates both parts.
+ *   level sizes  the slot pyramid's: W_0 = W, W_(l+1) = (W_l + 1) / 2, the same for H.
+ *   map pyramid  level l + 1 from level l's RESULT (not from level 0). cv::pyrDown centres the coarse pixel (X, Y) on the finer
+ *              pixel (2X, 2Y): its children are the 3 x 3 finer cells (2X + dx, 2Y + dy) that lie inside the finer plane, visited
+ *              dy = -1, 0, 1 outer, dx = -1, 0, 1 inner. A child counts iff n_obs >= 1, sigma > 0, invd > 0 and both are finite.
+ *              float32, every operation rounded on its own, no FMA: per counted child w = 1 / (sigma sigma), S = S + w,
+ *              N = N + w invd (S = N = 0 at the start). With n counted children, n >= 1 and 0 < S <= FLT_MAX:
+ *              invd = N / S, sigma = sqrtf((float)n / S) — the children's weighted-mean variance, not the fused one: neighbours
+ *              are not independent measurements —, n_obs = the largest counted child's n_obs. Otherwise all three are 0.
+ *   params     the level-0 block's five; levels 1..6; max_iters_level[l] 0..32 for l < levels: a level's iterations, 0 = max_iters.
+ *              Every used level exists in both slots (VO_ERR_INVALID otherwise) and has W_l, H_l >= 3 (VO_ERR_SIZE).
+ *   levels     for l = levels - 1 down to 0 the level-0 block's definition verbatim — pixel set, blocks of 1024 raster indices of
+ *              THAT level's plane, integer sums, the f64 block order, LDL^T, the 2^-20 pivot, update and stop — applied to level l
+ *              of the key slot's and the current slot's pyramid, level l of the map pyramid, K_l = (fx, fy, cx, cy) 2^-l (exact;
+ *              pyrDown's centre alignment: x_l = 2^-l x_0) and the pose the level above left (the top level: the start). After
+ *              status 0 or 1 a level hands its pose down; after status 2 or 3 the pose that status was met at, and the next level
+ *              runs all the same. Translations are metric at every level, so the pose needs no rescaling.
+ *   result     level 0's T_ck, status, iters, count, rms, H, b — with levels = 1 every one of them is vo_semidense_align's, bit for
+ *              bit — and status, iters, count, rms per level (index = level); start_prev (StereoVO only, below).
+ * vo_semidense_map_pyramid: levels 1 .. levels - 1 of a w x h map, each plane kind into ONE tightly packed buffer, level 1 first
+ * (vo_semidense_map_pyramid_size: its elements). One launch per level. Host planes, or all device planes with on_device. 2 <= levels
+ * <= 6; the planes may not exceed vo_config.max_width x max_height.
+ * vo_semidense_align_pyr: the operator, synchronous: the map pyramid's launches, then per level at most its iterations' launches,
+ * back to back without a host turn (a launch that finds its level done returns at once). Both images are slots; the map's level-0
+ * planes are host planes or, with on_device, device planes; they are not modified.
+ *
+ * StereoVO: vo_svo_set_semidense_align_pyr(svo, prm, start) — NULL = off — needs vo_svo_set_semidense_temporal on; it replaces
+ * vo_svo_set_semidense_align's launches while it is on (either setter with NULL turns the alignment off). Its allocations are made
+ * at the first enable only: the keyframe's levels 1..5 with the map pyramid's planes (one allocation) and, unless
+ * vo_svo_set_semidense_align made it, the state block. VO_ERR_INVALID while a frame is in flight or on a mono driver. At a keyframe
+ * the slot's levels 1 .. levels - 1 are copied next to the key plane, device to device; at every other frame the map pyramid's
+ * launches and the alignment's go on the side stream in front of the frame's temporal launch. Nothing waits. With it off no launch,
+ * wait, allocation or result bit differs; with it on the odometry's results, the static result and the map are the same bits.
+ *   start = VO_SEMIDENSE_ALIGN_START_ODOMETRY  the T_ck the temporal launch gets, as vo_svo_set_semidense_align.
+ *   start = VO_SEMIDENSE_ALIGN_START_PREVIOUS  an odometry of its own: at the first frame after a keyframe the identity; otherwise the
+ *              previous frame's aligned T_ck where that frame has a result against the same keyframe with status 0 or 1 — read from
+ *              the state block on the device by the top level's first launch: no host turn —, else the odometry's T_ck, which the
+ *              launch carries in its arguments. result.start_prev = 1 where the previous result was used.
+ * vo_svo_get_semidense_align_pyr: as vo_svo_get_semidense_align, with the per-level fields; either getter serves either setter (the
+ * level-0 getter leaves the per-level fields out). The aligned pose is not fed back anywhere. */
+#define VO_SEMIDENSE_ALIGN_MAX_LEVELS 6
+enum { VO_SEMIDENSE_ALIGN_START_ODOMETRY = 0, VO_SEMIDENSE_ALIGN_START_PREVIOUS = 1 };
+typedef struct {
+  int min_obs;     /* 1 */
+  float huber;     /* 10.0 [grey levels] */
+  int max_iters;   /* 10: a level's iterations where max_iters_level[l] = 0 */
+  float eps;       /* 1e-4 */
+  int min_pixels;  /* 100 */
+  int levels;      /* 4 */
+  int max_iters_level[VO_SEMIDENSE_ALIGN_MAX_LEVELS]; /* 0 */
+} vo_semidense_align_pyr_params;
+typedef struct {
+  float T_ck[16];
+  int status, iters, count;
+  double rms;
+  double H[21], b[6];
+  int levels, start_prev;
+  int level_status[VO_SEMIDENSE_ALIGN_MAX_LEVELS], level_iters[VO_SEMIDENSE_ALIGN_MAX_LEVELS], level_count[VO_SEMIDENSE_ALIGN_MAX_LEVELS];
+  double level_rms[VO_SEMIDENSE_ALIGN_MAX_LEVELS];
+} vo_semidense_align_pyr_result;
+int vo_semidense_align_pyr_default_params(vo_semidense_align_pyr_params *prm);
+int vo_semidense_map_pyramid_size(int width, int height, int levels, long long *elements);
+int vo_semidense_map_pyramid(vo_ctx *ctx, const float *invd, const float *sigma, const uint8_t *n_obs, int width, int height, int levels,
+                             float *invd_pyr, float *sigma_pyr, uint8_t *n_obs_pyr, int on_device);
+int vo_semidense_align_pyr(vo_ctx *ctx, int slot_key, int slot_cur, const float K[4], const float T_ck[16],
+                           const vo_semidense_align_pyr_params *prm, const float *invd, const float *sigma, const uint8_t *n_obs, int on_device,
+                           vo_semidense_align_pyr_result *result);
+int vo_svo_set_semidense_align_pyr(vo_svo *svo, const vo_semidense_align_pyr_params *prm, int start);
+int vo_svo_get_semidense_align_pyr(vo_svo *svo, vo_semidense_align_pyr_result *result, float T_wc[16], int *frame_id, int *key_frame_id);
+
 /* ---- undistortion / stereo rectification in front of the trackers ----------
  * core/visual_odometry/camera.cpp. A context holds the maps of two cameras
  * (cam 0 = left or the mono camera, cam 1 = right), device-resident. */

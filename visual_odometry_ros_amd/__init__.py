@@ -10,5 +10,5 @@ from .api import (Context, FeatureTracker, MotionEstimator, FeatureExtractor,  #
                   StereoFramePipeline, MonoFramePipeline, Camera, StereoCamera,
                   SparseBundleAdjustmentSolver, TrackIds, se3Exp_f, write_trajectory, StereoVO, MonoVO, triangulateDLT, ImageSlots, StereoBatch,
                   FivePointRansac, PoseInformation, PoseCovariance, propagate_pose_covariance, pose_covariance_ros,
-                  se3_adjoint, SemiDenseResult, SemiDenseMap, semidense_disparity_range, SemiDensePropagated, SemiDenseAligned,
+                  se3_adjoint, SemiDenseResult, SemiDenseMap, semidense_disparity_range, SemiDensePropagated, SemiDenseAligned, SemiDenseAlignedLevel,
                   SEMIDENSE_ALIGN_STATUS)

@@ -127,6 +127,15 @@ class SemiDenseAlignResult(C.Structure):  # vo_semidense_align_result
                 ("H", C.c_double * 21), ("b", C.c_double * 6)]
 
 
+class SemiDenseAlignPyrParams(C.Structure):  # vo_semidense_align_pyr_params
+    _fields_ = SemiDenseAlignParams._fields_ + [("levels", C.c_int), ("max_iters_level", C.c_int * 6)]
+
+
+class SemiDenseAlignPyrResult(C.Structure):  # vo_semidense_align_pyr_result
+    _fields_ = SemiDenseAlignResult._fields_ + [("levels", C.c_int), ("start_prev", C.c_int), ("level_status", C.c_int * 6),
+                                                ("level_iters", C.c_int * 6), ("level_count", C.c_int * 6), ("level_rms", C.c_double * 6)]
+
+
 class FivePointParams(C.Structure):
     _fields_ = [("thres_px", C.c_float), ("confidence", C.c_float), ("max_iters", C.c_int), ("seed", C.c_ulonglong)]
 
@@ -179,6 +188,8 @@ SYMBOLS = [
     "vo_svo_set_semidense_temporal", "vo_svo_get_semidense_map", "vo_svo_get_semidense_map_points",
     "vo_semidense_propagate_default_params", "vo_semidense_map_propagate", "vo_svo_set_semidense_propagate", "vo_svo_get_semidense_origin",
     "vo_semidense_align_default_params", "vo_semidense_align", "vo_svo_set_semidense_align", "vo_svo_get_semidense_align",
+    "vo_semidense_align_pyr_default_params", "vo_semidense_map_pyramid_size", "vo_semidense_map_pyramid", "vo_semidense_align_pyr",
+    "vo_svo_set_semidense_align_pyr", "vo_svo_get_semidense_align_pyr",
 ]
 
 _lib = None
@@ -299,6 +310,12 @@ def load():
     lib.vo_semidense_align.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp]
     lib.vo_svo_set_semidense_align.argtypes = [vp, vp]
     lib.vo_svo_get_semidense_align.argtypes = [vp, vp, vp, vp, vp]
+    lib.vo_semidense_align_pyr_default_params.argtypes = [vp]
+    lib.vo_semidense_map_pyramid_size.argtypes = [ci, ci, ci, vp]
+    lib.vo_semidense_map_pyramid.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, ci]
+    lib.vo_semidense_align_pyr.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp]
+    lib.vo_svo_set_semidense_align_pyr.argtypes = [vp, vp, ci]
+    lib.vo_svo_get_semidense_align_pyr.argtypes = [vp, vp, vp, vp, vp]
     lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_five_point_destroy.argtypes = [vp]
     lib.vo_five_point_destroy.restype = None

@@ -155,11 +155,19 @@ def _semidense_propagate_params(lib, params):
 SEMIDENSE_ALIGN_STATUS = {0: "converged", 1: "max_iters reached", 2: "too few pixels", 3: "singular system", 4: "no result"}
 
 
-class SemiDenseAligned(collections.namedtuple("SemiDenseAligned", "T_ck status iters count rms H b T_wc frame_id key_frame_id")):
+SEMIDENSE_ALIGN_START = {"odometry": 0, "previous": 1}
+SemiDenseAlignedLevel = collections.namedtuple("SemiDenseAlignedLevel", "status iters count rms")
+
+
+class SemiDenseAligned(collections.namedtuple("SemiDenseAligned", "T_ck status iters count rms H b T_wc frame_id key_frame_id levels start",
+                                              defaults=(None, None))):
     """An alignment against a semi-dense map (include/vo_hip.h, "Semi-dense alignment"): T_ck float32 (4, 4); status (the keys of
     SEMIDENSE_ALIGN_STATUS), iters; from the last evaluated system count, rms [grey levels], H float64 (6, 6) and b float64 (6,),
     in the order xi = (v, omega) of se3Exp_f. From a driver also T_wc float32 (4, 4) = the keyframe's T_wc times inverseSE3(T_ck),
-    the frame's id and the keyframe's (-1 with status 4: a keyframe frame has no result)."""
+    the frame's id and the keyframe's (-1 with status 4: a keyframe frame has no result). From the coarse-to-fine calls ("Semi-dense
+    alignment on a map pyramid") and a driver also levels: a tuple of SemiDenseAlignedLevel(status, iters, count, rms), index =
+    pyramid level, and from a driver start: "previous" where the previous frame's aligned pose was the start, else "odometry" (the
+    pose the call was given: the odometry's, or the identity at the first frame after a keyframe)."""
     __slots__ = ()
 
 
@@ -175,16 +183,39 @@ def _semidense_align_params(lib, params):
     return p
 
 
+def _semidense_align_pyr_params(lib, params):
+    """keyword parameters -> vo_semidense_align_pyr_params: the C defaults, then the caller's fields (max_iters_level: up to 6 counts,
+    index = level, 0 = max_iters)"""
+    p = _capi.SemiDenseAlignPyrParams()
+    lib.vo_semidense_align_pyr_default_params(C.byref(p))
+    known = {f[0] for f in _capi.SemiDenseAlignPyrParams._fields_}
+    for k, v in dict(params).items():
+        if k not in known:
+            raise ValueError(f"semi-dense alignment: unknown parameter {k!r}; known: {sorted(known)}")
+        if k == "max_iters_level":
+            v = [int(x) for x in v]
+            if len(v) > 6:
+                raise ValueError("semi-dense alignment: max_iters_level holds at most 6 counts")
+            v = (C.c_int * 6)(*(v + [0] * (6 - len(v))))
+        setattr(p, k, v)
+    return p
+
+
 def _semidense_aligned(r, T_wc=None, frame_id=None, key_frame_id=None):
-    """vo_semidense_align_result -> SemiDenseAligned (H as the full symmetric matrix)"""
+    """vo_semidense_align_result / vo_semidense_align_pyr_result -> SemiDenseAligned (H as the full symmetric matrix)"""
     H = np.zeros((6, 6), np.float64)
     n = 0
     for i in range(6):
         for j in range(i, 6):
             H[i, j] = H[j, i] = r.H[n]
             n += 1
+    levels = start = None
+    if isinstance(r, _capi.SemiDenseAlignPyrResult):
+        levels = tuple(SemiDenseAlignedLevel(int(r.level_status[l]), int(r.level_iters[l]), int(r.level_count[l]), float(r.level_rms[l]))
+                       for l in range(r.levels))
+        start = None if frame_id is None else ("previous" if r.start_prev else "odometry")
     return SemiDenseAligned(np.array(r.T_ck, np.float32).reshape(4, 4), int(r.status), int(r.iters), int(r.count), float(r.rms), H,
-                            np.array(r.b, np.float64), T_wc, frame_id, key_frame_id)
+                            np.array(r.b, np.float64), T_wc, frame_id, key_frame_id, levels, start)
 
 
 def _zncc_gate_arg(gate, stereo):
@@ -481,6 +512,58 @@ class Context:
             planes = [invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data]
         self.check(self.lib.vo_semidense_align(self._h, pk, stride, int(key_on_device is not None), int(slot_cur), Ka.ctypes.data, Ta.ctypes.data,
                                                C.byref(p), *planes, int(bool(map_on_device)), C.byref(res)))
+        return _semidense_aligned(res)
+
+    def semiDenseMapPyramid(self, map, levels, on_device=None, out=None):
+        """Levels 1 .. levels - 1 of a semi-dense map (include/vo_hip.h, "Semi-dense alignment on a map pyramid"): a list of
+        dict(invd=, sigma=, n_obs=) per level, [0] the map's own planes. map: a SemiDenseMap / dict(invd=, sigma=, n_obs=) of arrays,
+        or with on_device=(width, height) of DEVICE addresses and out=dict(invd=, sigma=, n_obs=) of DEVICE buffers that take each
+        plane kind's levels one behind the other (None is returned then)."""
+        get = (lambda k: getattr(map, k)) if isinstance(map, tuple) else (lambda k: map[k])
+        if on_device is not None:
+            w, h = on_device
+            self.check(self.lib.vo_semidense_map_pyramid(self._h, *(C.c_void_p(get(k)) for k in ("invd", "sigma", "n_obs")), int(w), int(h),
+                                                         int(levels), *(C.c_void_p(out[k]) for k in ("invd", "sigma", "n_obs")), 1))
+            return None
+        invd, sigma = np.ascontiguousarray(get("invd"), np.float32), np.ascontiguousarray(get("sigma"), np.float32)
+        n_obs = np.ascontiguousarray(get("n_obs"), np.uint8)
+        if invd.ndim != 2 or sigma.shape != invd.shape or n_obs.shape != invd.shape:
+            raise ValueError("invd, sigma and n_obs are planes of one (height, width)")
+        h, w = invd.shape
+        n = C.c_longlong()
+        self.check(self.lib.vo_semidense_map_pyramid_size(w, h, int(levels), C.byref(n)))
+        oi, os_, on = np.zeros(max(n.value, 1), np.float32), np.zeros(max(n.value, 1), np.float32), np.zeros(max(n.value, 1), np.uint8)
+        self.check(self.lib.vo_semidense_map_pyramid(self._h, invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data, w, h, int(levels),
+                                                     oi.ctypes.data, os_.ctypes.data, on.ctypes.data, 0))
+        out_levels, off = [dict(invd=invd, sigma=sigma, n_obs=n_obs)], 0
+        for _ in range(1, int(levels)):
+            w, h = (w + 1) // 2, (h + 1) // 2
+            out_levels.append({k: a[off:off + w * h].reshape(h, w).copy() for k, a in (("invd", oi), ("sigma", os_), ("n_obs", on))})
+            off += w * h
+        return out_levels
+
+    def semiDenseAlignPyramid(self, slot_key, slot_cur, K, T_ck, map, levels=4, map_on_device=False, **params):
+        """slot_cur's image aligned against slot_key's image and its semi-dense map, coarse to fine over `levels` levels of both
+        slots' pyramids and of a map pyramid the call builds (include/vo_hip.h, "Semi-dense alignment on a map pyramid"), from the
+        start T_ck (4 x 4, X_c = R X_k + t) with K = (fx, fy, cx, cy) of level 0. map: a SemiDenseMap / dict(invd=, sigma=, n_obs=)
+        of level-0 arrays, or with map_on_device of DEVICE addresses; it is not modified. Returns a SemiDenseAligned with levels.
+        params: the fields of vo_semidense_align_pyr_params."""
+        p = _semidense_align_pyr_params(self.lib, dict(params, levels=int(levels)))
+        Ka = np.ascontiguousarray(K, np.float32).reshape(4)
+        Ta = np.ascontiguousarray(T_ck, np.float32).reshape(4, 4)
+        get = (lambda k: getattr(map, k)) if isinstance(map, tuple) else (lambda k: map[k])
+        res = _capi.SemiDenseAlignPyrResult()
+        if map_on_device:
+            planes = [C.c_void_p(get(k)) for k in ("invd", "sigma", "n_obs")]
+        else:
+            invd, sigma = np.ascontiguousarray(get("invd"), np.float32), np.ascontiguousarray(get("sigma"), np.float32)
+            n_obs = np.ascontiguousarray(get("n_obs"), np.uint8)
+            w, h = self.slot_image_size(slot_cur)
+            if invd.shape != (h, w) or sigma.shape != (h, w) or n_obs.shape != (h, w):
+                raise ValueError(f"the map's planes must be ({h}, {w}) like slot {slot_cur}'s image")
+            planes = [invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data]
+        self.check(self.lib.vo_semidense_align_pyr(self._h, int(slot_key), int(slot_cur), Ka.ctypes.data, Ta.ctypes.data, C.byref(p), *planes,
+                                                   int(bool(map_on_device)), C.byref(res)))
         return _semidense_aligned(res)
 
     def semiDenseMapPropagate(self, old_map, key, slot_new, static, bf, K, T_ba, out=None, key_on_device=None, **params):
@@ -1449,7 +1532,8 @@ class StereoVO:
         semidense: dict of semi-dense stereo parameters (setSemiDense; "every": "keyframe" or "frame") — depth of the keyframes' pairs;
         its "temporal": True or dict(z_max=..., max_search=...) also switches setSemiDenseTemporal on, and with it
         "propagate": True or dict(min_obs=, max_diff=, chi=, sigma_add=) setSemiDensePropagate,
-        "align": True or dict(min_obs=, huber=, max_iters=, eps=, min_pixels=) setSemiDenseAlign.
+        "align": True or dict(min_obs=, huber=, max_iters=, eps=, min_pixels=) setSemiDenseAlign; with levels=, max_iters_level= or
+        start="odometry" | "previous" in it, coarse to fine on a map pyramid (setSemiDenseAlignPyramid).
         mask: the ignore mask every pair carries from the first one on (setMask).
         zncc_gate: dict(thres=, win=15, pattern="centered", pairs=("temporal",)) — the appearance gate (setZnccGate).
         pose_covariance=True: every frame chains the covariance of its pose on the device (getPoseCovariance); sigma_px > 0
@@ -1673,20 +1757,40 @@ class StereoVO:
         keyframe aligns its left image against the map as the previous frames left it, from the odometry's pose, on the side stream
         in front of the frame's temporal launch; the odometry's results, the semi-dense results and the map do not change. params:
         dict(min_obs=, huber=, max_iters=, eps=, min_pixels=) ({}: the defaults), None: off. Needs setSemiDenseTemporal. Refused
-        while a frame is in flight."""
+        while a frame is in flight. A dict that names levels, max_iters_level or start goes to setSemiDenseAlignPyramid."""
         if params is None:
             self.ctx.check(self.lib.vo_svo_set_semidense_align(self._h, None))
             return
+        if {"levels", "max_iters_level", "start"} & set(params):
+            return self.setSemiDenseAlignPyramid(params)
         p = _semidense_align_params(self.lib, params)
         self.ctx.check(self.lib.vo_svo_set_semidense_align(self._h, C.byref(p)))
 
+    def setSemiDenseAlignPyramid(self, params):
+        """The alignment of setSemiDenseAlign coarse to fine (include/vo_hip.h, "Semi-dense alignment on a map pyramid"): at a
+        keyframe the left image's coarser levels are kept next to its plane; at every other frame a pyramid of the map is formed and
+        the alignment runs from the top level down, on the side stream in front of the frame's temporal launch. params: dict(levels=4,
+        max_iters_level=(...), start="odometry" | "previous", and setSemiDenseAlign's fields); None: off. start="previous": the
+        alignment follows its own pose — the identity at the first frame after a keyframe, then the previous frame's aligned pose
+        where that frame converged (status 0 or 1), else the odometry's. Takes effect with the next keyframe. The odometry's results,
+        the semi-dense results and the map do not change. Needs setSemiDenseTemporal. Refused while a frame is in flight."""
+        if params is None:
+            self.ctx.check(self.lib.vo_svo_set_semidense_align_pyr(self._h, None, 0))
+            return
+        prm = dict(params)
+        start = prm.pop("start", "odometry")
+        if start not in SEMIDENSE_ALIGN_START:
+            raise ValueError(f"semi-dense alignment: start={start!r}; known: {sorted(SEMIDENSE_ALIGN_START)}")
+        p = _semidense_align_pyr_params(self.lib, prm)
+        self.ctx.check(self.lib.vo_svo_set_semidense_align_pyr(self._h, C.byref(p), SEMIDENSE_ALIGN_START[start]))
+
     def getSemiDenseAlign(self):
-        """The last frame's alignment (a SemiDenseAligned with T_wc, frame_id and key_frame_id); status 4 and key_frame_id -1 at a
-        keyframe frame, which has none. Waits for the side stream's last launch only."""
-        res = _capi.SemiDenseAlignResult()
+        """The last frame's alignment (a SemiDenseAligned with T_wc, frame_id, key_frame_id, the per-level fields and the start that
+        was used); status 4 and key_frame_id -1 at a keyframe frame, which has none. Waits for the side stream's last launch only."""
+        res = _capi.SemiDenseAlignPyrResult()
         T = np.zeros((4, 4), np.float32)
         fid, kid = C.c_int(), C.c_int()
-        self.ctx.check(self.lib.vo_svo_get_semidense_align(self._h, C.byref(res), T.ctypes.data, C.byref(fid), C.byref(kid)))
+        self.ctx.check(self.lib.vo_svo_get_semidense_align_pyr(self._h, C.byref(res), T.ctypes.data, C.byref(fid), C.byref(kid)))
         return _semidense_aligned(res, T, fid.value, kid.value)
 
     def getSemiDenseOrigin(self):

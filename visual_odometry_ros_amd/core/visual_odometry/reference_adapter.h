@@ -491,6 +491,14 @@ class StereoVO {
   bool getSemiDenseAlign(vo_semidense_align_result &result, float *T_wc = nullptr, int *frame_id = nullptr, int *key_frame_id = nullptr) {
     return impl_.getSemiDenseAlign(result, T_wc, frame_id, key_frame_id);
   }
+  // that alignment coarse to fine on a map pyramid (vo::StereoVO::setSemiDenseAlignPyramid): it converges from a frame's motion and
+  // more, and with start = VO_SEMIDENSE_ALIGN_START_PREVIOUS it follows its own pose from keyframe to keyframe
+  void setSemiDenseAlignPyramid(const vo_semidense_align_pyr_params *prm, int start = VO_SEMIDENSE_ALIGN_START_ODOMETRY) {
+    impl_.setSemiDenseAlignPyramid(prm, start);
+  }
+  bool getSemiDenseAlign(vo_semidense_align_pyr_result &result, float *T_wc = nullptr, int *frame_id = nullptr, int *key_frame_id = nullptr) {
+    return impl_.getSemiDenseAlign(result, T_wc, frame_id, key_frame_id);
+  }
   PointVec getSemiDenseMapPoints(bool world = true, int min_obs = 2) {
     vo::PointVec v;
     impl_.getSemiDenseMapPoints(v, nullptr, world, min_obs);

@@ -323,6 +323,23 @@ class StereoVO {
     ctx_->check(vo_svo_get_semidense_align(svo_, &result, T_wc, frame_id, key_frame_id));
     return result.status != VO_SEMIDENSE_ALIGN_NONE;
   }
+  // The same alignment coarse to fine on a map pyramid (vo_svo_set_semidense_align_pyr; include/vo_hip.h, "Semi-dense alignment on a
+  // map pyramid"): it converges from a frame's motion and more. start = VO_SEMIDENSE_ALIGN_START_PREVIOUS: an odometry of its own —
+  // the identity at the first frame after a keyframe, then the previous frame's aligned pose where that frame converged, else the
+  // odometry's. Takes effect with the next keyframe; replaces setSemiDenseAlign's launches while it is on. prm = nullptr: off.
+  static vo_semidense_align_pyr_params defaultSemiDenseAlignPyramidParams() {
+    vo_semidense_align_pyr_params p;
+    vo_semidense_align_pyr_default_params(&p);
+    return p;
+  }
+  void setSemiDenseAlignPyramid(const vo_semidense_align_pyr_params *prm, int start = VO_SEMIDENSE_ALIGN_START_ODOMETRY) {
+    ctx_->check(vo_svo_set_semidense_align_pyr(svo_, prm, start));
+  }
+  // getSemiDenseAlign with the per-level fields (index = level) and start_prev: the previous frame's aligned pose was the start
+  bool getSemiDenseAlign(vo_semidense_align_pyr_result &result, float *T_wc = nullptr, int *frame_id = nullptr, int *key_frame_id = nullptr) {
+    ctx_->check(vo_svo_get_semidense_align_pyr(svo_, &result, T_wc, frame_id, key_frame_id));
+    return result.status != VO_SEMIDENSE_ALIGN_NONE;
+  }
   // NOT in the reference: CLAHE on every image before the tracker (vo::Context::setEqualize on this driver's context): legal
   // between frames, applies to the images handed over from now on
   void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) { ctx_->setEqualize(mode, clip_limit, tiles_x, tiles_y); }

@@ -16,6 +16,8 @@
 //                      rows at a time, so that the loads are not one behind the other), and thread 0 solves the 6 x 6 system,
 //                      updates the pose and writes the state block. No float atomics; the ticket is the only atomic.
 //                      A launch that finds `done` set returns at once.
+//                      The coarse-to-fine operator runs the same kernel level by level: `first` says where a launch
+//                      takes its pose from (SDA_FIRST_*), `level` which record of the state block its result is filed under.
 //
 // The includer provides __global__, __shared__, __syncthreads, the built-in indices, int sda_wave_rank(bool, int *n) (the number of
 // lower lanes of the wavefront whose argument is true; *n: all lanes'), SDA_DRAIN (the wavefront's stores have left) and the
@@ -36,6 +38,17 @@
 #define SDA_FRONT 0.1f
 #define SDA_PIVOT (1.0 / 1048576.0)  // 2^-20: a pivot at or below this share of its diagonal entry is refused
 #define SDA_MAX_ITERS 32
+#define SDA_MAX_LEVELS 6
+// SdaArgs.first: 0 = a level's later launch (the pose of the state block; returns at once behind "done"); the others start a
+// level, whatever "done" holds, with iters = 0:
+#define SDA_FIRST_CALL 1   // a call's first launch: the pose is T0, the state block is overwritten
+#define SDA_FIRST_LEVEL 2  // the first launch of a lower level: the pose the level above left in the state block
+#define SDA_FIRST_PREV 3   // a call's first launch that starts from the PREVIOUS call's result where its status is 0 or 1, else T0
+
+struct SdaLevel {  // one level's last evaluated system, as far as the result reports it
+  int status, iters, count, pad;
+  double swrr, sw;
+};
 
 struct SdaState {  // the small device block: pose, status and the "done" word; the last evaluated system
   float T[16];
@@ -44,6 +57,8 @@ struct SdaState {  // the small device block: pose, status and the "done" word; 
   int pad;
   double swrr, sw;  // sum w r^2, sum w (unscaled)
   double H[21], b[6];
+  SdaLevel lv[SDA_MAX_LEVELS];  // per level of the coarse-to-fine operator ([0] alone for the level-0 operator)
+  int start_prev, pad2;         // the call started from the previous call's result (SDA_FIRST_PREV and its status was 0 or 1)
 };
 
 struct SdaArgs {
@@ -56,7 +71,8 @@ struct SdaArgs {
   double eps2;  // (double)eps * (double)eps: exact
   float fx, fy, cx, cy;
   int n_blocks;
-  int first;     // the call's first launch: the pose is T0, whatever the state block holds is overwritten (its ticket is 0)
+  int first;     // SDA_FIRST_*; 1: the call's first launch: the pose is T0, whatever the state block holds is overwritten (its ticket is 0)
+  int level;     // the pyramid level these planes are: the record of the state block that this launch's result is filed under
   float T0[12];  // the start, rows 0..2
   long long *partial;  // [n_blocks][SDA_NSUM]
   SdaState *st;
@@ -119,7 +135,7 @@ __device__ static inline void sda_se3_exp(const float xi[6], float T[12]) {
 }
 
 // the last workgroup's thread 0: S = the 30 sums in f64 (unscaled). Solves, updates the pose, writes the state block.
-__device__ static inline void sda_finish(const SdaArgs &a, const double *S, const float Tin[12]) {
+__device__ static inline void sda_finish(const SdaArgs &a, const double *S, const float Tin[12], bool from_T0) {
   SdaState *st = a.st;
   double A[6][6], bv[6];
   {
@@ -214,6 +230,14 @@ __device__ static inline void sda_finish(const SdaArgs &a, const double *S, cons
   st->T[15] = 1.0f;
   st->status = status;
   st->done = done;
+  SdaLevel *lv = &st->lv[a.level];
+  lv->status = status;
+  lv->iters = iters;
+  lv->count = count;
+  lv->pad = 0;
+  lv->swrr = S[27];
+  lv->sw = S[28];
+  if (a.first == SDA_FIRST_CALL || a.first == SDA_FIRST_PREV) st->start_prev = from_T0 ? 0 : 1;
 }
 
 __global__ __launch_bounds__(SDA_NT) void semidense_align_kernel(SdaArgs a) {
@@ -231,9 +255,11 @@ __global__ __launch_bounds__(SDA_NT) void semidense_align_kernel(SdaArgs a) {
   if (!a.first && a.st->done) return;  // (written by an earlier launch: every thread reads the same word)
   const int W = a.W, H = a.H;
   const long long np = (long long)W * (long long)H, base = (long long)blockIdx.x * SDA_BLOCK;
+  // (the state block's words read here were written by an earlier launch: every thread of every workgroup reads the same)
+  const bool from_T0 = a.first == SDA_FIRST_CALL || (a.first == SDA_FIRST_PREV && (unsigned)a.st->status > 1u);
   float T[12];
 #pragma unroll
-  for (int i = 0; i < 12; ++i) T[i] = a.first ? a.T0[i] : a.st->T[i];
+  for (int i = 0; i < 12; ++i) T[i] = from_T0 ? a.T0[i] : a.st->T[i];
   // ---- (a) the block's pixels of the set, packed ----------------------------------------------------------------------------------
   int n = 0;
   for (int k = 0; k < SDA_BLOCK / SDA_NT; ++k) {
@@ -349,7 +375,7 @@ __global__ __launch_bounds__(SDA_NT) void semidense_align_kernel(SdaArgs a) {
   if (tid < SDA_NSUM) s_sum[tid] = sum;
   __syncthreads();
   if (tid == 0) {
-    sda_finish(a, s_sum, T);
+    sda_finish(a, s_sum, T, from_T0);
     SDA_ST_AGENT(&a.st->ticket, 0u);  // back to zero for the next launch (every workgroup has taken its ticket: this one holds the last)
   }
 }

@@ -280,7 +280,10 @@ int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, in
   vo_ctx *c = s->c;
   vo_svo_semidense &d = s->sd;
   vo_svo_semidense_temporal &t = s->sdt;
-  if (s->sda.on) s->sda.have = false, s->sda.frame_id = frame_id;  // (vo_svo_set_semidense_align: no result unless one is enqueued below)
+  if (s->sda.on) {  // (vo_svo_set_semidense_align: no result unless one is enqueued below)
+    s->sda.prev_key = s->sda.have ? s->sda.key_frame_id : -1;
+    s->sda.have = false, s->sda.frame_id = frame_id;
+  }
   if (!is_keyframe && !t.have) return VO_OK;
   hipStream_t side = c->stream2;
   if (is_keyframe) {
@@ -294,6 +297,10 @@ int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, in
     }
     VO_CHECK_HIP(c, hipMemcpy2DAsync(t.buf.key, (size_t)d.w, P.lv[0].origin(), (size_t)P.lv[0].stride, (size_t)d.w, (size_t)d.h,
                                      hipMemcpyDeviceToDevice, side));
+    if (s->sda.on && s->sda.pyr) {  // vo_svo_set_semidense_align_pyr: the keyframe's coarser levels next to its plane
+      const int rc = vo_svo_semidense_align_key_levels(s, slot_l, frame_id);
+      if (rc) return rc;
+    }
     // the keyframe's own ignore mask goes with its plane: vo_svo_set_mask may change what later pairs carry
     vo_mask_view mv;
     hipStream_t keep = c->stream;

@@ -62,6 +62,13 @@ struct vo_svo_semidense_align {
   vo_sda_buffers buf;
   int frame_id = -1, key_frame_id = -1;
   float T_wk[16] = {};
+  // vo_svo_set_semidense_align_pyr: coarse to fine on the keyframe's levels (copied at the keyframe `key_levels_of`) and a map pyramid
+  bool pyr = false;
+  int start = 0;
+  vo_semidense_align_pyr_params pprm = {};
+  vo_sdm_pyramid py;
+  int key_levels = 0, key_levels_of = -1;
+  int prev_key = -1;  // the keyframe the PREVIOUS frame's result is against (-1: it has none)
 };
 
 struct vo_svo {
@@ -142,6 +149,8 @@ int vo_svo_semidense_propagate_resolve(vo_svo *s, bool chain);
 void vo_svo_semidense_propagate_free(vo_svo *s);
 // semidense_align.hip: on the side stream (c->stream points at it) in front of a non-keyframe frame's temporal launch
 int vo_svo_semidense_align_enqueue(vo_svo *s, int slot_l, int frame_id, const float T_ck[16]);
+// (vo_svo_set_semidense_align_pyr) at a keyframe, behind the key plane's copy: the slot's coarser levels next to it
+int vo_svo_semidense_align_key_levels(vo_svo *s, int slot_l, int frame_id);
 void vo_svo_semidense_align_free(vo_svo *s);
 
 void svo_mul44(const float A[16], const float B[16], float C[16]);

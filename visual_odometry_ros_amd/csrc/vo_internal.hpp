@@ -317,6 +317,22 @@ void vo_semidense_align_free(vo_ctx *c);
 // max_iters launches on c->stream, back to back: a DEVICE key plane and the map's DEVICE planes against the slot's level-0 plane
 int vo_sda_enqueue(vo_ctx *c, vo_sda_buffers *b, const uint8_t *d_key, int key_stride, int slot_cur, const float K[4], const float T_ck[16],
                    const vo_semidense_align_params *p, const float *invd, const float *sigma, const uint8_t *n_obs);
+// The coarse-to-fine alignment (include/vo_hip.h, "Semi-dense alignment on a map pyramid"): levels 1..5 of a map and, for a driver,
+// of the keyframe's left image, tight planes in one allocation sized by vo_config.max_width x max_height ([0] stays null).
+struct vo_sdm_pyramid {
+  void *base = nullptr;
+  float *invd[6] = {}, *sigma[6] = {};
+  uint8_t *n_obs[6] = {}, *key[6] = {};
+};
+int vo_sdm_pyramid_alloc(vo_ctx *c, vo_sdm_pyramid *py, bool with_key);
+void vo_sdm_pyramid_free(vo_sdm_pyramid *py);
+// levels - 1 launches on c->stream: level l of the map (DEVICE planes, [0] the w x h level 0) from level l - 1, l = 1 .. levels - 1
+int vo_sdm_enqueue(vo_ctx *c, int w, int h, int levels, float *const invd[], float *const sigma[], uint8_t *const n_obs[]);
+// per level, from levels - 1 down, its iterations' launches on c->stream: DEVICE planes per level ([l]: the key's level with its
+// stride, the map's level) against the slot's pyramid. first: SDA_FIRST_CALL or SDA_FIRST_PREV (semidense_align_device.hpp)
+int vo_sda_enqueue_pyr(vo_ctx *c, vo_sda_buffers *b, const uint8_t *const key[], const int key_stride[], int slot_cur, const float K[4],
+                       const float T_ck[16], const vo_semidense_align_pyr_params *p, const float *const invd[], const float *const sigma[],
+                       const uint8_t *const n_obs[], int first);
 
 // Image ingestion (H2D + pyramid chain) enqueues on the side stream when vo_set_ingest_side_stream is on: launchers
 // use c->stream, which this scope points at the ingest stream and restores on exit.
