@@ -26,7 +26,10 @@ iterations, pixel count, rms in grey levels, the 12 numbers of the aligned [R|t]
 [degrees] distance to the odometry's pose. --semidense-align-levels N (1..6) runs that alignment coarse to fine on N levels of a map
 pyramid, which converges from a frame's motion and more; --semidense-align-start previous then makes it an odometry of its own: the
 identity at the first frame after a keyframe, afterwards the previous frame's aligned pose where that frame converged, else the
-odometry's. With either, the line ends with the start that was used and "status:iterations:pixels" per level, level 0 first."""
+odometry's. With either, the line ends with the start that was used and "status:iterations:pixels" per level, level 0 first.
+--semidense-align-affine: the alignment also estimates a gain and an offset of the keyframe's grey levels (for streams whose exposure
+changes between a keyframe and its frames; status 5: they left their range); the line then carries the two behind the rotation
+distance, in front of the start."""
 import argparse
 import os
 import sys
@@ -99,6 +102,8 @@ def semidense_options(args):
         raise SystemExit("--semidense-align needs --semidense-temporal")
     if (args.semidense_align_levels is not None or args.semidense_align_start is not None) and not args.semidense_align:
         raise SystemExit("--semidense-align-levels / --semidense-align-start need --semidense-align FILE")
+    if args.semidense_align_affine and not args.semidense_align:
+        raise SystemExit("--semidense-align-affine needs --semidense-align FILE")
     if args.semidense_align_levels is not None and not 1 <= args.semidense_align_levels <= 6:
         raise SystemExit("--semidense-align-levels N: 1..6")
     if args.semidense_min_obs is not None and (not args.semidense_temporal or not 1 <= args.semidense_min_obs <= 255):
@@ -117,6 +122,8 @@ def semidense_options(args):
         sd["align"] = True
         if args.semidense_align_levels is not None or args.semidense_align_start is not None:
             sd["align"] = {"levels": args.semidense_align_levels or 4, "start": args.semidense_align_start or "odometry"}
+        if args.semidense_align_affine:
+            sd["align"] = dict({} if sd["align"] is True else sd["align"], affine=True)
     return {"semidense": sd}
 
 
@@ -126,9 +133,9 @@ def align_line(a, T_wc):
     R = E[:3, :3]
     s = 0.5 * np.linalg.norm([R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
     dt, dr = (float(np.linalg.norm(E[:3, 3])), float(np.degrees(np.arcsin(min(s, 1.0))))) if a.status != 4 else (0.0, 0.0)
-    tail = ""
+    tail = "" if a.gain is None else f" {a.gain:.6f} {a.offset:.4f}"  # (--semidense-align-affine)
     if a.levels is not None and len(a.levels) > 1:  # (coarse to fine: the start that was used, then every level's outcome)
-        tail = f" {a.start} " + " ".join(f"{lv.status}:{lv.iters}:{lv.count}" for lv in a.levels)
+        tail += f" {a.start} " + " ".join(f"{lv.status}:{lv.iters}:{lv.count}" for lv in a.levels)
     return (f"{a.frame_id} {a.key_frame_id} {a.status} {a.iters} {a.count} {a.rms:.4f} " + " ".join(f"{v:.6f}" for v in a.T_wc[:3].reshape(-1)) +
             f" {dt:.6f} {dr:.6f}{tail}\n")
 
@@ -182,6 +189,8 @@ def parse_args(argv=None):
                     help="--semidense-align: coarse to fine on N levels (1..6; 4 with --semidense-align-start alone) of a map pyramid")
     ap.add_argument("--semidense-align-start", choices=("odometry", "previous"), default=None,
                     help="--semidense-align: start from the odometry's pose (default) or from the previous frame's aligned pose")
+    ap.add_argument("--semidense-align-affine", action="store_true",
+                    help="--semidense-align: estimate a gain and an offset of the keyframe's grey levels next to the pose; two more columns")
     ap.add_argument("--semidense-min-obs", type=int, default=None, metavar="N", help="observations a fused pixel needs (default 2)")
     return ap.parse_args(argv)
 

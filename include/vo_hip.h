@@ -1122,6 +1122,83 @@ int vo_semidense_align_pyr(vo_ctx *ctx, int slot_key, int slot_cur, const float 
 int vo_svo_set_semidense_align_pyr(vo_svo *svo, const vo_semidense_align_pyr_params *prm, int start);
 int vo_svo_get_semidense_align_pyr(vo_svo *svo, vo_semidense_align_pyr_result *result, float T_wc[16], int *frame_id, int *key_frame_id);
 
+/* ---- Semi-dense alignment with affine brightness: gain and offset estimated next to the pose ----------
+ * The two blocks above compare raw grey levels of two images, r = sample - 16 Lk(x, y): an exposure change between the keyframe and
+ * the current image biases the pose (+15 grey levels: 0.7 mm -> 8 mm on the 640 x 240 test stream, status 0 or 1 all the same) and
+ * makes rms meaningless. This block estimates, jointly with the pose, a gain g and an offset o that map the KEYFRAME's grey levels
+ * into the current image's exposure. It is the "Semi-dense alignment" block but for what is written here; opt-in; the blocks above
+ * keep their bits. tests/semidense_align_affine_restatement.py restates it.
+ *   params     the block's own, and gain0, offset0 [grey levels]: 1/8 <= gain0 <= 8, |offset0| <= 255 (VO_ERR_INVALID otherwise).
+ *   state      next to T two integers: G, the gain in 2^-16, and O, the offset in 1/16 grey level. They start at
+ *              G0 = (int)floorf(65536 gain0 + 0.5f), O0 = (int)floorf(16 offset0 + 0.5f).
+ *   iteration  model = ((G (16 Lk(x, y)) + 2^15) >> 16) + O, formed in int64; r = sample - model, an integer in 1/16 grey level;
+ *              Huber's weight from this r as above.
+ *   unknowns   eight: xi, then dg and do. q_0..q_5 are the integers above, NOT scaled by the gain (the iteration converges without:
+ *              DESIGN.md §22 has the iterations it costs); q_6 = 16 Lk(x, y) (0..4080), q_7 = 16: with H and b scaled as above dg
+ *              multiplies the key's grey level and do comes out in grey levels.
+ *   sums       47 integers held in int64 per block of 1024 raster indices: the 36 sums of w q_i q_j (i <= j, row by row over the 8
+ *              columns), the 8 of w q_i r, sum w r^2, sum w and the count. Bound: G in [2^13, 2^19] and |O| <= 4080 (the update
+ *              keeps them there) give model <= 8 x 4080 + 4080 and |r| <= 40800 < 2^16; w <= 2^8, |q_i| <= 2^22, 2^10 pixels:
+ *              w q_i r <= 2^8 2^22 2^16 2^10 = 2^56, w q_i q_j <= 2^62 as above, w r^2 <= 2^8 2^32 2^10 = 2^50. Exact inside a
+ *              block; the blocks' sums are converted to f64 and added in block order, block 0 first; H = 2^-16 sum w q_i q_j,
+ *              b = 2^-16 sum w q_i r.
+ *   solve      count < min_pixels: status 2. H x = b by the LDL^T above in the same written order over j = 0..7, the 2^-20 pivot
+ *              test on every column: status 3; x_i for i = 7..0; a non-finite x: status 3. (The smallest d_j / H_jj on the test
+ *              stream's maps: 1.3e-3 on the 97 x 45 crop.)
+ *   update     in f64: G' = G + floor(65536 x_6 + 0.5), O' = O + floor(16 x_7 + 0.5). Not (2^13 <= G' <= 2^19 and |O'| <= 4080) —
+ *              which a NaN fails —: status VO_SEMIDENSE_ALIGN_AFFINE_RANGE, and T, G, O stay those the iteration started with.
+ *              Otherwise T <- T exp(-xi) from x_0..x_5 as above, G <- G', O <- O' (r = sample - model: raising G or O lowers r, as
+ *              T exp(-xi) does along q_0..q_5, so the signs of the eight components agree). The stop test is the one above, on
+ *              x_0..x_5 alone; statuses 0..4 keep their meaning. After status 2 or 3 the state is the one they were met at.
+ *              At the end point G and O move by a few quanta per iteration like the pose does.
+ *   pyramid    "Semi-dense alignment on a map pyramid" with this block per level: G and O are handed from level to level with the
+ *              pose, after any status (grey levels do not scale with the level); every level's record keeps the G, O it left.
+ *   result     T_ck, status, iters, count, rms; H (36 entries, the upper triangle of the 8 x 8 row by row) and b (8); G, O,
+ *              gain = G / 65536, offset = O / 16 (doubles); levels, start_prev and the per-level fields with level_G, level_O
+ *              (the level-0 operator: levels = 1).
+ * vo_semidense_align_affine / vo_semidense_align_pyr_affine: vo_semidense_align's / vo_semidense_align_pyr's arguments and the
+ * affine parameters (not NULL); synchronous, the same launches with the kernel of this block.
+ *
+ * StereoVO: vo_svo_set_semidense_align_affine(svo, affine) — NULL = off — is a modifier of whichever alignment option is on
+ * (vo_svo_set_semidense_align or vo_svo_set_semidense_align_pyr; VO_ERR_INVALID with neither; turning the alignment off turns it off
+ * too): the option's launches, at their place on the side stream in front of the temporal launch, run this block's kernel on a
+ * state block of their own, allocated at the first enable. VO_ERR_INVALID while a frame is in flight or on a mono driver. With it off
+ * no launch, allocation, wait or result bit differs; with it on the odometry's results, the static result and the map are the same
+ * bits. start = VO_SEMIDENSE_ALIGN_START_PREVIOUS takes G and O from the previous frame's result wherever it takes the pose (status
+ * 0 or 1, read on the device), else G0, O0 with the odometry's pose; the first frame after a keyframe starts from G0, O0. Turning
+ * the modifier on or off forgets the previous frame's result: the next frame has none to start from.
+ * vo_svo_get_semidense_align_affine: as vo_svo_get_semidense_align_pyr, VO_ERR_INVALID with the modifier off. While it is on, the
+ * two getters above return the affine run's T_ck, status (5 included), iters, count, rms and per-level fields; their H is the 21
+ * entries of the upper-left 6 x 6 and their b the first 6 — the pose's rows and columns of the 8 x 8 system, not its Schur
+ * complement. Neither the pose nor the gain is fed back anywhere. Not for MonoVO or vo_batch streams. */
+enum { VO_SEMIDENSE_ALIGN_AFFINE_RANGE = 5 };
+typedef struct {
+  float gain0;    /* 1.0 */
+  float offset0;  /* 0.0 [grey levels] */
+} vo_semidense_affine_params;
+typedef struct {
+  float T_ck[16];
+  int status, iters, count;
+  double rms;
+  double H[36], b[8];
+  double gain, offset;
+  int G, O;
+  int levels, start_prev;
+  int level_status[VO_SEMIDENSE_ALIGN_MAX_LEVELS], level_iters[VO_SEMIDENSE_ALIGN_MAX_LEVELS], level_count[VO_SEMIDENSE_ALIGN_MAX_LEVELS];
+  double level_rms[VO_SEMIDENSE_ALIGN_MAX_LEVELS];
+  int level_G[VO_SEMIDENSE_ALIGN_MAX_LEVELS], level_O[VO_SEMIDENSE_ALIGN_MAX_LEVELS];
+} vo_semidense_align_affine_result;
+int vo_semidense_affine_default_params(vo_semidense_affine_params *prm);
+int vo_semidense_align_affine(vo_ctx *ctx, const uint8_t *key_plane, int key_stride, int key_on_device, int slot_cur, const float K[4],
+                              const float T_ck[16], const vo_semidense_align_params *prm, const vo_semidense_affine_params *affine,
+                              const float *invd, const float *sigma, const uint8_t *n_obs, int on_device,
+                              vo_semidense_align_affine_result *result);
+int vo_semidense_align_pyr_affine(vo_ctx *ctx, int slot_key, int slot_cur, const float K[4], const float T_ck[16],
+                                  const vo_semidense_align_pyr_params *prm, const vo_semidense_affine_params *affine, const float *invd,
+                                  const float *sigma, const uint8_t *n_obs, int on_device, vo_semidense_align_affine_result *result);
+int vo_svo_set_semidense_align_affine(vo_svo *svo, const vo_semidense_affine_params *affine);
+int vo_svo_get_semidense_align_affine(vo_svo *svo, vo_semidense_align_affine_result *result, float T_wc[16], int *frame_id, int *key_frame_id);
+
 /* ---- undistortion / stereo rectification in front of the trackers ----------
  * core/visual_odometry/camera.cpp. A context holds the maps of two cameras
  * (cam 0 = left or the mono camera, cam 1 = right), device-resident. */

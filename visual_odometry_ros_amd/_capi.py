@@ -136,6 +136,17 @@ class SemiDenseAlignPyrResult(C.Structure):  # vo_semidense_align_pyr_result
                                                 ("level_iters", C.c_int * 6), ("level_count", C.c_int * 6), ("level_rms", C.c_double * 6)]
 
 
+class SemiDenseAffineParams(C.Structure):  # vo_semidense_affine_params
+    _fields_ = [("gain0", C.c_float), ("offset0", C.c_float)]
+
+
+class SemiDenseAlignAffineResult(C.Structure):  # vo_semidense_align_affine_result
+    _fields_ = [("T_ck", C.c_float * 16), ("status", C.c_int), ("iters", C.c_int), ("count", C.c_int), ("rms", C.c_double),
+                ("H", C.c_double * 36), ("b", C.c_double * 8), ("gain", C.c_double), ("offset", C.c_double), ("G", C.c_int), ("O", C.c_int),
+                ("levels", C.c_int), ("start_prev", C.c_int), ("level_status", C.c_int * 6), ("level_iters", C.c_int * 6),
+                ("level_count", C.c_int * 6), ("level_rms", C.c_double * 6), ("level_G", C.c_int * 6), ("level_O", C.c_int * 6)]
+
+
 class FivePointParams(C.Structure):
     _fields_ = [("thres_px", C.c_float), ("confidence", C.c_float), ("max_iters", C.c_int), ("seed", C.c_ulonglong)]
 
@@ -190,6 +201,8 @@ SYMBOLS = [
     "vo_semidense_align_default_params", "vo_semidense_align", "vo_svo_set_semidense_align", "vo_svo_get_semidense_align",
     "vo_semidense_align_pyr_default_params", "vo_semidense_map_pyramid_size", "vo_semidense_map_pyramid", "vo_semidense_align_pyr",
     "vo_svo_set_semidense_align_pyr", "vo_svo_get_semidense_align_pyr",
+    "vo_semidense_affine_default_params", "vo_semidense_align_affine", "vo_semidense_align_pyr_affine", "vo_svo_set_semidense_align_affine",
+    "vo_svo_get_semidense_align_affine",
 ]
 
 _lib = None
@@ -316,6 +329,11 @@ def load():
     lib.vo_semidense_align_pyr.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, ci, vp]
     lib.vo_svo_set_semidense_align_pyr.argtypes = [vp, vp, ci]
     lib.vo_svo_get_semidense_align_pyr.argtypes = [vp, vp, vp, vp, vp]
+    lib.vo_semidense_affine_default_params.argtypes = [vp]
+    lib.vo_semidense_align_affine.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+    lib.vo_semidense_align_pyr_affine.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp]
+    lib.vo_svo_set_semidense_align_affine.argtypes = [vp, vp]
+    lib.vo_svo_get_semidense_align_affine.argtypes = [vp, vp, vp, vp, vp]
     lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_five_point_destroy.argtypes = [vp]
     lib.vo_five_point_destroy.restype = None

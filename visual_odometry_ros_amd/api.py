@@ -157,17 +157,24 @@ SEMIDENSE_ALIGN_STATUS = {0: "converged", 1: "max_iters reached", 2: "too few pi
 
 SEMIDENSE_ALIGN_START = {"odometry": 0, "previous": 1}
 SemiDenseAlignedLevel = collections.namedtuple("SemiDenseAlignedLevel", "status iters count rms")
+# with affine brightness (include/vo_hip.h, "Semi-dense alignment with affine brightness"): one more status, G and O per level
+SEMIDENSE_ALIGN_AFFINE_STATUS = {**SEMIDENSE_ALIGN_STATUS, 5: "gain or offset left its range"}
+SemiDenseAlignedAffineLevel = collections.namedtuple("SemiDenseAlignedAffineLevel", "status iters count rms G O")
 
 
-class SemiDenseAligned(collections.namedtuple("SemiDenseAligned", "T_ck status iters count rms H b T_wc frame_id key_frame_id levels start",
-                                              defaults=(None, None))):
+class SemiDenseAligned(collections.namedtuple("SemiDenseAligned",
+                                              "T_ck status iters count rms H b T_wc frame_id key_frame_id levels start gain offset G O",
+                                              defaults=(None, None, None, None, None, None))):
     """An alignment against a semi-dense map (include/vo_hip.h, "Semi-dense alignment"): T_ck float32 (4, 4); status (the keys of
     SEMIDENSE_ALIGN_STATUS), iters; from the last evaluated system count, rms [grey levels], H float64 (6, 6) and b float64 (6,),
     in the order xi = (v, omega) of se3Exp_f. From a driver also T_wc float32 (4, 4) = the keyframe's T_wc times inverseSE3(T_ck),
     the frame's id and the keyframe's (-1 with status 4: a keyframe frame has no result). From the coarse-to-fine calls ("Semi-dense
     alignment on a map pyramid") and a driver also levels: a tuple of SemiDenseAlignedLevel(status, iters, count, rms), index =
     pyramid level, and from a driver start: "previous" where the previous frame's aligned pose was the start, else "odometry" (the
-    pose the call was given: the odometry's, or the identity at the first frame after a keyframe)."""
+    pose the call was given: the odometry's, or the identity at the first frame after a keyframe). With affine brightness
+    ("Semi-dense alignment with affine brightness") also gain, offset [grey levels] and the integers G, O they are formed from; H
+    is then (8, 8) and b (8,), in the order (xi, dg, do), status may be 5 (SEMIDENSE_ALIGN_AFFINE_STATUS) and the levels are
+    SemiDenseAlignedAffineLevel(status, iters, count, rms, G, O)."""
     __slots__ = ()
 
 
@@ -201,15 +208,38 @@ def _semidense_align_pyr_params(lib, params):
     return p
 
 
-def _semidense_aligned(r, T_wc=None, frame_id=None, key_frame_id=None):
-    """vo_semidense_align_result / vo_semidense_align_pyr_result -> SemiDenseAligned (H as the full symmetric matrix)"""
-    H = np.zeros((6, 6), np.float64)
+def _semidense_affine_params(lib, affine):
+    """True or dict(gain0=, offset0=) -> vo_semidense_affine_params: the C defaults, then the caller's fields"""
+    p = _capi.SemiDenseAffineParams()
+    lib.vo_semidense_affine_default_params(C.byref(p))
+    known = {f[0] for f in _capi.SemiDenseAffineParams._fields_}
+    for k, v in ({} if affine is True else dict(affine)).items():
+        if k not in known:
+            raise ValueError(f"semi-dense alignment, affine brightness: unknown parameter {k!r}; known: {sorted(known)}")
+        setattr(p, k, v)
+    return p
+
+
+def _semidense_aligned(r, T_wc=None, frame_id=None, key_frame_id=None, with_levels=True):
+    """vo_semidense_align_result / vo_semidense_align_pyr_result / vo_semidense_align_affine_result -> SemiDenseAligned (H as the
+    full symmetric matrix)"""
+    affine = isinstance(r, _capi.SemiDenseAlignAffineResult)
+    nu = 8 if affine else 6
+    H = np.zeros((nu, nu), np.float64)
     n = 0
-    for i in range(6):
-        for j in range(i, 6):
+    for i in range(nu):
+        for j in range(i, nu):
             H[i, j] = H[j, i] = r.H[n]
             n += 1
     levels = start = None
+    if affine:
+        if with_levels:
+            levels = tuple(SemiDenseAlignedAffineLevel(int(r.level_status[l]), int(r.level_iters[l]), int(r.level_count[l]),
+                                                       float(r.level_rms[l]), int(r.level_G[l]), int(r.level_O[l])) for l in range(r.levels))
+        start = None if frame_id is None else ("previous" if r.start_prev else "odometry")
+        return SemiDenseAligned(np.array(r.T_ck, np.float32).reshape(4, 4), int(r.status), int(r.iters), int(r.count), float(r.rms), H,
+                                np.array(r.b, np.float64), T_wc, frame_id, key_frame_id, levels, start, float(r.gain), float(r.offset),
+                                int(r.G), int(r.O))
     if isinstance(r, _capi.SemiDenseAlignPyrResult):
         levels = tuple(SemiDenseAlignedLevel(int(r.level_status[l]), int(r.level_iters[l]), int(r.level_count[l]), float(r.level_rms[l]))
                        for l in range(r.levels))
@@ -485,12 +515,13 @@ class Context:
                                                   C.byref(p), invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data, ts.ctypes.data, score.ctypes.data, 0))
         return SemiDenseMap(invd, sigma, n_obs, ts, score, None, None, None)
 
-    def semiDenseAlign(self, key, slot_cur, K, T_ck, map, key_on_device=None, map_on_device=False, **params):
+    def semiDenseAlign(self, key, slot_cur, K, T_ck, map, key_on_device=None, map_on_device=False, affine=None, **params):
         """slot_cur's level-0 plane aligned photometrically against the key plane's semi-dense map (include/vo_hip.h, "Semi-dense
         alignment"), from the start T_ck (4 x 4, X_c = R X_k + t) with K = (fx, fy, cx, cy): at most max_iters launches, one call.
         key: a u8 array, or a DEVICE address with key_on_device=stride. map: a SemiDenseMap / dict(invd=, sigma=, n_obs=) of
         arrays, or with map_on_device of DEVICE addresses; it is not modified. Returns a SemiDenseAligned. params: the fields of
-        vo_semidense_align_params."""
+        vo_semidense_align_params. affine=True or dict(gain0=, offset0=): a gain and an offset of the key's grey levels are estimated
+        next to the pose ("Semi-dense alignment with affine brightness"); the result also has gain, offset, H (8, 8), b (8,)."""
         p = _semidense_align_params(self.lib, params)
         Ka = np.ascontiguousarray(K, np.float32).reshape(4)
         Ta = np.ascontiguousarray(T_ck, np.float32).reshape(4, 4)
@@ -510,6 +541,11 @@ class Context:
             if invd.shape != (h, w) or sigma.shape != (h, w) or n_obs.shape != (h, w):
                 raise ValueError(f"the map's planes must be ({h}, {w}) like slot {slot_cur}'s image")
             planes = [invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data]
+        if affine:
+            ap, res = _semidense_affine_params(self.lib, affine), _capi.SemiDenseAlignAffineResult()
+            self.check(self.lib.vo_semidense_align_affine(self._h, pk, stride, int(key_on_device is not None), int(slot_cur), Ka.ctypes.data,
+                                                          Ta.ctypes.data, C.byref(p), C.byref(ap), *planes, int(bool(map_on_device)), C.byref(res)))
+            return _semidense_aligned(res, with_levels=False)
         self.check(self.lib.vo_semidense_align(self._h, pk, stride, int(key_on_device is not None), int(slot_cur), Ka.ctypes.data, Ta.ctypes.data,
                                                C.byref(p), *planes, int(bool(map_on_device)), C.byref(res)))
         return _semidense_aligned(res)
@@ -542,12 +578,13 @@ class Context:
             off += w * h
         return out_levels
 
-    def semiDenseAlignPyramid(self, slot_key, slot_cur, K, T_ck, map, levels=4, map_on_device=False, **params):
+    def semiDenseAlignPyramid(self, slot_key, slot_cur, K, T_ck, map, levels=4, map_on_device=False, affine=None, **params):
         """slot_cur's image aligned against slot_key's image and its semi-dense map, coarse to fine over `levels` levels of both
         slots' pyramids and of a map pyramid the call builds (include/vo_hip.h, "Semi-dense alignment on a map pyramid"), from the
         start T_ck (4 x 4, X_c = R X_k + t) with K = (fx, fy, cx, cy) of level 0. map: a SemiDenseMap / dict(invd=, sigma=, n_obs=)
         of level-0 arrays, or with map_on_device of DEVICE addresses; it is not modified. Returns a SemiDenseAligned with levels.
-        params: the fields of vo_semidense_align_pyr_params."""
+        params: the fields of vo_semidense_align_pyr_params. affine=True or dict(gain0=, offset0=): as semiDenseAlign's; gain and
+        offset are handed from level to level with the pose, and every level reports the G, O it left."""
         p = _semidense_align_pyr_params(self.lib, dict(params, levels=int(levels)))
         Ka = np.ascontiguousarray(K, np.float32).reshape(4)
         Ta = np.ascontiguousarray(T_ck, np.float32).reshape(4, 4)
@@ -562,6 +599,11 @@ class Context:
             if invd.shape != (h, w) or sigma.shape != (h, w) or n_obs.shape != (h, w):
                 raise ValueError(f"the map's planes must be ({h}, {w}) like slot {slot_cur}'s image")
             planes = [invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data]
+        if affine:
+            ap, res = _semidense_affine_params(self.lib, affine), _capi.SemiDenseAlignAffineResult()
+            self.check(self.lib.vo_semidense_align_pyr_affine(self._h, int(slot_key), int(slot_cur), Ka.ctypes.data, Ta.ctypes.data, C.byref(p),
+                                                              C.byref(ap), *planes, int(bool(map_on_device)), C.byref(res)))
+            return _semidense_aligned(res)
         self.check(self.lib.vo_semidense_align_pyr(self._h, int(slot_key), int(slot_cur), Ka.ctypes.data, Ta.ctypes.data, C.byref(p), *planes,
                                                    int(bool(map_on_device)), C.byref(res)))
         return _semidense_aligned(res)
@@ -1533,7 +1575,8 @@ class StereoVO:
         its "temporal": True or dict(z_max=..., max_search=...) also switches setSemiDenseTemporal on, and with it
         "propagate": True or dict(min_obs=, max_diff=, chi=, sigma_add=) setSemiDensePropagate,
         "align": True or dict(min_obs=, huber=, max_iters=, eps=, min_pixels=) setSemiDenseAlign; with levels=, max_iters_level= or
-        start="odometry" | "previous" in it, coarse to fine on a map pyramid (setSemiDenseAlignPyramid).
+        start="odometry" | "previous" in it, coarse to fine on a map pyramid (setSemiDenseAlignPyramid); with affine=True or
+        affine=dict(gain0=, offset0=) in it, gain and offset are estimated next to the pose (setSemiDenseAlignAffine).
         mask: the ignore mask every pair carries from the first one on (setMask).
         zncc_gate: dict(thres=, win=15, pattern="centered", pairs=("temporal",)) — the appearance gate (setZnccGate).
         pose_covariance=True: every frame chains the covariance of its pose on the device (getPoseCovariance); sigma_px > 0
@@ -1752,6 +1795,20 @@ class StereoVO:
         p = _semidense_propagate_params(self.lib, params)
         self.ctx.check(self.lib.vo_svo_set_semidense_propagate(self._h, C.byref(p)))
 
+    def setSemiDenseAlignAffine(self, params):
+        """A modifier of whichever alignment is on (include/vo_hip.h, "Semi-dense alignment with affine brightness"): its launches
+        estimate a gain and an offset of the keyframe's grey levels next to the pose, so that an exposure change between the keyframe
+        and the frame does not bias the pose. params: True or dict(gain0=1, offset0=0); None: off. Needs setSemiDenseAlign or
+        setSemiDenseAlignPyramid on; turning the alignment off turns it off too. getSemiDenseAlign then has gain, offset, G, O, H (8,
+        8) and b (8,). The odometry's results, the semi-dense results and the map do not change. Refused while a frame is in flight."""
+        if params is None or params is False:
+            self.ctx.check(self.lib.vo_svo_set_semidense_align_affine(self._h, None))
+            self._sda_affine = False
+            return
+        p = _semidense_affine_params(self.lib, params)
+        self.ctx.check(self.lib.vo_svo_set_semidense_align_affine(self._h, C.byref(p)))
+        self._sda_affine = True
+
     def setSemiDenseAlign(self, params):
         """Direct image alignment on the keyframe's map (include/vo_hip.h, "Semi-dense alignment"): every frame that is not a
         keyframe aligns its left image against the map as the previous frames left it, from the odometry's pose, on the side stream
@@ -1760,11 +1817,16 @@ class StereoVO:
         while a frame is in flight. A dict that names levels, max_iters_level or start goes to setSemiDenseAlignPyramid."""
         if params is None:
             self.ctx.check(self.lib.vo_svo_set_semidense_align(self._h, None))
+            self._sda_affine = False
             return
         if {"levels", "max_iters_level", "start"} & set(params):
             return self.setSemiDenseAlignPyramid(params)
+        params = dict(params)
+        affine = params.pop("affine", None)
         p = _semidense_align_params(self.lib, params)
         self.ctx.check(self.lib.vo_svo_set_semidense_align(self._h, C.byref(p)))
+        if affine is not None:
+            self.setSemiDenseAlignAffine(affine)
 
     def setSemiDenseAlignPyramid(self, params):
         """The alignment of setSemiDenseAlign coarse to fine (include/vo_hip.h, "Semi-dense alignment on a map pyramid"): at a
@@ -1776,21 +1838,28 @@ class StereoVO:
         the semi-dense results and the map do not change. Needs setSemiDenseTemporal. Refused while a frame is in flight."""
         if params is None:
             self.ctx.check(self.lib.vo_svo_set_semidense_align_pyr(self._h, None, 0))
+            self._sda_affine = False
             return
         prm = dict(params)
+        affine = prm.pop("affine", None)
         start = prm.pop("start", "odometry")
         if start not in SEMIDENSE_ALIGN_START:
             raise ValueError(f"semi-dense alignment: start={start!r}; known: {sorted(SEMIDENSE_ALIGN_START)}")
         p = _semidense_align_pyr_params(self.lib, prm)
         self.ctx.check(self.lib.vo_svo_set_semidense_align_pyr(self._h, C.byref(p), SEMIDENSE_ALIGN_START[start]))
+        if affine is not None:
+            self.setSemiDenseAlignAffine(affine)
 
     def getSemiDenseAlign(self):
         """The last frame's alignment (a SemiDenseAligned with T_wc, frame_id, key_frame_id, the per-level fields and the start that
-        was used); status 4 and key_frame_id -1 at a keyframe frame, which has none. Waits for the side stream's last launch only."""
-        res = _capi.SemiDenseAlignPyrResult()
+        was used); status 4 and key_frame_id -1 at a keyframe frame, which has none. Waits for the side stream's last launch only.
+        With setSemiDenseAlignAffine on: the affine run's, with gain, offset, G, O, H (8, 8) and b (8,)."""
+        affine = getattr(self, "_sda_affine", False)
+        res = _capi.SemiDenseAlignAffineResult() if affine else _capi.SemiDenseAlignPyrResult()
         T = np.zeros((4, 4), np.float32)
         fid, kid = C.c_int(), C.c_int()
-        self.ctx.check(self.lib.vo_svo_get_semidense_align_pyr(self._h, C.byref(res), T.ctypes.data, C.byref(fid), C.byref(kid)))
+        get = self.lib.vo_svo_get_semidense_align_affine if affine else self.lib.vo_svo_get_semidense_align_pyr
+        self.ctx.check(get(self._h, C.byref(res), T.ctypes.data, C.byref(fid), C.byref(kid)))
         return _semidense_aligned(res, T, fid.value, kid.value)
 
     def getSemiDenseOrigin(self):

@@ -499,6 +499,12 @@ class StereoVO {
   bool getSemiDenseAlign(vo_semidense_align_pyr_result &result, float *T_wc = nullptr, int *frame_id = nullptr, int *key_frame_id = nullptr) {
     return impl_.getSemiDenseAlign(result, T_wc, frame_id, key_frame_id);
   }
+  // either alignment with a gain and an offset of the keyframe's grey levels estimated next to the pose
+  // (vo::StereoVO::setSemiDenseAlignAffine): for streams whose exposure changes between a keyframe and its frames
+  void setSemiDenseAlignAffine(const vo_semidense_affine_params *affine) { impl_.setSemiDenseAlignAffine(affine); }
+  bool getSemiDenseAlign(vo_semidense_align_affine_result &result, float *T_wc = nullptr, int *frame_id = nullptr, int *key_frame_id = nullptr) {
+    return impl_.getSemiDenseAlign(result, T_wc, frame_id, key_frame_id);
+  }
   PointVec getSemiDenseMapPoints(bool world = true, int min_obs = 2) {
     vo::PointVec v;
     impl_.getSemiDenseMapPoints(v, nullptr, world, min_obs);

@@ -340,6 +340,21 @@ class StereoVO {
     ctx_->check(vo_svo_get_semidense_align_pyr(svo_, &result, T_wc, frame_id, key_frame_id));
     return result.status != VO_SEMIDENSE_ALIGN_NONE;
   }
+  // A modifier of whichever alignment is on (vo_svo_set_semidense_align_affine; include/vo_hip.h, "Semi-dense alignment with affine
+  // brightness"): a gain and an offset of the keyframe's grey levels are estimated next to the pose, so that an exposure change
+  // between the keyframe and the frame does not bias it. affine = nullptr: off. Needs setSemiDenseAlign or setSemiDenseAlignPyramid.
+  static vo_semidense_affine_params defaultSemiDenseAffineParams() {
+    vo_semidense_affine_params p;
+    vo_semidense_affine_default_params(&p);
+    return p;
+  }
+  void setSemiDenseAlignAffine(const vo_semidense_affine_params *affine) { ctx_->check(vo_svo_set_semidense_align_affine(svo_, affine)); }
+  // getSemiDenseAlign with gain, offset, G, O, the 8 x 8 system and G, O per level; refused while the modifier is off (the two
+  // getters above then serve, and while it is on return the affine run's pose, status, iters, count and rms)
+  bool getSemiDenseAlign(vo_semidense_align_affine_result &result, float *T_wc = nullptr, int *frame_id = nullptr, int *key_frame_id = nullptr) {
+    ctx_->check(vo_svo_get_semidense_align_affine(svo_, &result, T_wc, frame_id, key_frame_id));
+    return result.status != VO_SEMIDENSE_ALIGN_NONE;
+  }
   // NOT in the reference: CLAHE on every image before the tracker (vo::Context::setEqualize on this driver's context): legal
   // between frames, applies to the images handed over from now on
   void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) { ctx_->setEqualize(mode, clip_limit, tiles_x, tiles_y); }

@@ -69,6 +69,10 @@ struct vo_svo_semidense_align {
   vo_sdm_pyramid py;
   int key_levels = 0, key_levels_of = -1;
   int prev_key = -1;  // the keyframe the PREVIOUS frame's result is against (-1: it has none)
+  // vo_svo_set_semidense_align_affine: either option's launches run the kernel with affine brightness on a state block of its own
+  bool affine = false;
+  vo_semidense_affine_params aprm = {};
+  vo_sda_buffers abuf;
 };
 
 struct vo_svo {

@@ -333,6 +333,13 @@ int vo_sdm_enqueue(vo_ctx *c, int w, int h, int levels, float *const invd[], flo
 int vo_sda_enqueue_pyr(vo_ctx *c, vo_sda_buffers *b, const uint8_t *const key[], const int key_stride[], int slot_cur, const float K[4],
                        const float T_ck[16], const vo_semidense_align_pyr_params *p, const float *const invd[], const float *const sigma[],
                        const uint8_t *const n_obs[], int first);
+// The alignment with affine brightness (include/vo_hip.h, "Semi-dense alignment with affine brightness"): a state block of its own
+// kind and 47 sums per block in a vo_sda_buffers of its own; the launches of vo_sda_enqueue_pyr with that block's kernel (levels = 1
+// with the key plane as key[0]: the level-0 operator).
+int vo_sdaa_buffers_alloc(vo_ctx *c, vo_sda_buffers *b);
+int vo_sdaa_enqueue_pyr(vo_ctx *c, vo_sda_buffers *b, const uint8_t *const key[], const int key_stride[], int slot_cur, const float K[4],
+                        const float T_ck[16], const vo_semidense_align_pyr_params *p, const vo_semidense_affine_params *ap,
+                        const float *const invd[], const float *const sigma[], const uint8_t *const n_obs[], int first);
 
 // Image ingestion (H2D + pyramid chain) enqueues on the side stream when vo_set_ingest_side_stream is on: launchers
 // use c->stream, which this scope points at the ingest stream and restores on exit.
