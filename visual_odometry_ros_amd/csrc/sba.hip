@@ -722,8 +722,10 @@ __global__ __launch_bounds__(64) void sba_solve_kernel(SbaDev d, int iter) {
 // compile-time constant, so the factorisation is straight-line code: per (step k, column j < k) one lane broadcast of
 // L(k,j) (two v_readlane), temp_j = D_j L(k,j), one multiply and one add per lane — no LDS round trip, no barrier, the
 // same operations in the same order as sba_solve_kernel (and oracle_sba.c). 42 LDLT steps: 38 -> ~10 us. L is written
-// to LDS once for the transposed sweep, which needs column access. Ties among the |diagonal| values (exact equality)
-// take the sequential pivot pre-pass, as in the general kernel.
+// to LDS once for the transposed sweep, which needs column access: each lane reads its column back in one batch and the
+// sweep runs out of registers. The lane broadcasts of the factorisation go two k at a time so that no multiply waits for
+// its scalar operand. Ties among the |diagonal| values (exact equality) take the sequential pivot pre-pass, as in the
+// general kernel.
 __device__ __forceinline__ double sba_rl(double v, int src) {
   int2 p = __builtin_bit_cast(int2, v);
   p.x = __builtin_amdgcn_readlane(p.x, src);
@@ -829,13 +831,14 @@ __device__ __forceinline__ void sba_reg_solve_wave(double *sL, double *s_dg, int
   // ---- pivot order (see sba_solve_kernel): descending |diagonal| unless two are exactly equal
   {
     const double v = lane < N ? fabs(sL[lane * N + lane]) : -1.0;
-    int rank = 0, tie = 0;
+    int rank = 0, same = 0;  // same: a value equals itself, so a tie is a count above one (a NaN equals nothing: no tie)
 #pragma unroll
     for (int j = 0; j < N; ++j) {
       const double vj = sba_rl(v, j);
       rank += (vj > v) ? 1 : 0;
-      tie |= (vj == v && j != lane) ? 1 : 0;
+      same += (vj == v) ? 1 : 0;
     }
+    const int tie = same > 1;
     if (!__any(tie && lane < N)) {
       if (lane < N) s_sig[rank] = lane;
     } else {
@@ -870,8 +873,8 @@ __device__ __forceinline__ void sba_reg_solve_wave(double *sL, double *s_dg, int
     const int hi = my > sj ? my : sj, lo = my > sj ? sj : my;
     r[j] = sL[hi * N + lo];
   }
-#pragma unroll
-  for (int j = 0; j < N; ++j) r[j] = (lane < N && j <= lane) ? r[j] : 0.0;
+  // (entries j > lane, and every entry of a lane >= N, are loaded but never reach a result: the factorisation and both
+  // sweeps read r[j] under lane > j, the accumulators of a lane only from column lane on — zeroing them was 126 instructions)
   double y = lane < N ? sL[N * N + my] : 0.0;
   SBA_WAVE_SYNC();  // (sL is written again below)
   t_1 = sba_stamp_after(r[0] + y);
@@ -883,7 +886,9 @@ __device__ __forceinline__ void sba_reg_solve_wave(double *sL, double *s_dg, int
   // column k's turn comes: the same sums in the same order as the left-looking form (same bits), ~13 -> ~8 us.
   // (Finalising column j + 1 in front of the rest of column j's updates, to fill its chain of ~17 dependent instructions,
   // measured the same 9.9 us: 5 500 instructions of one wavefront at ~4.4 cycles each — two lane broadcasts, a wait state, a
-  // multiply and an add per (j, k) — is what the factorisation costs.)
+  // multiply and an add per (j, k). The wait state is gone below: 4 700 instructions. The bulk of a column through LDS
+  // broadcast reads one step behind, 2.5 slots per pair, was built too: the compiler hoists every read of a row in front of
+  // the arithmetic and spills 820 registers, and nothing short of inline assembly pins arithmetic — DESIGN.md facts table.)
   double dgl = 0.0;  // this lane's final diagonal entry D(lane)
   double acc[N];     // acc[k] = sum_{j < k, final} M(lane,j) temp_k[j], temp_k[j] = D_j M(k,j)
 #pragma unroll
@@ -895,8 +900,28 @@ __device__ __forceinline__ void sba_reg_solve_wave(double *sL, double *s_dg, int
     if (lane == j) dgl = ajj;
     if (fabs(ajj) > 0.0 && lane > j) r[j] /= ajj;
     const double wj = ajj * r[j];  // lane k: D_j M(k,j) = temp[j] of step k
+    // two k at a time, software-pipelined and pinned: [four lane reads] [the two adds of the pair before] [two multiplies].
+    // A multiply may read the scalar pair of a lane read two issue slots after it was written at the earliest; left to
+    // itself the scheduler reuses one pair and pays a wait state per (j, k).
+    double p0 = 0.0, p1 = 0.0;
 #pragma unroll
-    for (int k = j + 1; k < N; ++k) acc[k] += r[j] * sba_rl(wj, k);
+    for (int k = j + 1; k < N; k += 2) {
+      const double b0 = sba_rl(wj, k), b1 = k + 1 < N ? sba_rl(wj, k + 1) : 0.0;
+      __builtin_amdgcn_sched_barrier(0);
+      if (k > j + 1) {
+        acc[k - 2] += p0;
+        acc[k - 1] += p1;
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      p0 = r[j] * b0;
+      if (k + 1 < N) p1 = r[j] * b1;
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    if (j + 1 < N) {
+      const int kl = j + 1 + ((N - 1 - j - 1) / 2) * 2;  // the first k of the last pair
+      acc[kl] += p0;
+      if (kl + 1 < N) acc[kl + 1] += p1;
+    }
   }
   t_f = sba_stamp_after(dgl + r[N - 1]);
   // ---- solve: x = P^T L^-T D^+ L^-1 (P rhs); the entry of lane i stays in a register
@@ -907,13 +932,23 @@ __device__ __forceinline__ void sba_reg_solve_wave(double *sL, double *s_dg, int
   }
   const double tol = 2.2250738585072014e-308;
   if (lane < N) y = fabs(dgl) > tol ? y / dgl : 0.0;
+  // (the whole row under one mask instead of a mask per column: what lands on the diagonal and above it is never read)
+  if (lane < N) {
 #pragma unroll
-  for (int j = 0; j < N; ++j)
-    if (lane < N && j < lane) sL[lane * N + j] = r[j];
+    for (int j = 0; j < N - 1; ++j) sL[lane * N + j] = r[j];
+  }
   SBA_WAVE_SYNC();
-  for (int q = N - 1; q > 0; --q) {  // L^T sweep in DECREASING q, as sba_solve_kernel
-    const double yq = sba_rl(y, q);  // (q is wave-uniform)
-    if (lane < q) y -= sL[q * N + lane] * yq;
+  // column `lane` of L in one batch of loads — L(q, lane) does not depend on y, and the row registers are free — then the L^T
+  // sweep in DECREASING q, as sba_solve_kernel, out of registers: a select per step like the forward sweep, no LDS round
+  // trip and no branch on the chain. (lanes >= q read the upper triangle or column 0; the select drops what they compute)
+  const int cl = lane < N ? lane : 0;
+#pragma unroll
+  for (int q = 1; q < N; ++q) r[q] = sL[q * N + cl];
+#pragma unroll
+  for (int q = N - 1; q > 0; --q) {
+    const double yq = sba_rl(y, q);
+    const double t = y - r[q] * yq;
+    y = lane < q ? t : y;
   }
   // P^T: scatter back through sig
   if (lane < N) s_dg[my] = y;
