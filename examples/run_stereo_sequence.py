@@ -19,7 +19,10 @@ update (the temporal search and fusion); `semidense_fused_<keyframe's frame id>.
 2) observations (N = 1 keeps what the static result alone gave), written when the next keyframe replaces the map and at the end
 of the run. --semidense-propagate: with --semidense-temporal, a keyframe's map is carried over to the next keyframe (warped under
 the odometry's pose, fused with the new static result) instead of being seeded afresh, so a keyframe's file also holds what earlier
-keyframes observed. --semidense-align FILE: with --semidense-temporal, every frame that is not a keyframe aligns its left image
+keyframes observed. --semidense-regularize: with --semidense-temporal, a regularised copy of the map is kept next to it (entries their
+neighbours contradict removed, high-gradient holes whose neighbours agree filled, values smoothed) and written as
+`semidense_regularized_<keyframe's frame id>.ply` wherever the fused file is written; its filled pixels have one observation, so N
+applies to the measured ones only. --semidense-align FILE: with --semidense-temporal, every frame that is not a keyframe aligns its left image
 photometrically against the keyframe's map, from the odometry's pose (a second pose estimate; nothing uses it); one line per frame:
 frame id, keyframe's frame id (-1 at a keyframe frame), status (0 converged, 1 max_iters, 2 too few pixels, 3 singular, 4 none),
 iterations, pixel count, rms in grey levels, the 12 numbers of the aligned [R|t] of T_wc, and its translation [m] and rotation
@@ -95,7 +98,11 @@ def semidense_options(args):
             raise SystemExit("--semidense-every / --semidense-depth need --semidense DIR")
         if args.semidense_temporal or args.semidense_min_obs is not None or args.semidense_propagate or args.semidense_align:
             raise SystemExit("--semidense-temporal / --semidense-min-obs / --semidense-propagate / --semidense-align need --semidense DIR")
+        if args.semidense_regularize:
+            raise SystemExit("--semidense-regularize needs --semidense DIR")
         return {}
+    if args.semidense_regularize and not args.semidense_temporal:
+        raise SystemExit("--semidense-regularize needs --semidense-temporal")
     if args.semidense_propagate and not args.semidense_temporal:
         raise SystemExit("--semidense-propagate needs --semidense-temporal")
     if args.semidense_align and not args.semidense_temporal:
@@ -118,6 +125,8 @@ def semidense_options(args):
         sd["temporal"] = True
     if args.semidense_propagate:
         sd["propagate"] = True
+    if args.semidense_regularize:
+        sd["regularize"] = True
     if args.semidense_align:
         sd["align"] = True
         if args.semidense_align_levels is not None or args.semidense_align_start is not None:
@@ -183,6 +192,8 @@ def parse_args(argv=None):
                     help="--semidense: fuse every keyframe's depth with the following frames; semidense_fused_<id>.ply per keyframe")
     ap.add_argument("--semidense-propagate", action="store_true",
                     help="--semidense-temporal: carry a keyframe's fused map over to the next keyframe instead of seeding it afresh")
+    ap.add_argument("--semidense-regularize", action="store_true",
+                    help="--semidense-temporal: also keep a regularised copy of the map; semidense_regularized_<id>.ply per keyframe")
     ap.add_argument("--semidense-align", default=None, metavar="FILE",
                     help="--semidense-temporal: align every later frame's left image against the keyframe's map; one line per frame into FILE")
     ap.add_argument("--semidense-align-levels", type=int, default=None, metavar="N",
@@ -209,12 +220,14 @@ def main():
                                **zncc_options(args), **semidense_options(args))
     if args.semidense:
         os.makedirs(args.semidense, exist_ok=True)
-    sd_last, fused = -1, None  # (fused: the current keyframe's map as points, as of the last frame)
+    sd_last, fused, regd = -1, None, None  # (fused, regd: the current keyframe's map and its regularised copy as points, as of the last frame)
     min_obs = args.semidense_min_obs or 2
 
     def write_fused():
         if fused is not None:
             write_ply(os.path.join(args.semidense, f"semidense_fused_{fused['frame_id']:06d}.ply"), fused["xyz"], fused["sigma_invd"])
+        if regd is not None:
+            write_ply(os.path.join(args.semidense, f"semidense_regularized_{regd['frame_id']:06d}.ply"), regd["xyz"], regd["sigma_invd"])
     cov_file = open(args.covariance, "w") if args.covariance else None
     align_file = open(args.semidense_align, "w") if args.semidense_align else None
     svo.ctx.sum_order = args.sum_order
@@ -250,6 +263,8 @@ def main():
             if info.is_keyframe:
                 write_fused()
             fused = svo.getSemiDensePoints(world=True, fused=True, min_obs=min_obs)
+            if args.semidense_regularize:  # (a filled pixel has one observation: min_obs would drop what the option adds)
+                regd = svo.getSemiDensePoints(world=True, fused=True, regularized=True, min_obs=1)
         if k % 100 == 0 or k == n - 1:
             t = poses[-1][:3, 3]
             print(f"frame {k:6d}: {info.n_tracks_out:5d} tracks, {n_kf:4d} keyframes, position ({t[0]:9.3f} {t[1]:9.3f} {t[2]:9.3f})", flush=True)

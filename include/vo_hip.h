@@ -1199,6 +1199,71 @@ int vo_semidense_align_pyr_affine(vo_ctx *ctx, int slot_key, int slot_cur, const
 int vo_svo_set_semidense_align_affine(vo_svo *svo, const vo_semidense_affine_params *affine);
 int vo_svo_get_semidense_align_affine(vo_svo *svo, vo_semidense_align_affine_result *result, float T_wc[16], int *frame_id, int *key_frame_id);
 
+/* ---- Semi-dense regularisation: outlier removal, fill and smoothing of a map over each pixel's neighbourhood ----
+ * Every block above treats a map pixel on its own. This one asks whether a pixel agrees with the pixels next to it (LSD-SLAM's
+ * regularizeDepthMap / regularizeDepthMapFillHoles): an entry without consistent neighbours, or with more inconsistent than
+ * consistent ones, is removed; a high-gradient pixel without an entry whose neighbours agree with each other is filled; every kept
+ * value is replaced by a weighted mean of its consistent neighbours. What it gains is robustness and coverage, not precision on good
+ * pixels (§23 has the figures). Opt-in; it writes planes of its own and the blocks above keep their bits.
+ * Only + - x / sqrtf in float32, every operation rounded on its own (no FMA), in the order written here. All sums are per pixel, over
+ * the neighbours (x + dx, y + dy) in the order dy = -r .. r outer, dx = -r .. r inner, r = radius; neighbours outside the image do
+ * not exist. tests/semidense_regularize_restatement.py restates it.
+ *   inputs     a map: three W x H planes invd f32, sigma f32, n_obs u8, 3 <= W, H <= 65535; the keyframe's left level-0 u8 plane
+ *              Lk; an optional W x H u8 ignore mask (0 = ignore).
+ *   params     radius 1..3; chi > 0; dist_sigma >= 0 [1/m per pixel]; min_support 0..48; fill_min 0..48 (0: no filling);
+ *              g_min 1..360; all finite (VO_ERR_INVALID otherwise).
+ *   entry      a pixel with n_obs >= 1, 0 < sigma <= FLT_MAX and 0 < invd <= FLT_MAX (NaN and inf fail these tests: they never
+ *              enter a sum). var = sigma sigma.
+ *   stage A    fill. A candidate is a pixel that has no entry, with 1 <= x <= W-2 and 1 <= y <= H-2, whose mask byte is not 0,
+ *              with gx, gy as in the static block on Lk: gx^2 + gy^2 >= g_min^2 (integers), and fill_min > 0. Over its neighbours
+ *              that have an entry: w_n = 1 / var_n; S += invd_n w_n; Wt += w_n; V += var_n; cnt = their count; mean = S / Wt;
+ *              vmean = V / (float)cnt. It is filled where cnt >= fill_min and EVERY counted neighbour has dd = invd_n - mean,
+ *              dd dd <= (chi chi) (var_n + vmean): one neighbour off the mean refuses the fill, so that nothing is invented across a
+ *              depth step. A filled pixel carries invd = mean, var = vmean, n_obs = 1. (The mean variance, not 1 / Wt: neighbouring
+ *              pixels share taps — the map pyramid's stance.)
+ *   stage B    over map A = the entries and the filled pixels. For a pixel c of A and every neighbour n of A, c itself included:
+ *              dd = invd_n - invd_c; n is consistent where dd dd <= (chi chi) (var_c + var_n). Over the consistent ones:
+ *              w_n = 1 / (var_n + (dist_sigma dist_sigma) (float)(dx^2 + dy^2)); S += invd_n w_n; Wt += w_n. Two counts over the
+ *              ORIGINAL entries other than c (filled pixels vote in the mean, but neither support nor conflict): support = the
+ *              consistent ones, conflict = the others. c is kept where support >= min_support and conflict <= support.
+ *   outputs    four planes of their own. A kept pixel: invd_r = S / Wt, sigma_r = sqrtf(var_c) — the pixel's own: the regularised
+ *              map claims no information the filter did not have —, n_obs_r = its n_obs (a filled pixel's: 1). Everything else 0.
+ *              rstatus u8: 0 nothing (a filled pixel that is not kept included), 1 an entry kept and smoothed, 2 an entry removed,
+ *              3 filled and kept.
+ * vo_semidense_map_regularize: the operator, one launch, synchronous. The map, the mask (may be NULL) and the outputs are host
+ * planes, or all device planes with on_device; key_plane (key_stride bytes per row) is a host plane, or a device plane with
+ * key_on_device. No output may be an input or another output (VO_ERR_INVALID). The planes may not exceed vo_config.max_width x
+ * max_height. The result is a map: vo_semidense_align*, vo_semidense_map_pyramid and vo_semidense_map_points take it.
+ *
+ * StereoVO: vo_svo_set_semidense_regularize(svo, prm) — NULL = off — needs vo_svo_set_semidense_temporal on and makes its only
+ * allocation (the four planes) at the first enable; VO_ERR_INVALID while a frame is in flight or on a mono driver. With it off no
+ * launch, allocation, wait or result bit differs; with it on the odometry's results, the static result and the map are the same
+ * bits: the alignment, the propagation and the temporal search keep reading the raw map. vo_svo_result enqueues one launch on the
+ * side stream behind every launch that writes the map — at a keyframe the seed or the propagation's resolve (it then reads the set
+ * of planes that is current after the swap), at every other frame the temporal launch — with the key plane and the keyframe's mask
+ * copy the temporal option keeps; nothing waits for it. vo_svo_get_semidense_regularized: the planes (any may be NULL), size (0 x 0
+ * before the first launch since the option was switched on), the keyframe's frame_id and T_wc, n_fused as vo_svo_get_semidense_map.
+ * vo_svo_get_semidense_regularized_points: as vo_svo_get_semidense_map_points, of the regularised map. Both wait for the side
+ * stream's last launch only; VO_ERR_INVALID while a frame is in flight or with the option off. Not for MonoVO or vo_batch streams. */
+typedef struct {
+  int radius;        /* 2 */
+  float chi;         /* 2.0 */
+  float dist_sigma;  /* 0.01 [1/m per pixel] */
+  int min_support;   /* 1 */
+  int fill_min;      /* 8 */
+  int g_min;         /* 20 */
+} vo_semidense_regularize_params;
+int vo_semidense_regularize_default_params(vo_semidense_regularize_params *prm);
+int vo_semidense_map_regularize(vo_ctx *ctx, const float *invd, const float *sigma, const uint8_t *n_obs, const uint8_t *key_plane,
+                                int key_stride, int key_on_device, const uint8_t *mask, int width, int height,
+                                const vo_semidense_regularize_params *prm, float *invd_r, float *sigma_r, uint8_t *n_obs_r, uint8_t *rstatus,
+                                int on_device);
+int vo_svo_set_semidense_regularize(vo_svo *svo, const vo_semidense_regularize_params *prm);
+int vo_svo_get_semidense_regularized(vo_svo *svo, float *invd, float *sigma, uint8_t *n_obs, uint8_t *rstatus, int *width, int *height,
+                                     int *frame_id, float T_wc[16], int *n_fused);
+int vo_svo_get_semidense_regularized_points(vo_svo *svo, int world, int min_obs, int cap, float *xyz, float *sigma, uint16_t *pixel, int *n,
+                                            int *frame_id);
+
 /* ---- undistortion / stereo rectification in front of the trackers ----------
  * core/visual_odometry/camera.cpp. A context holds the maps of two cameras
  * (cam 0 = left or the mono camera, cam 1 = right), device-resident. */

@@ -11,4 +11,5 @@ from .api import (Context, FeatureTracker, MotionEstimator, FeatureExtractor,  #
                   SparseBundleAdjustmentSolver, TrackIds, se3Exp_f, write_trajectory, StereoVO, MonoVO, triangulateDLT, ImageSlots, StereoBatch,
                   FivePointRansac, PoseInformation, PoseCovariance, propagate_pose_covariance, pose_covariance_ros,
                   se3_adjoint, SemiDenseResult, SemiDenseMap, semidense_disparity_range, SemiDensePropagated, SemiDenseAligned, SemiDenseAlignedLevel,
-                  SEMIDENSE_ALIGN_STATUS, SemiDenseAlignedAffineLevel, SEMIDENSE_ALIGN_AFFINE_STATUS)
+                  SEMIDENSE_ALIGN_STATUS, SemiDenseAlignedAffineLevel, SEMIDENSE_ALIGN_AFFINE_STATUS,
+                  SemiDenseRegularized, SEMIDENSE_RSTATUS)

@@ -118,6 +118,11 @@ class SemiDensePropagateParams(C.Structure):  # vo_semidense_propagate_params
     _fields_ = [("min_obs", C.c_int), ("max_diff", C.c_int), ("chi", C.c_float), ("sigma_add", C.c_float)]
 
 
+class SemiDenseRegularizeParams(C.Structure):  # vo_semidense_regularize_params
+    _fields_ = [("radius", C.c_int), ("chi", C.c_float), ("dist_sigma", C.c_float), ("min_support", C.c_int), ("fill_min", C.c_int),
+                ("g_min", C.c_int)]
+
+
 class SemiDenseAlignParams(C.Structure):  # vo_semidense_align_params
     _fields_ = [("min_obs", C.c_int), ("huber", C.c_float), ("max_iters", C.c_int), ("eps", C.c_float), ("min_pixels", C.c_int)]
 
@@ -203,6 +208,8 @@ SYMBOLS = [
     "vo_svo_set_semidense_align_pyr", "vo_svo_get_semidense_align_pyr",
     "vo_semidense_affine_default_params", "vo_semidense_align_affine", "vo_semidense_align_pyr_affine", "vo_svo_set_semidense_align_affine",
     "vo_svo_get_semidense_align_affine",
+    "vo_semidense_regularize_default_params", "vo_semidense_map_regularize", "vo_svo_set_semidense_regularize",
+    "vo_svo_get_semidense_regularized", "vo_svo_get_semidense_regularized_points",
 ]
 
 _lib = None
@@ -334,6 +341,11 @@ def load():
     lib.vo_semidense_align_pyr_affine.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp, ci, vp]
     lib.vo_svo_set_semidense_align_affine.argtypes = [vp, vp]
     lib.vo_svo_get_semidense_align_affine.argtypes = [vp, vp, vp, vp, vp]
+    lib.vo_semidense_regularize_default_params.argtypes = [vp]
+    lib.vo_semidense_map_regularize.argtypes = [vp, vp, vp, vp, vp, ci, ci, vp, ci, ci, vp, vp, vp, vp, vp, ci]
+    lib.vo_svo_set_semidense_regularize.argtypes = [vp, vp]
+    lib.vo_svo_get_semidense_regularized.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.vo_svo_get_semidense_regularized_points.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp]
     lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_five_point_destroy.argtypes = [vp]
     lib.vo_five_point_destroy.restype = None

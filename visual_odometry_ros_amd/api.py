@@ -152,6 +152,30 @@ def _semidense_propagate_params(lib, params):
     return p
 
 
+SEMIDENSE_RSTATUS = {0: "nothing", 1: "kept and smoothed", 2: "an entry removed", 3: "filled and kept"}
+
+
+class SemiDenseRegularized(collections.namedtuple("SemiDenseRegularized", "invd sigma n_obs rstatus frame_id T_wc n_fused",
+                                                  defaults=(None, None, None))):
+    """A regularised semi-dense map (include/vo_hip.h, "Semi-dense regularisation"): invd, sigma float32 (height, width), n_obs uint8
+    — a map like a SemiDenseMap: semiDenseAlign, semiDenseAlignPyramid and semiDenseMapPyramid take it as their map, semiDenseMapPoints
+    its planes — and rstatus uint8 (the keys of SEMIDENSE_RSTATUS); from a driver also the keyframe's frame id, its T_wc and the
+    number of frames fused so far."""
+    __slots__ = ()
+
+
+def _semidense_regularize_params(lib, params):
+    """keyword parameters -> vo_semidense_regularize_params: the C defaults, then the caller's fields"""
+    p = _capi.SemiDenseRegularizeParams()
+    lib.vo_semidense_regularize_default_params(C.byref(p))
+    known = {f[0] for f in _capi.SemiDenseRegularizeParams._fields_}
+    for k, v in dict(params).items():
+        if k not in known:
+            raise ValueError(f"semi-dense regularisation: unknown parameter {k!r}; known: {sorted(known)}")
+        setattr(p, k, v)
+    return p
+
+
 SEMIDENSE_ALIGN_STATUS = {0: "converged", 1: "max_iters reached", 2: "too few pixels", 3: "singular system", 4: "no result"}
 
 
@@ -646,9 +670,50 @@ class Context:
             n_obs.ctypes.data, ts.ctypes.data, origin.ctypes.data, src.ctypes.data, 0))
         return SemiDensePropagated(invd, sigma, n_obs, ts, origin, src)
 
-    def semiDenseMapPoints(self, invd, sigma, n_obs, K, T=None, min_obs=1, capacity=None, on_device=None):
+    def semiDenseMapRegularize(self, map, key, mask=None, out=None, key_on_device=None, **params):
+        """A map regularised over each pixel's neighbourhood (include/vo_hip.h, "Semi-dense regularisation"): entries without
+        consistent neighbours removed, high-gradient holes whose neighbours agree filled, every kept value smoothed. map: a
+        SemiDenseMap / dict(invd=, sigma=, n_obs=) of arrays, key the keyframe's left u8 plane (an array, or a DEVICE address with
+        key_on_device=stride), mask an optional u8 plane (0 = ignore). Returns a SemiDenseRegularized; the arguments stay. With
+        out=dict(invd=, sigma=, n_obs=, rstatus=, size=(width, height)) of DEVICE addresses the map's planes and the mask are DEVICE
+        addresses too and None is returned. params: the fields of vo_semidense_regularize_params."""
+        p = _semidense_regularize_params(self.lib, params)
+        get = (lambda k: getattr(map, k)) if isinstance(map, tuple) else (lambda k: map[k])
+        if key_on_device is not None:
+            pk, stride = C.c_void_p(key), int(key_on_device)
+        else:
+            ka = _u8(key)
+            pk, stride = ka.ctypes.data, ka.strides[0]
+        if out is not None:
+            w, h = out["size"]
+            self.check(self.lib.vo_semidense_map_regularize(
+                self._h, *(C.c_void_p(get(k)) for k in ("invd", "sigma", "n_obs")), pk, stride, int(key_on_device is not None),
+                C.c_void_p(mask) if mask else None, int(w), int(h), C.byref(p),
+                *(C.c_void_p(out[k]) for k in ("invd", "sigma", "n_obs", "rstatus")), 1))
+            return None
+        invd, sigma = np.ascontiguousarray(get("invd"), np.float32), np.ascontiguousarray(get("sigma"), np.float32)
+        n_obs = np.ascontiguousarray(get("n_obs"), np.uint8)
+        ma = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        if invd.ndim != 2 or sigma.shape != invd.shape or n_obs.shape != invd.shape or (ma is not None and ma.shape != invd.shape) or \
+                (key_on_device is None and ka.shape != invd.shape):
+            raise ValueError("invd, sigma, n_obs, key and mask are planes of one (height, width)")
+        h, w = invd.shape
+        o_invd, o_sigma = np.zeros((h, w), np.float32), np.zeros((h, w), np.float32)
+        o_no, o_rs = np.zeros((h, w), np.uint8), np.zeros((h, w), np.uint8)
+        self.check(self.lib.vo_semidense_map_regularize(
+            self._h, invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data, pk, stride, int(key_on_device is not None),
+            None if ma is None else ma.ctypes.data, w, h, C.byref(p), o_invd.ctypes.data, o_sigma.ctypes.data, o_no.ctypes.data,
+            o_rs.ctypes.data, 0))
+        return SemiDenseRegularized(o_invd, o_sigma, o_no, o_rs)
+
+    def semiDenseMapPoints(self, invd, sigma=None, n_obs=None, K=None, T=None, min_obs=1, capacity=None, on_device=None):
         """The map's pixels with n_obs >= min_obs in raster order: (xyz float32 [n, 3], sigma float32 [n], pixel uint16 [n, 2]) with
-        z = 1 / invd; the rest as semiDensePoints."""
+        z = 1 / invd; the rest as semiDensePoints. In place of the three planes a map tuple (SemiDenseMap, SemiDenseRegularized,
+        SemiDensePropagated) may be given alone: semiDenseMapPoints(map, K=K, ...)."""
+        if isinstance(invd, tuple) and sigma is None and n_obs is None:
+            invd, sigma, n_obs = invd.invd, invd.sigma, invd.n_obs
+        if sigma is None or n_obs is None or K is None:
+            raise ValueError("semiDenseMapPoints: invd, sigma, n_obs (or a map tuple) and K")
         if on_device is not None:
             w, h = on_device
             pi, ps, pn = C.c_void_p(invd), C.c_void_p(sigma), C.c_void_p(n_obs)
@@ -1574,6 +1639,7 @@ class StereoVO:
         semidense: dict of semi-dense stereo parameters (setSemiDense; "every": "keyframe" or "frame") — depth of the keyframes' pairs;
         its "temporal": True or dict(z_max=..., max_search=...) also switches setSemiDenseTemporal on, and with it
         "propagate": True or dict(min_obs=, max_diff=, chi=, sigma_add=) setSemiDensePropagate,
+        "regularize": True or dict(radius=, chi=, dist_sigma=, min_support=, fill_min=, g_min=) setSemiDenseRegularize,
         "align": True or dict(min_obs=, huber=, max_iters=, eps=, min_pixels=) setSemiDenseAlign; with levels=, max_iters_level= or
         start="odometry" | "previous" in it, coarse to fine on a map pyramid (setSemiDenseAlignPyramid); with affine=True or
         affine=dict(gain0=, offset0=) in it, gain and offset are estimated next to the pose (setSemiDenseAlignAffine).
@@ -1609,8 +1675,11 @@ class StereoVO:
         if semidense is not None:
             sd = dict(semidense)
             temporal, propagate, align = sd.pop("temporal", None), sd.pop("propagate", None), sd.pop("align", None)
+            regularize = sd.pop("regularize", None)
             if propagate and not temporal:
                 raise ValueError('semidense: "propagate" needs "temporal"')
+            if regularize and not temporal:
+                raise ValueError('semidense: "regularize" needs "temporal"')
             if align and not temporal:
                 raise ValueError('semidense: "align" needs "temporal"')
             self.setSemiDense(sd, every=sd.pop("every", "keyframe"))
@@ -1620,6 +1689,8 @@ class StereoVO:
                 self.setSemiDensePropagate({} if propagate is True else propagate)
             if align:
                 self.setSemiDenseAlign({} if align is True else align)
+            if regularize:
+                self.setSemiDenseRegularize({} if regularize is True else regularize)
         self._info = SvoFrameInfo()
         self.stats_frame = []  # AlgorithmStatistics::FrameStatistics::Twc per frame (stereo_vo.cpp:979-980)
 
@@ -1769,11 +1840,22 @@ class StereoVO:
         p = _semidense_temporal_params(self.lib, params)
         self.ctx.check(self.lib.vo_svo_set_semidense_temporal(self._h, C.byref(p)))
 
-    def getSemiDenseMap(self):
+    def getSemiDenseMap(self, regularized=False):
         """The last keyframe's map (a SemiDenseMap with frame_id, T_wc (4, 4) and n_fused), None before a keyframe. Waits for the side
-        stream's last launch only."""
+        stream's last launch only. regularized=True (setSemiDenseRegularize): the regularised copy of that map instead, a
+        SemiDenseRegularized with rstatus; None before the first frame since the option was switched on."""
         w, h, fid, nf = C.c_int(), C.c_int(), C.c_int(), C.c_int()
         T = np.zeros((4, 4), np.float32)
+        if regularized:
+            get = self.lib.vo_svo_get_semidense_regularized
+            self.ctx.check(get(self._h, None, None, None, None, C.byref(w), C.byref(h), C.byref(fid), None, None))
+            if w.value <= 0:
+                return None
+            invd, sg = np.zeros((h.value, w.value), np.float32), np.zeros((h.value, w.value), np.float32)
+            no, rs = np.zeros((h.value, w.value), np.uint8), np.zeros((h.value, w.value), np.uint8)
+            self.ctx.check(get(self._h, invd.ctypes.data, sg.ctypes.data, no.ctypes.data, rs.ctypes.data, C.byref(w), C.byref(h), C.byref(fid),
+                               T.ctypes.data, C.byref(nf)))
+            return SemiDenseRegularized(invd, sg, no, rs, fid.value, T, nf.value)
         self.ctx.check(self.lib.vo_svo_get_semidense_map(self._h, None, None, None, None, C.byref(w), C.byref(h), C.byref(fid), None, None))
         if w.value <= 0:
             return None
@@ -1794,6 +1876,19 @@ class StereoVO:
             return
         p = _semidense_propagate_params(self.lib, params)
         self.ctx.check(self.lib.vo_svo_set_semidense_propagate(self._h, C.byref(p)))
+
+    def setSemiDenseRegularize(self, params):
+        """A regularised copy of the map (include/vo_hip.h, "Semi-dense regularisation"): behind every launch that writes the map one
+        launch on the side stream removes the entries their neighbours contradict, fills high-gradient holes whose neighbours agree
+        and smooths the rest, into planes of its own (getSemiDenseMap(regularized=True), getSemiDensePoints(fused=True,
+        regularized=True)); the odometry's results, the semi-dense results and the map itself do not change. params:
+        dict(radius=, chi=, dist_sigma=, min_support=, fill_min=, g_min=) ({}: the defaults), None: off. Needs setSemiDenseTemporal.
+        Refused while a frame is in flight."""
+        if params is None:
+            self.ctx.check(self.lib.vo_svo_set_semidense_regularize(self._h, None))
+            return
+        p = _semidense_regularize_params(self.lib, params)
+        self.ctx.check(self.lib.vo_svo_set_semidense_regularize(self._h, C.byref(p)))
 
     def setSemiDenseAlignAffine(self, params):
         """A modifier of whichever alignment is on (include/vo_hip.h, "Semi-dense alignment with affine brightness"): its launches
@@ -1874,12 +1969,17 @@ class StereoVO:
         self.ctx.check(self.lib.vo_svo_get_semidense_origin(self._h, origin.ctypes.data, C.byref(w), C.byref(h), C.byref(fid)))
         return origin, fid.value
 
-    def getSemiDensePoints(self, world=True, capacity=None, fused=False, min_obs=2):
+    def getSemiDensePoints(self, world=True, capacity=None, fused=False, min_obs=2, regularized=False):
         """The accepted pixels of the last semi-dense result as points, raster order: dict(xyz float32 [n, 3] — in the world frame
         (the frame's T_wc) or, world=False, the left camera's —, sigma_invd [n], pixel uint16 [n, 2], frame_id); None before any.
         capacity: room for that many points (default: all); more raise VoError(VO_ERR_CAPACITY) whose `n` holds the true count.
-        fused=True (setSemiDenseTemporal): the last keyframe's map instead — its pixels with n_obs >= min_obs, z = 1 / invd."""
-        if fused:
+        fused=True (setSemiDenseTemporal): the last keyframe's map instead — its pixels with n_obs >= min_obs, z = 1 / invd; with
+        regularized=True (setSemiDenseRegularize) the regularised copy of that map (a filled pixel has n_obs 1)."""
+        if regularized:
+            if not fused:
+                raise ValueError("getSemiDensePoints: regularized=True is of the fused map: fused=True")
+            get = lambda *a: self.lib.vo_svo_get_semidense_regularized_points(self._h, int(bool(world)), int(min_obs), *a)
+        elif fused:
             get = lambda *a: self.lib.vo_svo_get_semidense_map_points(self._h, int(bool(world)), int(min_obs), *a)
         else:
             get = lambda *a: self.lib.vo_svo_get_semidense_points(self._h, int(bool(world)), *a)

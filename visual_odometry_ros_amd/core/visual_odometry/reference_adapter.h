@@ -512,6 +512,16 @@ class StereoVO {
     for (size_t i = 0; i < v.size(); ++i) o[i] = Point(v[i].x, v[i].y, v[i].z);
     return o;
   }
+  // a regularised copy of that map (vo::StereoVO::setSemiDenseRegularize): outliers removed, thin gaps filled, values smoothed over
+  // each pixel's neighbourhood; getSemiDenseRegularizedPoints() is that copy's pixels seen at least min_obs times (a filled one: once)
+  void setSemiDenseRegularize(const vo_semidense_regularize_params *prm) { impl_.setSemiDenseRegularize(prm); }
+  PointVec getSemiDenseRegularizedPoints(bool world = true, int min_obs = 1) {
+    vo::PointVec v;
+    impl_.getSemiDenseRegularizedPoints(v, nullptr, world, min_obs);
+    PointVec o(v.size());
+    for (size_t i = 0; i < v.size(); ++i) o[i] = Point(v[i].x, v[i].y, v[i].z);
+    return o;
+  }
   // NOT in the reference: CLAHE equalisation of every image before the tracker (vo::StereoVO::setEqualize; VO_EQ_CLAHE / VO_EQ_OFF)
   void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) { impl_.setEqualize(mode, clip_limit, tiles_x, tiles_y); }
   vo::StereoVO &device() { return impl_; }

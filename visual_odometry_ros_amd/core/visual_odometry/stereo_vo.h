@@ -306,6 +306,30 @@ class StereoVO {
     if (from_frame_id) *from_frame_id = from;
     return w > 0;
   }
+  // A regularised copy of the map (vo_svo_set_semidense_regularize; include/vo_hip.h, "Semi-dense regularisation"): behind every
+  // launch that writes the map one launch on the side stream removes the entries their neighbours contradict, fills high-gradient
+  // holes whose neighbours agree and smooths the rest, into planes of its own; the map itself keeps its bits. Needs
+  // setSemiDenseTemporal. prm = nullptr: off. Throws while a frame is in flight.
+  static vo_semidense_regularize_params defaultSemiDenseRegularizeParams() {
+    vo_semidense_regularize_params p;
+    vo_semidense_regularize_default_params(&p);
+    return p;
+  }
+  void setSemiDenseRegularize(const vo_semidense_regularize_params *prm) { ctx_->check(vo_svo_set_semidense_regularize(svo_, prm)); }
+  // the regularised map as points (the pixels with n_obs >= min_obs; a filled pixel has n_obs 1), as getSemiDenseMapPoints. false (and
+  // empty vectors) before the first frame since the option was switched on.
+  bool getSemiDenseRegularizedPoints(PointVec &xyz, std::vector<float> *sigma = nullptr, bool world = true, int min_obs = 1,
+                                     int *frame_id = nullptr) {
+    int n = 0, fid = -1;
+    const int rc = vo_svo_get_semidense_regularized_points(svo_, world ? 1 : 0, min_obs, 0, nullptr, nullptr, nullptr, &n, &fid);
+    if (rc != VO_ERR_CAPACITY) ctx_->check(rc);  // (room for none: the count is what was asked for)
+    xyz.resize((size_t)n);
+    if (sigma) sigma->resize((size_t)n);
+    if (frame_id) *frame_id = fid;
+    if (n) ctx_->check(vo_svo_get_semidense_regularized_points(svo_, world ? 1 : 0, min_obs, n, reinterpret_cast<float *>(xyz.data()),
+                                                               sigma ? sigma->data() : nullptr, nullptr, &n, &fid));
+    return fid >= 0;
+  }
   // Direct image alignment on the keyframe's map (vo_svo_set_semidense_align; include/vo_hip.h, "Semi-dense alignment"): every frame
   // that is not a keyframe aligns its left image against the map from the odometry's pose, on the side stream in front of the
   // frame's temporal launch; nothing uses the aligned pose. Needs setSemiDenseTemporal. prm = nullptr: off. Throws while a frame is

@@ -98,6 +98,7 @@ struct vo_semidense_state {
 void vo_semidense_free(vo_ctx *c) {
   vo_semidense_temporal_free(c);
   vo_semidense_propagate_free(c);
+  vo_semidense_regularize_free(c);
   vo_semidense_align_free(c);
   if (!c->semidense) return;
   vo_sd_buffers_free(&c->semidense->buf);

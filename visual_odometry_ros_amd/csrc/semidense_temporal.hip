@@ -234,8 +234,8 @@ extern "C" int vo_semidense_temporal(vo_ctx *c, const uint8_t *key_plane, int ke
 }
 
 // the pixels with n_obs >= min_obs of DEVICE planes as a list (host outputs); b: the compaction's scratch. Synchronous on c->stream.
-static int sdt_points(vo_ctx *c, vo_sd_buffers *b, const float *d_invd, const float *d_sigma, const uint8_t *d_n_obs, int W, int H, const float K[4],
-                      const float *T, int min_obs, int cap, float *xyz, float *sigma_out, uint16_t *pixel, int *n) {
+int vo_sdt_points(vo_ctx *c, vo_sd_buffers *b, const float *d_invd, const float *d_sigma, const uint8_t *d_n_obs, int W, int H, const float K[4],
+                  const float *T, int min_obs, int cap, float *xyz, float *sigma_out, uint16_t *pixel, int *n) {
   const size_t np = (size_t)W * (size_t)H;
   hipLaunchKernelGGL(semidense_map_key_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c->stream, d_n_obs, b->key, min_obs, (int)np);
   VO_CHECK_HIP(c, hipGetLastError());
@@ -265,7 +265,7 @@ extern "C" int vo_semidense_map_points(vo_ctx *c, const float *invd, const float
     d_sig = sigma ? b->sigma : nullptr;
     d_no = b->status;
   }
-  return sdt_points(c, b, d_invd, d_sig, d_no, width, height, K, T, min_obs, cap, xyz, sigma_out, pixel, n);
+  return vo_sdt_points(c, b, d_invd, d_sig, d_no, width, height, K, T, min_obs, cap, xyz, sigma_out, pixel, n);
 }
 
 // ---- StereoVO's hook ------------------------------------------------------------------------------------------------------------------
@@ -346,12 +346,17 @@ int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, in
     ++t.n_fused;
     d.busy |= 1u << slot_l;
   }
+  if (s->sdr.on) {  // vo_svo_set_semidense_regularize: behind the launch that wrote the map, on the planes that are current now
+    const int rc = vo_svo_semidense_regularize_enqueue(s);
+    if (rc) return rc;
+  }
   VO_CHECK_HIP(c, hipEventRecord(d.done, side));
   return VO_OK;
 }
 
 void vo_svo_semidense_temporal_free(vo_svo *s) {
   vo_svo_semidense_propagate_free(s);
+  vo_svo_semidense_regularize_free(s);
   vo_svo_semidense_align_free(s);
   vo_sdt_buffers_free(&s->sdt.buf);
   s->sdt = vo_svo_semidense_temporal();
@@ -366,6 +371,7 @@ extern "C" int vo_svo_set_semidense_temporal(vo_svo *s, const vo_semidense_tempo
   if (!prm) {
     t.on = false;
     t.have = false;
+    s->sdr.have = false;  // (vo_svo_set_semidense_regularize: its planes belong to a map that is gone)
     return VO_OK;
   }
   if (!s->sd.on) VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_temporal: needs the static option: vo_svo_set_semidense first");
@@ -421,6 +427,6 @@ extern "C" int vo_svo_get_semidense_map_points(vo_svo *s, int world, int min_obs
   *n = 0;
   if (frame_id) *frame_id = t.have ? t.frame_id : -1;
   if (!t.have) return VO_OK;
-  return sdt_points(s->c, &s->sd.buf, t.buf.invd, t.buf.sigma, t.buf.n_obs, t.w, t.h, s->prm.frame.Kl, world ? t.T_wk : nullptr, min_obs, cap, xyz,
-                    sigma, pixel, n);
+  return vo_sdt_points(s->c, &s->sd.buf, t.buf.invd, t.buf.sigma, t.buf.n_obs, t.w, t.h, s->prm.frame.Kl, world ? t.T_wk : nullptr, min_obs, cap, xyz,
+                       sigma, pixel, n);
 }

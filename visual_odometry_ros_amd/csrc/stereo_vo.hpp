@@ -54,6 +54,17 @@ struct vo_svo_semidense_propagate {
   float T_ba[16] = {};
 };
 
+// vo_svo_set_semidense_regularize (semidense_regularize.hip): behind every launch that writes the temporal option's map one launch
+// writes a regularised copy into `buf`; the map itself is never touched. have: `buf` holds the regularised map of the keyframe
+// frame_id after n_fused temporal launches.
+struct vo_svo_semidense_regularize {
+  bool on = false, have = false;
+  vo_semidense_regularize_params prm = {};
+  vo_sdr_buffers buf;
+  int w = 0, h = 0, frame_id = -1, n_fused = 0;
+  float T_wk[16] = {};
+};
+
 // vo_svo_set_semidense_align (semidense_align.hip): at every frame that is not a keyframe the frame's left image is aligned against
 // the keyframe's map, on the side stream in front of the frame's temporal launch. `have`: the last frame has a result in `buf`.
 struct vo_svo_semidense_align {
@@ -115,6 +126,7 @@ struct vo_svo {
   vo_svo_semidense_temporal sdt;  // vo_svo_set_semidense_temporal: the keyframe's map, fused with every later frame
   vo_svo_semidense_propagate sdp;  // vo_svo_set_semidense_propagate: that map carried over to the next keyframe
   vo_svo_semidense_align sda;  // vo_svo_set_semidense_align: every later frame's left image aligned against that map
+  vo_svo_semidense_regularize sdr;  // vo_svo_set_semidense_regularize: a regularised copy of that map behind every launch that writes it
   int mono = 0;  // the keyframe storage serves a MonoVO (mono_vo.hip): one observation per keyframe entry, bundled flags
   // all_stkeyframes_ (stats_keyframe): every keyframe's current pose (host) and where its related landmarks' ids are kept
   // on the device (a pool that only grows)
@@ -151,6 +163,9 @@ void vo_svo_semidense_temporal_free(vo_svo *s);
 int vo_svo_semidense_propagate_scatter(vo_svo *s, int slot_l, const float T_wc[16]);
 int vo_svo_semidense_propagate_resolve(vo_svo *s, bool chain);
 void vo_svo_semidense_propagate_free(vo_svo *s);
+// semidense_regularize.hip: one launch on the side stream behind the launch that wrote the map (seed, resolve or temporal)
+int vo_svo_semidense_regularize_enqueue(vo_svo *s);
+void vo_svo_semidense_regularize_free(vo_svo *s);
 // semidense_align.hip: on the side stream (c->stream points at it) in front of a non-keyframe frame's temporal launch
 int vo_svo_semidense_align_enqueue(vo_svo *s, int slot_l, int frame_id, const float T_ck[16]);
 // (vo_svo_set_semidense_align_pyr) at a keyframe, behind the key plane's copy: the slot's coarser levels next to it

@@ -131,6 +131,7 @@ struct vo_ctx {
   struct vo_semidense_state *semidense;  // vo_semidense_stereo / vo_semidense_points: their planes and scratch (semidense.hip), made on first use
   struct vo_semidense_propagate_state *semidense_p;  // vo_semidense_map_propagate: its keys and, for host planes, the new map's device copies
   struct vo_semidense_align_state *semidense_a;  // vo_semidense_align: its state block and partial sums
+  struct vo_semidense_regularize_state *semidense_r;  // vo_semidense_map_regularize with host planes: the mask's and the outputs' device copies
 };
 
 static inline hipError_t vo_dev_malloc(vo_ctx *c, void **p, size_t bytes) {
@@ -287,6 +288,9 @@ int vo_sdt_ctx_buffers(vo_ctx *c, vo_sdt_buffers **b);  // the context's own buf
 int vo_sdt_enqueue(vo_ctx *c, const uint8_t *d_key, int key_stride, const vo_mask_view *key_mask, int slot_cur, const float K[4],
                    const float T_ck[16], const vo_semidense_temporal_params *p, float *invd, float *sigma, uint8_t *n_obs, uint8_t *tstatus,
                    float *score);
+// the pixels with n_obs >= min_obs of DEVICE planes as a list (host outputs); b: the compaction's scratch. Synchronous on c->stream.
+int vo_sdt_points(vo_ctx *c, vo_sd_buffers *b, const float *d_invd, const float *d_sigma, const uint8_t *d_n_obs, int W, int H, const float K[4],
+                  const float *T, int min_obs, int cap, float *xyz, float *sigma_out, uint16_t *pixel, int *n);
 
 // The semi-dense propagation (semidense_propagate.hip; include/vo_hip.h, "Semi-dense propagation"): the plane of keys (all 0 between
 // calls: zeroed at allocation, every resolve launch stores 0 back), a set of map planes, origin and — the context's operator — src:
@@ -302,6 +306,19 @@ struct vo_sdp_buffers {
 int vo_sdp_buffers_alloc(vo_ctx *c, vo_sdp_buffers *b, bool driver);
 void vo_sdp_buffers_free(vo_sdp_buffers *b);
 void vo_semidense_propagate_free(vo_ctx *c);
+
+// The semi-dense regularisation (semidense_regularize.hip; include/vo_hip.h, "Semi-dense regularisation"): the four planes of a
+// regularised map and — the context's operator — a copy of the caller's mask: one allocation sized by vo_config.max_width x
+// max_height.
+struct vo_sdr_buffers {
+  void *base = nullptr;
+  float *invd = nullptr, *sigma = nullptr;
+  uint8_t *n_obs = nullptr, *rstatus = nullptr, *mask = nullptr;
+  size_t npix = 0;
+};
+int vo_sdr_buffers_alloc(vo_ctx *c, vo_sdr_buffers *b, bool driver);
+void vo_sdr_buffers_free(vo_sdr_buffers *b);
+void vo_semidense_regularize_free(vo_ctx *c);
 
 // The semi-dense alignment (semidense_align.hip; include/vo_hip.h, "Semi-dense alignment"): the small state block (pose, status, the
 // "done" word and the ticket, zero between launches; the last evaluated system) and a row of 30 integer sums per block of 1024
