@@ -19,7 +19,10 @@ update (the temporal search and fusion); `semidense_fused_<keyframe's frame id>.
 2) observations (N = 1 keeps what the static result alone gave), written when the next keyframe replaces the map and at the end
 of the run. --semidense-propagate: with --semidense-temporal, a keyframe's map is carried over to the next keyframe (warped under
 the odometry's pose, fused with the new static result) instead of being seeded afresh, so a keyframe's file also holds what earlier
-keyframes observed. --semidense-regularize: with --semidense-temporal, a regularised copy of the map is kept next to it (entries their
+keyframes observed. --semidense-world FILE.ply: with --semidense-temporal, every keyframe's map is fused into one world-frame voxel
+map when the next keyframe replaces it (the last one at the end); FILE.ply has x y z grey count keyframes per voxel
+(--semidense-voxel V: the voxel's edge, default 0.1 m; --semidense-world-min-keyframes N: only voxels N keyframes reached).
+--semidense-regularize: with --semidense-temporal, a regularised copy of the map is kept next to it (entries their
 neighbours contradict removed, high-gradient holes whose neighbours agree filled, values smoothed) and written as
 `semidense_regularized_<keyframe's frame id>.ply` wherever the fused file is written; its filled pixels have one observation, so N
 applies to the measured ones only. --semidense-align FILE: with --semidense-temporal, every frame that is not a keyframe aligns its left image
@@ -100,7 +103,17 @@ def semidense_options(args):
             raise SystemExit("--semidense-temporal / --semidense-min-obs / --semidense-propagate / --semidense-align need --semidense DIR")
         if args.semidense_regularize:
             raise SystemExit("--semidense-regularize needs --semidense DIR")
+        if args.semidense_world or args.semidense_voxel is not None or args.semidense_world_min_keyframes is not None:
+            raise SystemExit("--semidense-world / --semidense-voxel / --semidense-world-min-keyframes need --semidense DIR")
         return {}
+    if args.semidense_world and not args.semidense_temporal:
+        raise SystemExit("--semidense-world needs --semidense-temporal")
+    if (args.semidense_voxel is not None or args.semidense_world_min_keyframes is not None) and not args.semidense_world:
+        raise SystemExit("--semidense-voxel / --semidense-world-min-keyframes need --semidense-world FILE.ply")
+    if args.semidense_voxel is not None and not args.semidense_voxel > 0:
+        raise SystemExit("--semidense-voxel V: metres, > 0")
+    if args.semidense_world_min_keyframes is not None and args.semidense_world_min_keyframes < 1:
+        raise SystemExit("--semidense-world-min-keyframes N: >= 1")
     if args.semidense_regularize and not args.semidense_temporal:
         raise SystemExit("--semidense-regularize needs --semidense-temporal")
     if args.semidense_propagate and not args.semidense_temporal:
@@ -127,6 +140,8 @@ def semidense_options(args):
         sd["propagate"] = True
     if args.semidense_regularize:
         sd["regularize"] = True
+    if args.semidense_world:
+        sd["world"] = True if args.semidense_voxel is None else {"voxel": args.semidense_voxel}
     if args.semidense_align:
         sd["align"] = True
         if args.semidense_align_levels is not None or args.semidense_align_start is not None:
@@ -156,6 +171,15 @@ def write_ply(path, xyz, sigma_invd):
                 "property float x\nproperty float y\nproperty float z\nproperty float sigma_invd\nend_header\n")
         for (x, y, z), s in zip(xyz, sigma_invd):
             f.write(f"{x:.6g} {y:.6g} {z:.6g} {s:.6g}\n")
+
+
+def write_world_ply(path, w):
+    """one ASCII PLY of a world map (a SemiDenseWorldPoints): x y z, grey, the points and the keyframes per voxel"""
+    with open(path, "w") as f:
+        f.write("ply\nformat ascii 1.0\n" + f"element vertex {len(w.xyz)}\n" + "property float x\nproperty float y\nproperty float z\n"
+                "property uchar grey\nproperty uint count\nproperty uint keyframes\nend_header\n")
+        for (x, y, z), g, c, k in zip(w.xyz, w.grey, w.count, w.keyframes):
+            f.write(f"{x:.6g} {y:.6g} {z:.6g} {int(g)} {int(c)} {int(k)}\n")
 
 
 def parse_args(argv=None):
@@ -194,6 +218,11 @@ def parse_args(argv=None):
                     help="--semidense-temporal: carry a keyframe's fused map over to the next keyframe instead of seeding it afresh")
     ap.add_argument("--semidense-regularize", action="store_true",
                     help="--semidense-temporal: also keep a regularised copy of the map; semidense_regularized_<id>.ply per keyframe")
+    ap.add_argument("--semidense-world", default=None, metavar="FILE.ply",
+                    help="--semidense-temporal: fuse every keyframe's map into one world-frame voxel map; one ASCII PLY at the end")
+    ap.add_argument("--semidense-voxel", type=float, default=None, metavar="V", help="voxel edge of --semidense-world in metres (default 0.1)")
+    ap.add_argument("--semidense-world-min-keyframes", type=int, default=None, metavar="N",
+                    help="--semidense-world: write the voxels at least N keyframes have reached (default 1)")
     ap.add_argument("--semidense-align", default=None, metavar="FILE",
                     help="--semidense-temporal: align every later frame's left image against the keyframe's map; one line per frame into FILE")
     ap.add_argument("--semidense-align-levels", type=int, default=None, metavar="N",
@@ -272,6 +301,13 @@ def main():
     dt = time.perf_counter() - t0
     if args.semidense and args.semidense_temporal:
         write_fused()
+    if args.semidense_world:
+        svo.flushSemiDenseWorld()  # (the last keyframe's map: no later keyframe replaces it)
+        wm = svo.getSemiDenseWorld(min_keyframes=args.semidense_world_min_keyframes or 1)
+        write_world_ply(args.semidense_world, wm)
+        st = svo.getSemiDenseWorldStats()
+        print(f"world map: {len(wm.xyz)} voxels written of {st['occupied']} ({st['integrations']} keyframes integrated, {st['refused']} refused, "
+              f"{st['inserted']} points) -> {args.semidense_world}")
     V.write_trajectory(args.trajectory, ids, np.stack(poses))
     if args.keyframes:
         kfs = svo.getKeyframes()

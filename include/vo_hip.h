@@ -439,10 +439,13 @@ int vo_stereo_frame_recoveries(const vo_ctx *ctx);
  *                         results, bit for bit (tests compare the two; the A/B lever of the measurement); >= 2: the fused launch
  *                         with at most that many workgroups (tests: every workgroup strides over several landmark groups)
  *   VO_DBG_SDP_STAGE      vo_semidense_map_propagate launches 1: its scatter only (the plane of keys stays as the launch leaves
- *                         it), 2: its resolve only (on the keys an earlier call left) — what each launch costs (measurement) */
+ *                         it), 2: its resolve only (on the keys an earlier call left) — what each launch costs (measurement)
+ *   VO_DBG_SDW_FORM       1: the world map's integrations of this context run the simple kernel form (every point probes the global
+ *                         table itself) instead of the pre-aggregated one — the same table contents, bit for bit (tests compare the
+ *                         two; the A/B lever of the measurement) */
 enum { VO_DBG_FAIL_JOIN = 0, VO_DBG_CONC_GRID = 1, VO_DBG_SBA_LDS_SOLVE = 2, VO_DBG_SKIP_DETECT = 3, VO_OPT_POLL_YIELD = 4,
        VO_DBG_MVO_HOST_ADVANCE = 5, VO_DBG_STAGED_DETECT = 6, VO_DBG_CANDS_IN_FRAME = 7, VO_DBG_SBA_SPLIT = 8,
-       VO_DBG_SDP_STAGE = 9, VO_DBG_COUNT = 10 };
+       VO_DBG_SDP_STAGE = 9, VO_DBG_SDW_FORM = 10, VO_DBG_COUNT = 11 };
 int vo_debug_set(vo_ctx *ctx, int key, int value);
 /* Device and pinned-host allocations made on behalf of this context so far (vo_create included). A steady-state frame —
  * keyframes and their local BA included — makes none: tests/test_stereo_vo_gpu.py asserts it. */
@@ -1263,6 +1266,94 @@ int vo_svo_get_semidense_regularized(vo_svo *svo, float *invd, float *sigma, uin
                                      int *frame_id, float T_wc[16], int *n_fused);
 int vo_svo_get_semidense_regularized_points(vo_svo *svo, int world, int min_obs, int cap, float *xyz, float *sigma, uint16_t *pixel, int *n,
                                             int *frame_id);
+
+/* ---- Semi-dense world map: the keyframes' semi-dense maps fused into one sparse voxel table in the world frame ----
+ * Every block above ends at one keyframe's map. This one adds the map of a sequence: a sparse set of voxels of edge `voxel` [m] in the
+ * world frame, held in an open-addressing hash table of 2^capacity_log2 slots of 64 bytes on the device, into which a keyframe's map
+ * is integrated once, when the next keyframe replaces it. A voxel keeps a weighted mean position and grey value, the number of points
+ * and the number of integrations (keyframes) that reached it; "seen by k keyframes" is the filter a single cloud cannot give.
+ * Opt-in; the blocks above keep their bits. float32 with every operation rounded on its own (no FMA), in the order written here, up
+ * to the voxel index; every accumulator is an integer, so the order in which points arrive changes no bit of any voxel.
+ * tests/semidense_world_restatement.py restates it.
+ *   inputs     of one integration: a map, three W x H planes invd f32, sigma f32, n_obs u8 (the entry test is the regularisation
+ *              block's); optionally the keyframe's left level-0 u8 plane Lk (key_stride bytes per row); K = fx, fy, cx, cy; T_wk
+ *              row-major 4 x 4; seq, 1 for the first integration into a table (or since its last clear) and one more per call, refused
+ *              calls included.
+ *   params     voxel > 0 [m]; capacity_log2 10..28; min_obs 1..255; z_max > 0 [m]; all finite (VO_ERR_INVALID otherwise).
+ *   point      an entry at (x, y): z = 1.0f / invd. It is SKIPPED (and counted so) where n_obs < min_obs or z > z_max. Else
+ *              X = (((float)x - cx) / fx * z, ((float)y - cy) / fy * z, z) and X'[r] = (T[r][0] X + (T[r][1] Y + T[r][2] Z)) + T[r][3]
+ *              as vo_semidense_map_points forms them.
+ *   voxel      per axis a: u = X'[a] / voxel, i = floorf(u). Unless -2^20 <= i < 2^20 on all three axes — tested on the float, so
+ *              that NaN and inf fail — the point is dropped and counted as OUT OF RANGE. q = min((int)((u - i) * 1024.0f), 1023):
+ *              u - i is exact except for a negative u so close to an integer that it rounds to 1.0f, which the clamp takes.
+ *              key (64 bits) = 2^63 | (i_x + 2^20) << 42 | (i_y + 2^20) << 21 | (i_z + 2^20); 0 means "empty".
+ *   weight     sz = (sigma * z) * z (the depth's standard deviation), r = voxel / sz, w = r * r,
+ *              wq = w >= 65535.0f ? 65536 : (uint32)w + 1.
+ *   sums       per voxel, all integers: sw += wq, sx / sy / sz += wq * q_a, sg += wq * Lk(x, y) (64 bits; sg stays 0 without a
+ *              plane), cnt += 1 (32 bits); kf_cnt with last_seq: old = atomicMax(&last_seq, seq), the one point that sees old < seq
+ *              adds 1 to kf_cnt. Points inserted are counted.
+ *   slot       home = (key * 0x9E3779B97F4A7C15 mod 2^64) >> (64 - capacity_log2), then linear probing; an empty slot is claimed with
+ *              a 64-bit compare-and-swap on its key word. Which slot a voxel sits in is the one thing that depends on arrival order.
+ *   refusal    all or nothing: an integration is refused as a whole where occupied + W H > 2^capacity_log2 / 2, with `occupied` the
+ *              count the previous accepted integration published — decided on the device, the same in every workgroup, no host turn.
+ *              A refused integration leaves every slot and every count but `refused` (+ 1) untouched; it still takes its seq. An
+ *              accepted one therefore always finds a free slot within half a table; `integrations` counts the accepted ones.
+ *   extraction the voxels with cnt >= min_count and kf_cnt >= min_keyframes (both >= 1) in ASCENDING KEY order (compacted on the
+ *              device in arrival order, sorted on the host: the getter is not on a hot path, and may allocate device scratch the first
+ *              time it needs more records than before). Per record: index i32[3]; xyz f32[3], per axis
+ *              (float)(((double)i + ((double)s_a / (double)sw + 0.5) * (1.0 / 1024)) * (double)voxel), each operation rounded on its
+ *              own; weight u32 = min(sw, 2^32 - 1); count = cnt; keyframes = kf_cnt; grey u8 = (sg + sw / 2) / sw (integer division);
+ *              sums u64[5] = sw, sx, sy, sz, sg (the operator only). Every output may be NULL. *n = the true count, also with
+ *              VO_ERR_CAPACITY (n > cap: the first cap records in key order are written).
+ * vo_semidense_world_create makes the handle's one allocation (64 bytes x 2^capacity_log2: 268 MB at the default 22) on the
+ * context's device; destroy it before the context. vo_semidense_world_integrate: one launch, synchronous; the map is host planes, or
+ * device planes with on_device; key_plane may be NULL, a host plane, or a device plane with key_on_device. The planes may not exceed
+ * vo_config.max_width x max_height (VO_ERR_SIZE). vo_semidense_world_clear empties the table and zeroes every count and seq.
+ *
+ * StereoVO: vo_svo_set_semidense_world(svo, prm, source) — prm NULL = off — needs vo_svo_set_semidense_temporal on and, for
+ * source = VO_SEMIDENSE_WORLD_REGULARIZED, vo_svo_set_semidense_regularize; VO_ERR_INVALID otherwise, while a frame is in flight or
+ * on a mono driver. Its only allocation (the table) happens at the first enable; capacity_log2 is fixed from then on, and a later
+ * enable with another voxel, min_obs or z_max clears the table. With it off no launch, allocation, wait or result bit differs; with
+ * it on the odometry's results, the static result, the map, the alignment and the regularised planes are the same bits. At a keyframe
+ * change vo_svo_result enqueues ONE launch on the side stream that integrates the OUTGOING keyframe's map (raw, or its regularised
+ * copy; with the regularised source a keyframe without such a copy is not integrated) with that keyframe's T_wc, K of the left camera
+ * and key plane — in front of the propagation's scatter, the key plane's copy and the seed, which overwrite them; nothing waits for
+ * it. vo_svo_semidense_world_flush integrates the CURRENT keyframe's map now (the end of a sequence) and marks it, so that the next
+ * keyframe change does not integrate it again. vo_svo_get_semidense_world_points / _stats wait for the side stream's last launch
+ * only; vo_svo_semidense_world_clear empties the table. All: VO_ERR_INVALID while a frame is in flight or with the option off.
+ *
+ * Out of scope: re-anchoring voxels after the local BA moves a keyframe (a keyframe is integrated with the pose it had when it was
+ * replaced); free-space carving and the removal of moving objects; a TSDF, surfaces or meshes; growing or rehashing the table; a
+ * tighter refusal bound than W H; streaming the map out in tiles; MonoVO and vo_batch streams; any use of the map in the odometry.
+ * With vo_svo_set_semidense_propagate on a propagated pixel re-enters every keyframe that carries it, so kf_cnt counts carried
+ * surfaces too: min_keyframes then asks for less than independent confirmation. */
+typedef struct {
+  float voxel;        /* 0.10 [m] */
+  int capacity_log2;  /* 22 */
+  int min_obs;        /* 2 */
+  float z_max;        /* 40 [m] */
+} vo_semidense_world_params;
+typedef struct {
+  unsigned long long occupied, capacity, integrations, refused, inserted, skipped, out_of_range;
+} vo_semidense_world_info;
+enum { VO_SEMIDENSE_WORLD_RAW = 0, VO_SEMIDENSE_WORLD_REGULARIZED = 1 };
+typedef struct vo_semidense_world vo_semidense_world;
+int vo_semidense_world_default_params(vo_semidense_world_params *prm);
+int vo_semidense_world_create(vo_ctx *ctx, const vo_semidense_world_params *prm, vo_semidense_world **wm);
+void vo_semidense_world_destroy(vo_semidense_world *wm);
+int vo_semidense_world_clear(vo_semidense_world *wm);
+int vo_semidense_world_integrate(vo_semidense_world *wm, const float *invd, const float *sigma, const uint8_t *n_obs,
+                                 const uint8_t *key_plane, int key_stride, int key_on_device, int width, int height, int on_device,
+                                 const float K[4], const float T_wk[16]);
+int vo_semidense_world_stats(vo_semidense_world *wm, vo_semidense_world_info *info);
+int vo_semidense_world_points(vo_semidense_world *wm, int min_count, int min_keyframes, int cap, int32_t *index, float *xyz,
+                              uint32_t *weight, uint32_t *count, uint32_t *keyframes, uint8_t *grey, uint64_t *sums, int *n);
+int vo_svo_set_semidense_world(vo_svo *svo, const vo_semidense_world_params *prm, int source);
+int vo_svo_semidense_world_flush(vo_svo *svo);
+int vo_svo_semidense_world_clear(vo_svo *svo);
+int vo_svo_get_semidense_world_stats(vo_svo *svo, vo_semidense_world_info *info);
+int vo_svo_get_semidense_world_points(vo_svo *svo, int min_count, int min_keyframes, int cap, int32_t *index, float *xyz,
+                                      uint32_t *weight, uint32_t *count, uint32_t *keyframes, uint8_t *grey, int *n);
 
 /* ---- undistortion / stereo rectification in front of the trackers ----------
  * core/visual_odometry/camera.cpp. A context holds the maps of two cameras

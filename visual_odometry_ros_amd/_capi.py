@@ -123,6 +123,14 @@ class SemiDenseRegularizeParams(C.Structure):  # vo_semidense_regularize_params
                 ("g_min", C.c_int)]
 
 
+class SemiDenseWorldParams(C.Structure):  # vo_semidense_world_params
+    _fields_ = [("voxel", C.c_float), ("capacity_log2", C.c_int), ("min_obs", C.c_int), ("z_max", C.c_float)]
+
+
+class SemiDenseWorldInfo(C.Structure):  # vo_semidense_world_info
+    _fields_ = [(k, C.c_ulonglong) for k in ("occupied", "capacity", "integrations", "refused", "inserted", "skipped", "out_of_range")]
+
+
 class SemiDenseAlignParams(C.Structure):  # vo_semidense_align_params
     _fields_ = [("min_obs", C.c_int), ("huber", C.c_float), ("max_iters", C.c_int), ("eps", C.c_float), ("min_pixels", C.c_int)]
 
@@ -210,6 +218,9 @@ SYMBOLS = [
     "vo_svo_get_semidense_align_affine",
     "vo_semidense_regularize_default_params", "vo_semidense_map_regularize", "vo_svo_set_semidense_regularize",
     "vo_svo_get_semidense_regularized", "vo_svo_get_semidense_regularized_points",
+    "vo_semidense_world_default_params", "vo_semidense_world_create", "vo_semidense_world_destroy", "vo_semidense_world_clear",
+    "vo_semidense_world_integrate", "vo_semidense_world_stats", "vo_semidense_world_points", "vo_svo_set_semidense_world",
+    "vo_svo_semidense_world_flush", "vo_svo_semidense_world_clear", "vo_svo_get_semidense_world_stats", "vo_svo_get_semidense_world_points",
 ]
 
 _lib = None
@@ -346,6 +357,19 @@ def load():
     lib.vo_svo_set_semidense_regularize.argtypes = [vp, vp]
     lib.vo_svo_get_semidense_regularized.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.vo_svo_get_semidense_regularized_points.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp]
+    lib.vo_semidense_world_default_params.argtypes = [vp]
+    lib.vo_semidense_world_create.argtypes = [vp, vp, vp]
+    lib.vo_semidense_world_destroy.argtypes = [vp]
+    lib.vo_semidense_world_destroy.restype = None
+    lib.vo_semidense_world_clear.argtypes = [vp]
+    lib.vo_semidense_world_integrate.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp]
+    lib.vo_semidense_world_stats.argtypes = [vp, vp]
+    lib.vo_semidense_world_points.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.vo_svo_set_semidense_world.argtypes = [vp, vp, ci]
+    lib.vo_svo_semidense_world_flush.argtypes = [vp]
+    lib.vo_svo_semidense_world_clear.argtypes = [vp]
+    lib.vo_svo_get_semidense_world_stats.argtypes = [vp, vp]
+    lib.vo_svo_get_semidense_world_points.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
     lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_five_point_destroy.argtypes = [vp]
     lib.vo_five_point_destroy.restype = None

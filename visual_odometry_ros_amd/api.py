@@ -176,6 +176,117 @@ def _semidense_regularize_params(lib, params):
     return p
 
 
+SEMIDENSE_WORLD_SOURCE = {"raw": 0, "regularized": 1}
+
+
+class SemiDenseWorldPoints(collections.namedtuple("SemiDenseWorldPoints", "index xyz weight count keyframes grey sums", defaults=(None,))):
+    """The voxels of a world map in ascending key order (include/vo_hip.h, "Semi-dense world map"): index int32 [n, 3], xyz float32
+    [n, 3] (the weighted mean position [m]), weight uint32 [n], count uint32 [n] (points), keyframes uint32 [n] (integrations that
+    reached the voxel), grey uint8 [n]; from the operator also sums uint64 [n, 5] = sw, sx, sy, sz, sg."""
+    __slots__ = ()
+
+
+def _semidense_world_params(lib, params):
+    """keyword parameters -> vo_semidense_world_params: the C defaults, then the caller's fields"""
+    p = _capi.SemiDenseWorldParams()
+    lib.vo_semidense_world_default_params(C.byref(p))
+    known = {f[0] for f in _capi.SemiDenseWorldParams._fields_}
+    for k, v in dict(params).items():
+        if k not in known:
+            raise ValueError(f"semi-dense world map: unknown parameter {k!r}; known: {sorted(known)}")
+        setattr(p, k, v)
+    return p
+
+
+def _semidense_world_points(check, get, capacity, with_sums):
+    """the two-call pattern of the getters: the count, then the records"""
+    n = C.c_int()
+    if capacity is None:
+        rc = get(0, None, None, None, None, None, None, *((None,) if with_sums else ()), C.byref(n))
+        if rc < 0 and rc != -8:  # (VO_ERR_CAPACITY: the count is what was asked for)
+            check(rc)
+        capacity = n.value
+    cap = int(capacity)
+    m = max(cap, 1)
+    idx, xyz = np.zeros((m, 3), np.int32), np.zeros((m, 3), np.float32)
+    wt, cnt, kf, grey = np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m, np.uint8)
+    sums = np.zeros((m, 5), np.uint64)
+    rc = get(cap, idx.ctypes.data, xyz.ctypes.data, wt.ctypes.data, cnt.ctypes.data, kf.ctypes.data, grey.ctypes.data,
+             *((sums.ctypes.data,) if with_sums else ()), C.byref(n))
+    try:
+        check(rc)
+    except VoError as e:
+        e.n = n.value
+        raise
+    k = min(n.value, cap)
+    return SemiDenseWorldPoints(idx[:k], xyz[:k], wt[:k], cnt[:k], kf[:k], grey[:k], sums[:k] if with_sums else None)
+
+
+class SemiDenseWorld:
+    """A world-frame voxel map (include/vo_hip.h, "Semi-dense world map"; Context.semiDenseWorld makes one): a hash table of
+    2^capacity_log2 slots on the context's device into which semi-dense maps are integrated with their keyframes' poses."""
+
+    def __init__(self, ctx, **params):
+        self.ctx, self.lib = ctx, ctx.lib
+        self.params = _semidense_world_params(self.lib, params)
+        self._h = C.c_void_p()
+        ctx.check(self.lib.vo_semidense_world_create(ctx.handle, C.byref(self.params), C.byref(self._h)))
+        ctx._children.add(self)
+
+    def integrate(self, map, K, T_wk, key=None, on_device=None, key_on_device=None):
+        """One integration: map a SemiDenseMap / SemiDenseRegularized / dict(invd=, sigma=, n_obs=) of arrays, K = fx, fy, cx, cy,
+        T_wk (4, 4), key the keyframe's left u8 plane or None. With on_device=(width, height) the map's planes are DEVICE addresses;
+        with key_on_device=stride so is key. Whether it was refused shows in stats()."""
+        get = (lambda k: getattr(map, k)) if isinstance(map, tuple) else (lambda k: map[k])
+        Ka, Ta = np.ascontiguousarray(K, np.float32).reshape(4), np.ascontiguousarray(T_wk, np.float32).reshape(4, 4)
+        if on_device is not None:
+            w, h = on_device
+            planes = [C.c_void_p(get(k)) for k in ("invd", "sigma", "n_obs")]
+        else:
+            invd, sigma = np.ascontiguousarray(get("invd"), np.float32), np.ascontiguousarray(get("sigma"), np.float32)
+            n_obs = np.ascontiguousarray(get("n_obs"), np.uint8)
+            if invd.ndim != 2 or sigma.shape != invd.shape or n_obs.shape != invd.shape:
+                raise ValueError("invd, sigma and n_obs are planes of one (height, width)")
+            h, w = invd.shape
+            planes = [invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data]
+        if key is None:
+            pk, stride = None, 0
+        elif key_on_device is not None:
+            pk, stride = C.c_void_p(key), int(key_on_device)
+        else:
+            ka = _u8(key)
+            if ka.shape != (h, w):
+                raise ValueError("key is a plane of the map's (height, width)")
+            pk, stride = ka.ctypes.data, ka.strides[0]
+        self.ctx.check(self.lib.vo_semidense_world_integrate(self._h, *planes, pk, stride, int(key_on_device is not None), int(w), int(h),
+                                                             int(on_device is not None), Ka.ctypes.data, Ta.ctypes.data))
+
+    def points(self, min_count=1, min_keyframes=1, capacity=None):
+        """The voxels with count >= min_count and keyframes >= min_keyframes: a SemiDenseWorldPoints in ascending key order."""
+        get = lambda *a: self.lib.vo_semidense_world_points(self._h, int(min_count), int(min_keyframes), *a)
+        return _semidense_world_points(self.ctx.check, get, capacity, True)
+
+    def stats(self):
+        """dict(occupied, capacity, integrations, refused, inserted, skipped, out_of_range)"""
+        info = _capi.SemiDenseWorldInfo()
+        self.ctx.check(self.lib.vo_semidense_world_stats(self._h, C.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in _capi.SemiDenseWorldInfo._fields_}
+
+    def clear(self):
+        self.ctx.check(self.lib.vo_semidense_world_clear(self._h))
+
+    def close(self):
+        if self._h:
+            self.lib.vo_semidense_world_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
 SEMIDENSE_ALIGN_STATUS = {0: "converged", 1: "max_iters reached", 2: "too few pixels", 3: "singular system", 4: "no result"}
 
 
@@ -705,6 +816,12 @@ class Context:
             None if ma is None else ma.ctypes.data, w, h, C.byref(p), o_invd.ctypes.data, o_sigma.ctypes.data, o_no.ctypes.data,
             o_rs.ctypes.data, 0))
         return SemiDenseRegularized(o_invd, o_sigma, o_no, o_rs)
+
+    def semiDenseWorld(self, **params):
+        """A world-frame voxel map on this context (include/vo_hip.h, "Semi-dense world map"): a SemiDenseWorld with integrate(map,
+        K, T_wk, key=None), points(min_count=1, min_keyframes=1), stats(), clear() and close(). params: voxel=0.1 [m],
+        capacity_log2=22 (64-byte slots), min_obs=2, z_max=40 [m]."""
+        return SemiDenseWorld(self, **params)
 
     def semiDenseMapPoints(self, invd, sigma=None, n_obs=None, K=None, T=None, min_obs=1, capacity=None, on_device=None):
         """The map's pixels with n_obs >= min_obs in raster order: (xyz float32 [n, 3], sigma float32 [n], pixel uint16 [n, 2]) with
@@ -1640,6 +1757,7 @@ class StereoVO:
         its "temporal": True or dict(z_max=..., max_search=...) also switches setSemiDenseTemporal on, and with it
         "propagate": True or dict(min_obs=, max_diff=, chi=, sigma_add=) setSemiDensePropagate,
         "regularize": True or dict(radius=, chi=, dist_sigma=, min_support=, fill_min=, g_min=) setSemiDenseRegularize,
+        "world": True or dict(voxel=, capacity_log2=, min_obs=, z_max=, source="raw" | "regularized") setSemiDenseWorld,
         "align": True or dict(min_obs=, huber=, max_iters=, eps=, min_pixels=) setSemiDenseAlign; with levels=, max_iters_level= or
         start="odometry" | "previous" in it, coarse to fine on a map pyramid (setSemiDenseAlignPyramid); with affine=True or
         affine=dict(gain0=, offset0=) in it, gain and offset are estimated next to the pose (setSemiDenseAlignAffine).
@@ -1675,7 +1793,9 @@ class StereoVO:
         if semidense is not None:
             sd = dict(semidense)
             temporal, propagate, align = sd.pop("temporal", None), sd.pop("propagate", None), sd.pop("align", None)
-            regularize = sd.pop("regularize", None)
+            regularize, world = sd.pop("regularize", None), sd.pop("world", None)
+            if world and not temporal:
+                raise ValueError('semidense: "world" needs "temporal"')
             if propagate and not temporal:
                 raise ValueError('semidense: "propagate" needs "temporal"')
             if regularize and not temporal:
@@ -1691,6 +1811,8 @@ class StereoVO:
                 self.setSemiDenseAlign({} if align is True else align)
             if regularize:
                 self.setSemiDenseRegularize({} if regularize is True else regularize)
+            if world:
+                self.setSemiDenseWorld({} if world is True else world)
         self._info = SvoFrameInfo()
         self.stats_frame = []  # AlgorithmStatistics::FrameStatistics::Twc per frame (stereo_vo.cpp:979-980)
 
@@ -1889,6 +2011,44 @@ class StereoVO:
             return
         p = _semidense_regularize_params(self.lib, params)
         self.ctx.check(self.lib.vo_svo_set_semidense_regularize(self._h, C.byref(p)))
+
+    def setSemiDenseWorld(self, params, source=None):
+        """The keyframes' maps fused into one world-frame voxel map (include/vo_hip.h, "Semi-dense world map"): when a keyframe is
+        replaced, one launch on the side stream integrates its map, with its T_wc and key plane, into a hash table of voxels;
+        flushSemiDenseWorld() integrates the current keyframe's at the end of a sequence, getSemiDenseWorld() reads the voxels. The
+        odometry's results, the semi-dense results and the map do not change. params: dict(voxel=, capacity_log2=, min_obs=, z_max=,
+        source="raw" | "regularized") ({}: the defaults), None: off. Needs setSemiDenseTemporal; source="regularized" also
+        setSemiDenseRegularize. Refused while a frame is in flight."""
+        if params is None:
+            self.ctx.check(self.lib.vo_svo_set_semidense_world(self._h, None, 0))
+            return
+        params = dict(params)
+        src = params.pop("source", "raw")
+        if source is not None:
+            src = source
+        if src not in SEMIDENSE_WORLD_SOURCE:
+            raise ValueError(f"setSemiDenseWorld: source {src!r}; known: {sorted(SEMIDENSE_WORLD_SOURCE)}")
+        p = _semidense_world_params(self.lib, params)
+        self.ctx.check(self.lib.vo_svo_set_semidense_world(self._h, C.byref(p), SEMIDENSE_WORLD_SOURCE[src]))
+
+    def flushSemiDenseWorld(self):
+        """Integrates the current keyframe's map now (the end of a sequence); the next keyframe change does not integrate it again."""
+        self.ctx.check(self.lib.vo_svo_semidense_world_flush(self._h))
+
+    def clearSemiDenseWorld(self):
+        self.ctx.check(self.lib.vo_svo_semidense_world_clear(self._h))
+
+    def getSemiDenseWorld(self, min_count=1, min_keyframes=1, capacity=None):
+        """The world map's voxels with count >= min_count and keyframes >= min_keyframes: a SemiDenseWorldPoints in ascending key
+        order. Waits for the side stream's last launch only."""
+        get = lambda *a: self.lib.vo_svo_get_semidense_world_points(self._h, int(min_count), int(min_keyframes), *a)
+        return _semidense_world_points(self.ctx.check, get, capacity, False)
+
+    def getSemiDenseWorldStats(self):
+        """dict(occupied, capacity, integrations, refused, inserted, skipped, out_of_range) of the world map"""
+        info = _capi.SemiDenseWorldInfo()
+        self.ctx.check(self.lib.vo_svo_get_semidense_world_stats(self._h, C.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in _capi.SemiDenseWorldInfo._fields_}
 
     def setSemiDenseAlignAffine(self, params):
         """A modifier of whichever alignment is on (include/vo_hip.h, "Semi-dense alignment with affine brightness"): its launches

@@ -522,6 +522,17 @@ class StereoVO {
     for (size_t i = 0; i < v.size(); ++i) o[i] = Point(v[i].x, v[i].y, v[i].z);
     return o;
   }
+  // the keyframes' maps fused into one world-frame voxel map (vo::StereoVO::setSemiDenseWorld): flushSemiDenseWorld() at the end of a
+  // sequence, getSemiDenseWorldPoints() the voxels' mean positions seen by at least min_keyframes keyframes
+  void setSemiDenseWorld(const vo_semidense_world_params *prm, int source = VO_SEMIDENSE_WORLD_RAW) { impl_.setSemiDenseWorld(prm, source); }
+  void flushSemiDenseWorld() { impl_.flushSemiDenseWorld(); }
+  PointVec getSemiDenseWorldPoints(int min_count = 1, int min_keyframes = 1) {
+    vo::PointVec v;
+    impl_.getSemiDenseWorldPoints(v, min_count, min_keyframes);
+    PointVec o(v.size());
+    for (size_t i = 0; i < v.size(); ++i) o[i] = Point(v[i].x, v[i].y, v[i].z);
+    return o;
+  }
   // NOT in the reference: CLAHE equalisation of every image before the tracker (vo::StereoVO::setEqualize; VO_EQ_CLAHE / VO_EQ_OFF)
   void setEqualize(int mode, double clip_limit = 40.0, int tiles_x = 8, int tiles_y = 8) { impl_.setEqualize(mode, clip_limit, tiles_x, tiles_y); }
   vo::StereoVO &device() { return impl_; }

@@ -330,6 +330,42 @@ class StereoVO {
                                                                sigma ? sigma->data() : nullptr, nullptr, &n, &fid));
     return fid >= 0;
   }
+  // The keyframes' maps fused into one world-frame voxel map (vo_svo_set_semidense_world; include/vo_hip.h, "Semi-dense world map"):
+  // when a keyframe is replaced one launch on the side stream integrates its map (source VO_SEMIDENSE_WORLD_RAW, or _REGULARIZED:
+  // its regularised copy) into a hash table of voxels; the odometry's results and every semi-dense result keep their bits. Needs
+  // setSemiDenseTemporal (and setSemiDenseRegularize for the regularised source). prm = nullptr: off. Throws while a frame is in flight.
+  static vo_semidense_world_params defaultSemiDenseWorldParams() {
+    vo_semidense_world_params p;
+    vo_semidense_world_default_params(&p);
+    return p;
+  }
+  void setSemiDenseWorld(const vo_semidense_world_params *prm, int source = VO_SEMIDENSE_WORLD_RAW) {
+    ctx_->check(vo_svo_set_semidense_world(svo_, prm, source));
+  }
+  // the current keyframe's map into the world map now (the end of a sequence); the next keyframe change does not integrate it again
+  void flushSemiDenseWorld() { ctx_->check(vo_svo_semidense_world_flush(svo_)); }
+  void clearSemiDenseWorld() { ctx_->check(vo_svo_semidense_world_clear(svo_)); }
+  vo_semidense_world_info getSemiDenseWorldStats() {
+    vo_semidense_world_info info;
+    ctx_->check(vo_svo_get_semidense_world_stats(svo_, &info));
+    return info;
+  }
+  // the voxels with at least min_count points seen by at least min_keyframes keyframes, in ascending key order: their weighted mean
+  // positions and, where asked for, point counts, keyframe counts and grey values. Returns their number.
+  int getSemiDenseWorldPoints(PointVec &xyz, int min_count = 1, int min_keyframes = 1, std::vector<uint32_t> *count = nullptr,
+                              std::vector<uint32_t> *keyframes = nullptr, std::vector<uint8_t> *grey = nullptr) {
+    int n = 0;
+    const int rc = vo_svo_get_semidense_world_points(svo_, min_count, min_keyframes, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &n);
+    if (rc != VO_ERR_CAPACITY) ctx_->check(rc);  // (room for none: the count is what was asked for)
+    xyz.resize((size_t)n);
+    if (count) count->resize((size_t)n);
+    if (keyframes) keyframes->resize((size_t)n);
+    if (grey) grey->resize((size_t)n);
+    if (n) ctx_->check(vo_svo_get_semidense_world_points(svo_, min_count, min_keyframes, n, nullptr, reinterpret_cast<float *>(xyz.data()), nullptr,
+                                                         count ? count->data() : nullptr, keyframes ? keyframes->data() : nullptr,
+                                                         grey ? grey->data() : nullptr, &n));
+    return n;
+  }
   // Direct image alignment on the keyframe's map (vo_svo_set_semidense_align; include/vo_hip.h, "Semi-dense alignment"): every frame
   // that is not a keyframe aligns its left image against the map from the odometry's pose, on the side stream in front of the
   // frame's temporal launch; nothing uses the aligned pose. Needs setSemiDenseTemporal. prm = nullptr: off. Throws while a frame is

@@ -289,6 +289,11 @@ int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, in
   if (is_keyframe) {
     const vo_pyramid &P = c->slots[slot_l];
     const size_t np = (size_t)d.w * (size_t)d.h;
+    // vo_svo_set_semidense_world: the outgoing keyframe's map goes into the world table before anything below overwrites it or its key plane
+    if (s->sdw.on) {
+      const int rc = vo_svo_semidense_world_enqueue(s);
+      if (rc) return rc;
+    }
     // vo_svo_set_semidense_propagate: the old map is warped into this keyframe before its key plane is overwritten
     const bool propagate = s->sdp.on, chain = propagate && t.have && s->sdp.chain && t.w == d.w && t.h == d.h;
     if (chain) {
@@ -321,6 +326,7 @@ int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, in
       VO_CHECK_HIP(c, hipGetLastError());
     }
     t.have = true;
+    s->sdw.done = false;
     t.frame_id = frame_id;
     t.n_fused = 0;
     memcpy(t.T_wk, T_wc, sizeof(t.T_wk));
@@ -355,6 +361,7 @@ int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, in
 }
 
 void vo_svo_semidense_temporal_free(vo_svo *s) {
+  vo_svo_semidense_world_free(s);
   vo_svo_semidense_propagate_free(s);
   vo_svo_semidense_regularize_free(s);
   vo_svo_semidense_align_free(s);

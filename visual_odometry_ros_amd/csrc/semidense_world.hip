@@ -1,0 +1,397 @@
+// semidense_world.hip — the world-frame voxel map that fuses the keyframes' semi-dense maps (include/vo_hip.h, "Semi-dense world
+// map"): the handle (vo_semidense_world_create / _integrate / _points / _stats / _clear / _destroy) and StereoVO's hook
+// (vo_svo_set_semidense_world, vo_svo_semidense_world_flush, vo_svo_get_semidense_world_points / _stats; the launch is placed by
+// vo_svo_semidense_temporal_enqueue in front of whatever overwrites the outgoing keyframe's map). semidense_world_device.hpp has the
+// kernels.
+#include "stereo_vo.hpp"
+#include "vo_internal.hpp"
+#include "vo_kernels.hpp"
+
+#include <math.h>
+
+#include <algorithm>
+#include <vector>
+
+#define SDW_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
+#define SDW_ST_AGENT(p, v) __hip_atomic_store((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define SDW_ATOMIC_ADD_AGENT(p, v) __hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+// (the explicit wait behind either fence, as semidense_align.hip)
+#define SDW_FENCE_RELEASE()                             \
+  do {                                                  \
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    \
+  } while (0)
+#define SDW_FENCE_ACQUIRE()                             \
+  do {                                                  \
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    \
+  } while (0)
+__device__ __forceinline__ unsigned long long sdw_cas64(unsigned long long *p, unsigned long long cmp, unsigned long long v) {
+  return atomicCAS(p, cmp, v);
+}
+#include "semidense_world_device.hpp"
+
+static_assert(sizeof(SdwSlot) == 64, "a slot is 64 bytes");
+
+struct vo_semidense_world {
+  vo_ctx *c = nullptr;
+  vo_semidense_world_params prm = {};
+  SdwSlot *slots = nullptr;
+  SdwState *st = nullptr;
+  unsigned seq = 0;             // the sequence number of the last call, refused ones included
+  SdwSlot *scratch = nullptr;   // the extraction's records (grows with the first getter that needs more)
+  size_t scratch_cap = 0;
+};
+
+extern "C" int vo_semidense_world_default_params(vo_semidense_world_params *p) {
+  if (!p) return VO_ERR_INVALID;
+  memset(p, 0, sizeof(*p));
+  p->voxel = 0.10f;
+  p->capacity_log2 = 22;
+  p->min_obs = 2;
+  p->z_max = 40.0f;
+  return VO_OK;
+}
+
+static int sdw_check_params(vo_ctx *c, const vo_semidense_world_params *p) {
+  if (!(p->voxel > 0.0f) || !isfinite(p->voxel)) VO_FAIL(c, VO_ERR_INVALID, "semi-dense world map: voxel must be positive and finite");
+  if (p->capacity_log2 < 10 || p->capacity_log2 > 28)
+    VO_FAIL(c, VO_ERR_INVALID, "semi-dense world map: capacity_log2=%d: expected 10..28", p->capacity_log2);
+  if (p->min_obs < 1 || p->min_obs > 255) VO_FAIL(c, VO_ERR_INVALID, "semi-dense world map: min_obs=%d: expected 1..255", p->min_obs);
+  if (!(p->z_max > 0.0f) || !isfinite(p->z_max)) VO_FAIL(c, VO_ERR_INVALID, "semi-dense world map: z_max must be positive and finite");
+  return VO_OK;
+}
+
+extern "C" int vo_semidense_world_create(vo_ctx *c, const vo_semidense_world_params *prm, vo_semidense_world **out) {
+  if (!c || !prm || !out) return VO_ERR_INVALID;
+  *out = nullptr;
+  const int rc = sdw_check_params(c, prm);
+  if (rc) return rc;
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  vo_semidense_world *wm = new vo_semidense_world();
+  wm->c = c;
+  wm->prm = *prm;
+  const size_t bytes = sizeof(SdwSlot) << prm->capacity_log2;
+  void *base = nullptr;
+  if (vo_dev_malloc(c, &base, bytes + sizeof(SdwState)) != hipSuccess) {
+    delete wm;
+    VO_FAIL(c, VO_ERR_HIP, "semi-dense world map: no device memory for 2^%d slots of 64 bytes", prm->capacity_log2);
+  }
+  wm->slots = (SdwSlot *)base;
+  wm->st = (SdwState *)((char *)base + bytes);
+  if (hipMemsetAsync(base, 0, bytes + sizeof(SdwState), c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+    (void)hipFree(base);
+    delete wm;
+    VO_FAIL(c, VO_ERR_HIP, "semi-dense world map: the table could not be cleared");
+  }
+  *out = wm;
+  return VO_OK;
+}
+
+extern "C" void vo_semidense_world_destroy(vo_semidense_world *wm) {
+  if (!wm) return;
+  (void)hipSetDevice(wm->c->device);
+  if (wm->slots) (void)hipFree(wm->slots);
+  if (wm->scratch) (void)hipFree(wm->scratch);
+  delete wm;
+}
+
+static int sdw_clear(vo_semidense_world *wm, hipStream_t s) {
+  vo_ctx *c = wm->c;
+  VO_CHECK_HIP(c, hipMemsetAsync(wm->slots, 0, (sizeof(SdwSlot) << wm->prm.capacity_log2) + sizeof(SdwState), s));
+  wm->seq = 0;
+  return VO_OK;
+}
+
+extern "C" int vo_semidense_world_clear(vo_semidense_world *wm) {
+  if (!wm) return VO_ERR_INVALID;
+  vo_ctx *c = wm->c;
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  const int rc = sdw_clear(wm, c->stream);
+  if (rc) return rc;
+  VO_CHECK_HIP(c, hipStreamSynchronize(c->stream));
+  return VO_OK;
+}
+
+// ---- the launch -------------------------------------------------------------------------------------------------------------------
+// On stream s, DEVICE planes throughout; d_key may be null. Every call that reaches the launch takes a sequence number.
+static int sdw_enqueue(vo_semidense_world *wm, hipStream_t s, const float *invd, const float *sigma, const uint8_t *n_obs, const uint8_t *d_key,
+                       int key_stride, int W, int H, const float K[4], const float T_wk[16]) {
+  vo_ctx *c = wm->c;
+  if (W < 1 || H < 1 || W > 65535 || H > 65535 || (long long)W * H > 0x7FFFFFFFll)
+    VO_FAIL(c, VO_ERR_SIZE, "semi-dense world map: the map must have 1 .. 65535 pixels a side and fewer than 2^31 in all");
+  if (d_key && key_stride < W) VO_FAIL(c, VO_ERR_INVALID, "semi-dense world map: key_stride %d below the width %d", key_stride, W);
+  if (!(K[0] > 0.0f) || !(K[1] > 0.0f) || !isfinite(K[0]) || !isfinite(K[1]) || !isfinite(K[2]) || !isfinite(K[3]))
+    VO_FAIL(c, VO_ERR_INVALID, "semi-dense world map: fx, fy must be positive, K finite");
+  for (int i = 0; i < 12; ++i)
+    if (!isfinite(T_wk[i])) VO_FAIL(c, VO_ERR_INVALID, "semi-dense world map: T_wk is not finite");
+  SdwArgs a;
+  memset(&a, 0, sizeof(a));
+  a.invd = invd;
+  a.sigma = sigma;
+  a.n_obs = n_obs;
+  a.Lk = d_key;
+  a.strideK = key_stride;
+  a.W = W;
+  a.H = H;
+  a.min_obs = wm->prm.min_obs;
+  a.z_max = wm->prm.z_max;
+  a.voxel = wm->prm.voxel;
+  a.fx = K[0], a.fy = K[1], a.cx = K[2], a.cy = K[3];
+  memcpy(a.T, T_wk, sizeof(a.T));
+  a.seq = ++wm->seq;
+  a.capacity_log2 = wm->prm.capacity_log2;
+  a.slots = wm->slots;
+  a.st = wm->st;
+  const unsigned nb = (unsigned)(((size_t)W * (size_t)H + SDW_BLOCK - 1) / SDW_BLOCK);
+  hipStream_t keep = c->stream;
+  c->stream = s;
+  vo_prof_begin(c, VO_K_AUX);
+  if (c->dbg[VO_DBG_SDW_FORM] == 1)
+    hipLaunchKernelGGL(semidense_world_integrate_kernel<false>, dim3(nb), dim3(SDW_NT), 0, s, a);
+  else
+    hipLaunchKernelGGL(semidense_world_integrate_kernel<true>, dim3(nb), dim3(SDW_NT), 0, s, a);
+  vo_prof_end(c);
+  c->stream = keep;
+  VO_CHECK_HIP(c, hipGetLastError());
+  return VO_OK;
+}
+
+extern "C" int vo_semidense_world_integrate(vo_semidense_world *wm, const float *invd, const float *sigma, const uint8_t *n_obs,
+                                            const uint8_t *key_plane, int key_stride, int key_on_device, int width, int height, int on_device,
+                                            const float K[4], const float T_wk[16]) {
+  if (!wm || !invd || !sigma || !n_obs || !K || !T_wk || width <= 0 || height <= 0) return VO_ERR_INVALID;
+  vo_ctx *c = wm->c;
+  if (width > c->cfg.max_width || height > c->cfg.max_height)
+    VO_FAIL(c, VO_ERR_SIZE, "%d x %d planes exceed vo_config.max_width x max_height", width, height);
+  if (key_plane && key_stride < width) VO_FAIL(c, VO_ERR_INVALID, "semi-dense world map: key_stride %d below the width %d", key_stride, width);
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const int W = width, H = height;
+  const size_t np = (size_t)W * (size_t)H;
+  vo_sdt_buffers *b = nullptr;  // the map's and the key plane's device copies
+  if ((key_plane && !key_on_device) || !on_device) {
+    const int rc = vo_sdt_ctx_buffers(c, &b);
+    if (rc) return rc;
+  }
+  const uint8_t *d_key = key_plane;
+  int d_stride = key_stride;
+  if (key_plane && !key_on_device) {
+    VO_CHECK_HIP(c, hipMemcpy2DAsync(b->key, (size_t)W, key_plane, (size_t)key_stride, (size_t)W, (size_t)H, hipMemcpyHostToDevice, s));
+    d_key = b->key;
+    d_stride = W;
+  }
+  const float *d_invd = invd, *d_sigma = sigma;
+  const uint8_t *d_no = n_obs;
+  if (!on_device) {
+    VO_CHECK_HIP(c, hipMemcpyAsync(b->invd, invd, np * sizeof(float), hipMemcpyHostToDevice, s));
+    VO_CHECK_HIP(c, hipMemcpyAsync(b->sigma, sigma, np * sizeof(float), hipMemcpyHostToDevice, s));
+    VO_CHECK_HIP(c, hipMemcpyAsync(b->n_obs, n_obs, np, hipMemcpyHostToDevice, s));
+    d_invd = b->invd, d_sigma = b->sigma, d_no = b->n_obs;
+  }
+  const int rc = sdw_enqueue(wm, s, d_invd, d_sigma, d_no, d_key, d_stride, W, H, K, T_wk);
+  VO_CHECK_HIP(c, hipStreamSynchronize(s));  // (the copies read the caller's memory)
+  return rc;
+}
+
+// ---- stats and extraction: synchronous on stream s ----------------------------------------------------------------------------------
+static int sdw_stats(vo_semidense_world *wm, hipStream_t s, vo_semidense_world_info *info) {
+  vo_ctx *c = wm->c;
+  SdwState st;
+  VO_CHECK_HIP(c, hipMemcpyAsync(&st, wm->st, sizeof(st), hipMemcpyDeviceToHost, s));
+  VO_CHECK_HIP(c, hipStreamSynchronize(s));
+  info->occupied = st.occupied;
+  info->capacity = 1ull << wm->prm.capacity_log2;
+  info->integrations = st.integrations;
+  info->refused = st.refused;
+  info->inserted = st.inserted;
+  info->skipped = st.skipped;
+  info->out_of_range = st.out_of_range;
+  return VO_OK;
+}
+
+extern "C" int vo_semidense_world_stats(vo_semidense_world *wm, vo_semidense_world_info *info) {
+  if (!wm || !info) return VO_ERR_INVALID;
+  VO_CHECK_HIP(wm->c, hipSetDevice(wm->c->device));
+  return sdw_stats(wm, wm->c->stream, info);
+}
+
+static int sdw_extract_launch(vo_semidense_world *wm, hipStream_t s, int min_count, int min_keyframes, unsigned *n) {
+  vo_ctx *c = wm->c;
+  SdwExtractArgs a;
+  memset(&a, 0, sizeof(a));
+  a.slots = wm->slots;
+  a.n_slots = (size_t)1 << wm->prm.capacity_log2;
+  a.min_count = (unsigned)min_count;
+  a.min_keyframes = (unsigned)min_keyframes;
+  a.out = wm->scratch;
+  a.cap = (unsigned)wm->scratch_cap;
+  a.st = wm->st;
+  VO_CHECK_HIP(c, hipMemsetAsync(&wm->st->n_extract, 0, sizeof(unsigned), s));
+  hipLaunchKernelGGL(semidense_world_extract_kernel, dim3((unsigned)(a.n_slots / SDW_NT)), dim3(SDW_NT), 0, s, a);
+  VO_CHECK_HIP(c, hipGetLastError());
+  VO_CHECK_HIP(c, hipMemcpyAsync(n, &wm->st->n_extract, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  VO_CHECK_HIP(c, hipStreamSynchronize(s));
+  return VO_OK;
+}
+
+static int sdw_points(vo_semidense_world *wm, hipStream_t s, int min_count, int min_keyframes, int cap, int32_t *index, float *xyz,
+                      uint32_t *weight, uint32_t *count, uint32_t *keyframes, uint8_t *grey, uint64_t *sums, int *n) {
+  vo_ctx *c = wm->c;
+  if (min_count < 1 || min_keyframes < 1) VO_FAIL(c, VO_ERR_INVALID, "semi-dense world map: min_count and min_keyframes are >= 1");
+  unsigned k = 0;
+  int rc = sdw_extract_launch(wm, s, min_count, min_keyframes, &k);
+  if (rc) return rc;
+  *n = (int)k;
+  if (cap == 0 || k == 0) return k > (unsigned)cap ? VO_ERR_CAPACITY : VO_OK;
+  if ((size_t)k > wm->scratch_cap) {  // the first getter that needs more records than any before: the scratch grows, the launch repeats
+    if (wm->scratch) (void)hipFree(wm->scratch);
+    wm->scratch = nullptr;
+    wm->scratch_cap = 0;
+    VO_CHECK_HIP(c, vo_dev_malloc(c, (void **)&wm->scratch, (size_t)k * sizeof(SdwSlot)));
+    wm->scratch_cap = k;
+    rc = sdw_extract_launch(wm, s, min_count, min_keyframes, &k);
+    if (rc) return rc;
+  }
+  std::vector<SdwSlot> rec(k);
+  VO_CHECK_HIP(c, hipMemcpyAsync(rec.data(), wm->scratch, (size_t)k * sizeof(SdwSlot), hipMemcpyDeviceToHost, s));
+  VO_CHECK_HIP(c, hipStreamSynchronize(s));
+  std::sort(rec.begin(), rec.end(), [](const SdwSlot &x, const SdwSlot &y) { return x.key < y.key; });
+  const size_t m = k < (unsigned)cap ? k : (size_t)cap;
+  const double voxel = (double)wm->prm.voxel;
+  for (size_t i = 0; i < m; ++i) {
+    const SdwSlot &r = rec[i];
+    const sdw_u64 sxyz[3] = {r.sx, r.sy, r.sz};
+    for (int ax = 0; ax < 3; ++ax) {
+      const int idx = (int)((r.key >> (42 - 21 * ax)) & 0x1FFFFFull) - 1048576;
+      if (index) index[3 * i + ax] = idx;
+      if (xyz) {  // (host code: -ffp-contract=off, every operation rounded on its own)
+        const double f = (double)sxyz[ax] / (double)r.sw + 0.5;
+        const double p = (double)idx + f * (1.0 / 1024);
+        xyz[3 * i + ax] = (float)(p * voxel);
+      }
+    }
+    if (weight) weight[i] = r.sw > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)r.sw;
+    if (count) count[i] = r.cnt;
+    if (keyframes) keyframes[i] = r.kf_cnt;
+    if (grey) grey[i] = (uint8_t)((r.sg + r.sw / 2) / r.sw);
+    if (sums) sums[5 * i] = r.sw, sums[5 * i + 1] = r.sx, sums[5 * i + 2] = r.sy, sums[5 * i + 3] = r.sz, sums[5 * i + 4] = r.sg;
+  }
+  return k > (unsigned)cap ? VO_ERR_CAPACITY : VO_OK;
+}
+
+extern "C" int vo_semidense_world_points(vo_semidense_world *wm, int min_count, int min_keyframes, int cap, int32_t *index, float *xyz,
+                                         uint32_t *weight, uint32_t *count, uint32_t *keyframes, uint8_t *grey, uint64_t *sums, int *n) {
+  if (!wm || !n || cap < 0) return VO_ERR_INVALID;
+  VO_CHECK_HIP(wm->c, hipSetDevice(wm->c->device));
+  return sdw_points(wm, wm->c->stream, min_count, min_keyframes, cap, index, xyz, weight, count, keyframes, grey, sums, n);
+}
+
+// ---- StereoVO's hook ------------------------------------------------------------------------------------------------------------------
+// The current keyframe's map — the temporal option's planes, or the regularised copy — into the table, on the side stream behind the
+// launches that wrote it. Called by vo_svo_semidense_temporal_enqueue at the top of a keyframe change, in front of the propagation's
+// scatter and the key plane's copy, and by vo_svo_semidense_world_flush; `done`: the map is marked so that it is not integrated twice.
+int vo_svo_semidense_world_enqueue(vo_svo *s) {
+  vo_svo_semidense_world &w = s->sdw;
+  const vo_svo_semidense_temporal &t = s->sdt;
+  if (!w.on || !t.have || w.done) return VO_OK;
+  const float *invd = t.buf.invd, *sigma = t.buf.sigma;
+  const uint8_t *n_obs = t.buf.n_obs;
+  if (w.source == VO_SEMIDENSE_WORLD_REGULARIZED) {
+    const vo_svo_semidense_regularize &r = s->sdr;
+    if (!r.on || !r.have || r.frame_id != t.frame_id) return VO_OK;  // no regularised planes of this keyframe: nothing to integrate
+    invd = r.buf.invd, sigma = r.buf.sigma, n_obs = r.buf.n_obs;
+  }
+  const int rc = sdw_enqueue(w.wm, s->c->stream2, invd, sigma, n_obs, t.buf.key, t.w, t.w, t.h, s->prm.frame.Kl, t.T_wk);
+  if (rc) return rc;
+  w.done = true;
+  return VO_OK;
+}
+
+void vo_svo_semidense_world_free(vo_svo *s) {
+  vo_semidense_world_destroy(s->sdw.wm);
+  s->sdw = vo_svo_semidense_world();
+}
+
+extern "C" int vo_svo_set_semidense_world(vo_svo *s, const vo_semidense_world_params *prm, int source) {
+  if (!s) return VO_ERR_INVALID;
+  vo_ctx *c = s->c;
+  if (s->pending) VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world: a frame is in flight: call vo_svo_result first");
+  if (s->mono) VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world: a stereo driver only");
+  vo_svo_semidense_world &w = s->sdw;
+  if (!prm) {
+    w.on = false;
+    return VO_OK;
+  }
+  if (!s->sdt.on || !s->sd.on)
+    VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world: needs the temporal option: vo_svo_set_semidense_temporal first");
+  if (source != VO_SEMIDENSE_WORLD_RAW && source != VO_SEMIDENSE_WORLD_REGULARIZED)
+    VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world: source=%d: expected VO_SEMIDENSE_WORLD_RAW or _REGULARIZED", source);
+  if (source == VO_SEMIDENSE_WORLD_REGULARIZED && !s->sdr.on)
+    VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world: the regularised source needs vo_svo_set_semidense_regularize first");
+  int rc = sdw_check_params(c, prm);
+  if (rc) return rc;
+  if (w.wm && w.wm->prm.capacity_log2 != prm->capacity_log2)
+    VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world: capacity_log2 is fixed by the first enable (%d)", w.wm->prm.capacity_log2);
+  if (!w.wm) {
+    rc = vo_semidense_world_create(c, prm, &w.wm);  // the option's only allocation, at the first enable
+    if (rc) return rc;
+  } else if (memcmp(&w.wm->prm, prm, sizeof(*prm)) != 0) {  // another voxel or gate: the sums of the old one mean nothing
+    VO_CHECK_HIP(c, hipSetDevice(c->device));
+    if (s->sd.have) VO_CHECK_HIP(c, hipEventSynchronize(s->sd.done));
+    rc = vo_semidense_world_clear(w.wm);
+    if (rc) return rc;
+    w.wm->prm = *prm;
+    w.done = false;
+  }
+  w.source = source;
+  w.on = true;
+  return VO_OK;
+}
+
+static int svo_sdw_ready(vo_svo *s, const char *who) {
+  vo_ctx *c = s->c;
+  if (s->pending) VO_FAIL(c, VO_ERR_INVALID, "%s: a frame is in flight: call vo_svo_result first", who);
+  if (!s->sdw.on || !s->sdw.wm) VO_FAIL(c, VO_ERR_INVALID, "%s: the option is off: vo_svo_set_semidense_world", who);
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  if (s->sd.have) VO_CHECK_HIP(c, hipEventSynchronize(s->sd.done));  // the side stream's last launch only
+  return VO_OK;
+}
+
+extern "C" int vo_svo_semidense_world_flush(vo_svo *s) {
+  if (!s) return VO_ERR_INVALID;
+  vo_ctx *c = s->c;
+  if (s->pending) VO_FAIL(c, VO_ERR_INVALID, "vo_svo_semidense_world_flush: a frame is in flight: call vo_svo_result first");
+  if (!s->sdw.on || !s->sdw.wm) VO_FAIL(c, VO_ERR_INVALID, "vo_svo_semidense_world_flush: the option is off: vo_svo_set_semidense_world");
+  if (!s->sdt.on || !s->sdt.have || s->sdw.done) return VO_OK;
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  const int rc = vo_svo_semidense_world_enqueue(s);
+  if (rc) return rc;
+  VO_CHECK_HIP(c, hipEventRecord(s->sd.done, c->stream2));
+  return VO_OK;
+}
+
+extern "C" int vo_svo_semidense_world_clear(vo_svo *s) {
+  if (!s) return VO_ERR_INVALID;
+  int rc = svo_sdw_ready(s, "vo_svo_semidense_world_clear");
+  if (rc) return rc;
+  rc = vo_semidense_world_clear(s->sdw.wm);
+  if (rc) return rc;
+  s->sdw.done = false;
+  return VO_OK;
+}
+
+extern "C" int vo_svo_get_semidense_world_stats(vo_svo *s, vo_semidense_world_info *info) {
+  if (!s || !info) return VO_ERR_INVALID;
+  const int rc = svo_sdw_ready(s, "vo_svo_get_semidense_world_stats");
+  if (rc) return rc;
+  return sdw_stats(s->sdw.wm, s->c->stream, info);
+}
+
+extern "C" int vo_svo_get_semidense_world_points(vo_svo *s, int min_count, int min_keyframes, int cap, int32_t *index, float *xyz,
+                                                 uint32_t *weight, uint32_t *count, uint32_t *keyframes, uint8_t *grey, int *n) {
+  if (!s || !n || cap < 0) return VO_ERR_INVALID;
+  const int rc = svo_sdw_ready(s, "vo_svo_get_semidense_world_points");
+  if (rc) return rc;
+  return sdw_points(s->sdw.wm, s->c->stream, min_count, min_keyframes, cap, index, xyz, weight, count, keyframes, grey, nullptr, n);
+}

@@ -65,6 +65,14 @@ struct vo_svo_semidense_regularize {
   float T_wk[16] = {};
 };
 
+// vo_svo_set_semidense_world (semidense_world.hip): the outgoing keyframe's map goes into a world-frame voxel table when the next
+// keyframe replaces it (or at vo_svo_semidense_world_flush). done: the current keyframe's map is in the table already.
+struct vo_svo_semidense_world {
+  bool on = false, done = false;
+  int source = 0;
+  struct vo_semidense_world *wm = nullptr;
+};
+
 // vo_svo_set_semidense_align (semidense_align.hip): at every frame that is not a keyframe the frame's left image is aligned against
 // the keyframe's map, on the side stream in front of the frame's temporal launch. `have`: the last frame has a result in `buf`.
 struct vo_svo_semidense_align {
@@ -127,6 +135,7 @@ struct vo_svo {
   vo_svo_semidense_propagate sdp;  // vo_svo_set_semidense_propagate: that map carried over to the next keyframe
   vo_svo_semidense_align sda;  // vo_svo_set_semidense_align: every later frame's left image aligned against that map
   vo_svo_semidense_regularize sdr;  // vo_svo_set_semidense_regularize: a regularised copy of that map behind every launch that writes it
+  vo_svo_semidense_world sdw;  // vo_svo_set_semidense_world: the keyframes' maps fused into one world-frame voxel table
   int mono = 0;  // the keyframe storage serves a MonoVO (mono_vo.hip): one observation per keyframe entry, bundled flags
   // all_stkeyframes_ (stats_keyframe): every keyframe's current pose (host) and where its related landmarks' ids are kept
   // on the device (a pool that only grows)
@@ -166,6 +175,9 @@ void vo_svo_semidense_propagate_free(vo_svo *s);
 // semidense_regularize.hip: one launch on the side stream behind the launch that wrote the map (seed, resolve or temporal)
 int vo_svo_semidense_regularize_enqueue(vo_svo *s);
 void vo_svo_semidense_regularize_free(vo_svo *s);
+// semidense_world.hip: the current keyframe's map into the table, on the side stream, unless it is there already
+int vo_svo_semidense_world_enqueue(vo_svo *s);
+void vo_svo_semidense_world_free(vo_svo *s);
 // semidense_align.hip: on the side stream (c->stream points at it) in front of a non-keyframe frame's temporal launch
 int vo_svo_semidense_align_enqueue(vo_svo *s, int slot_l, int frame_id, const float T_ck[16]);
 // (vo_svo_set_semidense_align_pyr) at a keyframe, behind the key plane's copy: the slot's coarser levels next to it
