@@ -21,7 +21,8 @@ of the run. --semidense-propagate: with --semidense-temporal, a keyframe's map i
 the odometry's pose, fused with the new static result) instead of being seeded afresh, so a keyframe's file also holds what earlier
 keyframes observed. --semidense-world FILE.ply: with --semidense-temporal, every keyframe's map is fused into one world-frame voxel
 map when the next keyframe replaces it (the last one at the end); FILE.ply has x y z grey count keyframes per voxel
-(--semidense-voxel V: the voxel's edge, default 0.1 m; --semidense-world-min-keyframes N: only voxels N keyframes reached).
+(--semidense-voxel V: the voxel's edge, default 0.1 m; --semidense-world-min-keyframes N: only voxels N keyframes reached;
+--semidense-world-reanchor [MIN_MOVE]: the map follows the local bundle adjustment, so that it agrees with the keyframe poses).
 --semidense-regularize: with --semidense-temporal, a regularised copy of the map is kept next to it (entries their
 neighbours contradict removed, high-gradient holes whose neighbours agree filled, values smoothed) and written as
 `semidense_regularized_<keyframe's frame id>.ply` wherever the fused file is written; its filled pixels have one observation, so N
@@ -105,11 +106,15 @@ def semidense_options(args):
             raise SystemExit("--semidense-regularize needs --semidense DIR")
         if args.semidense_world or args.semidense_voxel is not None or args.semidense_world_min_keyframes is not None:
             raise SystemExit("--semidense-world / --semidense-voxel / --semidense-world-min-keyframes need --semidense DIR")
+        if args.semidense_world_reanchor is not None:
+            raise SystemExit("--semidense-world-reanchor needs --semidense DIR")
         return {}
     if args.semidense_world and not args.semidense_temporal:
         raise SystemExit("--semidense-world needs --semidense-temporal")
     if (args.semidense_voxel is not None or args.semidense_world_min_keyframes is not None) and not args.semidense_world:
         raise SystemExit("--semidense-voxel / --semidense-world-min-keyframes need --semidense-world FILE.ply")
+    if args.semidense_world_reanchor is not None and (not args.semidense_world or not args.semidense_world_reanchor >= 0):
+        raise SystemExit("--semidense-world-reanchor [MIN_MOVE]: voxels, >= 0, with --semidense-world FILE.ply")
     if args.semidense_voxel is not None and not args.semidense_voxel > 0:
         raise SystemExit("--semidense-voxel V: metres, > 0")
     if args.semidense_world_min_keyframes is not None and args.semidense_world_min_keyframes < 1:
@@ -142,6 +147,9 @@ def semidense_options(args):
         sd["regularize"] = True
     if args.semidense_world:
         sd["world"] = True if args.semidense_voxel is None else {"voxel": args.semidense_voxel}
+        if args.semidense_world_reanchor is not None:
+            sd["world"] = dict({} if sd["world"] is True else sd["world"],
+                               reanchor=True if args.semidense_world_reanchor == 0 else {"min_move": args.semidense_world_reanchor})
     if args.semidense_align:
         sd["align"] = True
         if args.semidense_align_levels is not None or args.semidense_align_start is not None:
@@ -223,6 +231,9 @@ def parse_args(argv=None):
     ap.add_argument("--semidense-voxel", type=float, default=None, metavar="V", help="voxel edge of --semidense-world in metres (default 0.1)")
     ap.add_argument("--semidense-world-min-keyframes", type=int, default=None, metavar="N",
                     help="--semidense-world: write the voxels at least N keyframes have reached (default 1)")
+    ap.add_argument("--semidense-world-reanchor", type=float, nargs="?", const=0.0, default=None, metavar="MIN_MOVE",
+                    help="--semidense-world: the map follows the local BA: a keyframe's map is re-anchored where the BA moves the keyframe "
+                         "(by MIN_MOVE voxels or more; default: any change)")
     ap.add_argument("--semidense-align", default=None, metavar="FILE",
                     help="--semidense-temporal: align every later frame's left image against the keyframe's map; one line per frame into FILE")
     ap.add_argument("--semidense-align-levels", type=int, default=None, metavar="N",

@@ -1322,8 +1322,8 @@ int vo_svo_get_semidense_regularized_points(vo_svo *svo, int world, int min_obs,
  * keyframe change does not integrate it again. vo_svo_get_semidense_world_points / _stats wait for the side stream's last launch
  * only; vo_svo_semidense_world_clear empties the table. All: VO_ERR_INVALID while a frame is in flight or with the option off.
  *
- * Out of scope: re-anchoring voxels after the local BA moves a keyframe (a keyframe is integrated with the pose it had when it was
- * replaced); free-space carving and the removal of moving objects; a TSDF, surfaces or meshes; growing or rehashing the table; a
+ * Out of scope: re-anchoring voxels after the local BA moves a keyframe (since added: DESIGN §25, the block below; without that option
+ * a keyframe stays integrated with the pose it had when it was replaced); free-space carving and the removal of moving objects; a TSDF, surfaces or meshes; growing or rehashing the table; a
  * tighter refusal bound than W H; streaming the map out in tiles; MonoVO and vo_batch streams; any use of the map in the odometry.
  * With vo_svo_set_semidense_propagate on a propagated pixel re-enters every keyframe that carries it, so kf_cnt counts carried
  * surfaces too: min_keyframes then asks for less than independent confirmation. */
@@ -1354,6 +1354,76 @@ int vo_svo_semidense_world_clear(vo_svo *svo);
 int vo_svo_get_semidense_world_stats(vo_svo *svo, vo_semidense_world_info *info);
 int vo_svo_get_semidense_world_points(vo_svo *svo, int min_count, int min_keyframes, int cap, int32_t *index, float *xyz,
                                       uint32_t *weight, uint32_t *count, uint32_t *keyframes, uint8_t *grey, int *n);
+
+/* ---- Semi-dense world map: removal and re-anchoring -----------------------------------------------------------------
+ * Every accumulator of the table above is an integer, so an integration can be taken out again EXACTLY and put back under another
+ * pose: afterwards every live voxel holds the bits it would hold had the map been integrated with the new pose in the first place —
+ * no float drift, no dependence on arrival order. tests/semidense_world_reanchor_restatement.py restates it.
+ *   removal    of one earlier integration, given the SAME planes, K, T_wk, key plane and parameters: the points, keys, q, wq and grey
+ *              are those of the integration (the same text forms them). It takes a seq of its own, like an integration.
+ *   lookup     home slot and linear probing as above, but the key words are only READ, never compare-and-swapped: a probe that
+ *              meets key 0 ends, the point is counted as MISSING and nothing is subtracted. Otherwise the point counts as REMOVED.
+ *   sums       sw, sx, sy, sz, sg get the two's complement added (0 - v modulo 2^64), cnt gets 0u - c; kf_cnt with last_seq:
+ *              old = atomicMax(&last_seq, seq), the one arrival that sees old < seq adds 0u - 1u. Removing what was never integrated
+ *              into a voxel that exists wraps its sums: the caller's business, as is removing twice.
+ *   vacated    a voxel whose cnt reaches 0 KEEPS its key, so that the probe chains of its neighbours stay intact. The extraction
+ *              skips it (min_count >= 1); `occupied` keeps meaning "claimed slots", and a removal never changes it. `vacant` is the
+ *              number of slots with key != 0 and cnt == 0, counted by a small launch of its own when the statistics are asked for.
+ *              A later integration that reaches a vacated voxel finds its slot and fills it again.
+ *   refusal    all or nothing, by the integration's own test on the same word: occupied + W H > 2^capacity_log2 / 2. A refused
+ *              removal touches `refused_removals` (+ 1) only (and takes its seq). A removal and the integration enqueued behind it
+ *              therefore decide alike, without a host turn.
+ *   re-anchor  vo_semidense_world_reanchor(planes, K, T_old, T_new): where the first 12 floats of the two poses have equal BITS,
+ *              *moved = 0, no launch, no seq. Otherwise *moved = 1 and it enqueues the removal with T_old, then the integration
+ *              above with T_new, back to back (two seqs); both poses are validated before either launch. `integrations`,
+ *              `inserted`, `skipped` and `out_of_range` of vo_semidense_world_info therefore count re-integrations too.
+ *   counters   vo_semidense_world_reanchor_info: removals (accepted), refused_removals, removed and missing (points), reanchors
+ *              (calls that enqueued their pair, refused pairs included), vacant. vo_semidense_world_info keeps its layout; clear
+ *              zeroes these too.
+ * vo_semidense_world_remove takes the arguments of _integrate and is synchronous like it. The launch has the integration's geometry
+ * (ceil(W H / 1024) workgroups of 256) and its pre-aggregated shape: one global update per distinct voxel of a workgroup.
+ *
+ *
+ * StereoVO: vo_svo_set_semidense_world_reanchor(svo, on, min_move) — needs vo_svo_set_semidense_world on and vo_svo_params.local_ba;
+ * VO_ERR_INVALID otherwise, with a negative or non-finite min_move, while a frame is in flight or on a mono driver. Without it a
+ * keyframe's map stays in the table with the pose it had when the next keyframe replaced it, while the local BA goes on moving that
+ * keyframe for as long as it sits in the window: vo_svo_get_keyframes publishes the current poses, the world map the stale ones. With
+ * it the map follows. The first enable makes the option's one allocation, a ring of kf_window places of 10 bytes per pixel of
+ * max_width x max_height (invd f32, sigma f32, n_obs u8, the key plane u8). Wherever the driver integrates a keyframe's map (the
+ * keyframe change, the flush) it first copies what it integrates into a free place, device to device on the side stream in front of
+ * everything that overwrites the outgoing map, and records an ANCHOR: the keyframe's frame_id, its index among vo_svo_get_keyframes'
+ * keyframes and the pose the map goes in with, the "applied" pose. The integration itself is unchanged. In vo_svo_result of a
+ * keyframe frame, behind that frame's integration on the side stream, every anchor whose keyframe is still in the window is re-anchored
+ * from its applied pose to the keyframe's current one where their first 12 floats differ in bits and
+ *   move = max_r |dt_r| + z_max * max_r sum_c |dR_rc| >= min_move * voxel   (in double, from the two float poses; min_move in voxels,
+ * 0: any difference), and the current pose becomes the applied one. Nothing waits. An anchor whose keyframe has left the window is
+ * frozen and its place reused. The device decides whether a pair is refused; a refused pair leaves the map where it was, so the next
+ * call of vo_svo_get_semidense_world_stats, _anchors or _reanchor_stats — refused_removals comes with the counters they fetch, no
+ * copy or wait of its own; _points does not look — gives the anchor its previous pose back (a table never gets emptier and the
+ * driver's maps have one size, so the refused pairs are the last ones enqueued). The invariant: after one of these three the
+ * table holds the bits of a fresh table fed, in order, every anchor's map with its applied pose. With min_move 0 every applied pose
+ * equals the keyframe's pose of vo_svo_get_keyframes to the bit. vo_svo_get_semidense_world_anchors returns the anchors in
+ * integration order (*n the true count, VO_ERR_CAPACITY where n > cap; every output may be NULL; in_window: the keyframe is still
+ * in the window), vo_svo_get_semidense_world_reanchor_stats the counters above. vo_svo_semidense_world_clear forgets the anchors.
+ * While the option is off integrated maps get no anchor. With it off no launch, allocation, wait or result bit differs; with it on
+ * the odometry, every semi-dense result and the keyframe poses keep every bit.
+ *
+ * Out of scope: a fused remove-and-add launch; a compact per-keyframe point list instead of retained planes; reclaiming vacated
+ * slots or rehashing; re-anchoring the per-keyframe map, the propagation or the alignment; re-anchoring keyframes that have left the
+ * window; MonoVO and vo_batch; any use of the map in the odometry. */
+typedef struct {
+  unsigned long long removals, refused_removals, removed, missing, reanchors, vacant;
+} vo_semidense_world_reanchor_info;
+int vo_semidense_world_remove(vo_semidense_world *wm, const float *invd, const float *sigma, const uint8_t *n_obs,
+                              const uint8_t *key_plane, int key_stride, int key_on_device, int width, int height, int on_device,
+                              const float K[4], const float T_wk[16]);
+int vo_semidense_world_reanchor(vo_semidense_world *wm, const float *invd, const float *sigma, const uint8_t *n_obs,
+                                const uint8_t *key_plane, int key_stride, int key_on_device, int width, int height, int on_device,
+                                const float K[4], const float T_old[16], const float T_new[16], int *moved);
+int vo_semidense_world_reanchor_stats(vo_semidense_world *wm, vo_semidense_world_reanchor_info *info);
+int vo_svo_set_semidense_world_reanchor(vo_svo *svo, int on, float min_move);
+int vo_svo_get_semidense_world_anchors(vo_svo *svo, int cap, int32_t *frame_id, int32_t *kf_index, float *T_wk, int32_t *in_window, int *n);
+int vo_svo_get_semidense_world_reanchor_stats(vo_svo *svo, vo_semidense_world_reanchor_info *info);
 
 /* ---- undistortion / stereo rectification in front of the trackers ----------
  * core/visual_odometry/camera.cpp. A context holds the maps of two cameras

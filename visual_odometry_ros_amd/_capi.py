@@ -131,6 +131,10 @@ class SemiDenseWorldInfo(C.Structure):  # vo_semidense_world_info
     _fields_ = [(k, C.c_ulonglong) for k in ("occupied", "capacity", "integrations", "refused", "inserted", "skipped", "out_of_range")]
 
 
+class SemiDenseWorldReanchorInfo(C.Structure):  # vo_semidense_world_reanchor_info
+    _fields_ = [(k, C.c_ulonglong) for k in ("removals", "refused_removals", "removed", "missing", "reanchors", "vacant")]
+
+
 class SemiDenseAlignParams(C.Structure):  # vo_semidense_align_params
     _fields_ = [("min_obs", C.c_int), ("huber", C.c_float), ("max_iters", C.c_int), ("eps", C.c_float), ("min_pixels", C.c_int)]
 
@@ -219,7 +223,9 @@ SYMBOLS = [
     "vo_semidense_regularize_default_params", "vo_semidense_map_regularize", "vo_svo_set_semidense_regularize",
     "vo_svo_get_semidense_regularized", "vo_svo_get_semidense_regularized_points",
     "vo_semidense_world_default_params", "vo_semidense_world_create", "vo_semidense_world_destroy", "vo_semidense_world_clear",
-    "vo_semidense_world_integrate", "vo_semidense_world_stats", "vo_semidense_world_points", "vo_svo_set_semidense_world",
+    "vo_semidense_world_integrate", "vo_semidense_world_remove", "vo_semidense_world_reanchor", "vo_semidense_world_reanchor_stats",
+    "vo_svo_set_semidense_world_reanchor", "vo_svo_get_semidense_world_anchors", "vo_svo_get_semidense_world_reanchor_stats",
+    "vo_semidense_world_stats", "vo_semidense_world_points", "vo_svo_set_semidense_world",
     "vo_svo_semidense_world_flush", "vo_svo_semidense_world_clear", "vo_svo_get_semidense_world_stats", "vo_svo_get_semidense_world_points",
 ]
 
@@ -364,6 +370,12 @@ def load():
     lib.vo_semidense_world_clear.argtypes = [vp]
     lib.vo_semidense_world_integrate.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp]
     lib.vo_semidense_world_stats.argtypes = [vp, vp]
+    lib.vo_semidense_world_remove.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp]
+    lib.vo_semidense_world_reanchor.argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp]
+    lib.vo_semidense_world_reanchor_stats.argtypes = [vp, vp]
+    lib.vo_svo_set_semidense_world_reanchor.argtypes = [vp, ci, C.c_float]
+    lib.vo_svo_get_semidense_world_anchors.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    lib.vo_svo_get_semidense_world_reanchor_stats.argtypes = [vp, vp]
     lib.vo_semidense_world_points.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.vo_svo_set_semidense_world.argtypes = [vp, vp, ci]
     lib.vo_svo_semidense_world_flush.argtypes = [vp]

@@ -237,8 +237,31 @@ class SemiDenseWorld:
         """One integration: map a SemiDenseMap / SemiDenseRegularized / dict(invd=, sigma=, n_obs=) of arrays, K = fx, fy, cx, cy,
         T_wk (4, 4), key the keyframe's left u8 plane or None. With on_device=(width, height) the map's planes are DEVICE addresses;
         with key_on_device=stride so is key. Whether it was refused shows in stats()."""
+        self._launch(self.lib.vo_semidense_world_integrate, map, K, (T_wk,), key, on_device, key_on_device)
+
+    def remove(self, map, K, T_wk, key=None, on_device=None, key_on_device=None):
+        """The exact removal of an earlier integrate(...) with the same arguments (include/vo_hip.h, "Semi-dense world map: removal
+        and re-anchoring"): every sum of every voxel it reached goes back by what it added. Whether it was refused, and the points
+        that found no voxel, show in reanchorStats()."""
+        self._launch(self.lib.vo_semidense_world_remove, map, K, (T_wk,), key, on_device, key_on_device)
+
+    def reanchor(self, map, K, T_old, T_new, key=None, on_device=None, key_on_device=None):
+        """The map integrated earlier with T_old moves to T_new: the removal with T_old and the integration with T_new back to
+        back. Returns False, with nothing launched, where the two poses' first 12 floats have the same bits; True otherwise."""
+        moved = C.c_int()
+        self._launch(self.lib.vo_semidense_world_reanchor, map, K, (T_old, T_new), key, on_device, key_on_device, C.byref(moved))
+        return bool(moved.value)
+
+    def reanchorStats(self):
+        """dict(removals, refused_removals, removed, missing, reanchors, vacant); vacant is counted by a launch of its own"""
+        info = _capi.SemiDenseWorldReanchorInfo()
+        self.ctx.check(self.lib.vo_semidense_world_reanchor_stats(self._h, C.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in _capi.SemiDenseWorldReanchorInfo._fields_}
+
+    def _launch(self, fn, map, K, poses, key, on_device, key_on_device, *tail):
         get = (lambda k: getattr(map, k)) if isinstance(map, tuple) else (lambda k: map[k])
-        Ka, Ta = np.ascontiguousarray(K, np.float32).reshape(4), np.ascontiguousarray(T_wk, np.float32).reshape(4, 4)
+        Ka = np.ascontiguousarray(K, np.float32).reshape(4)
+        Ts = [np.ascontiguousarray(T, np.float32).reshape(4, 4) for T in poses]
         if on_device is not None:
             w, h = on_device
             planes = [C.c_void_p(get(k)) for k in ("invd", "sigma", "n_obs")]
@@ -258,8 +281,8 @@ class SemiDenseWorld:
             if ka.shape != (h, w):
                 raise ValueError("key is a plane of the map's (height, width)")
             pk, stride = ka.ctypes.data, ka.strides[0]
-        self.ctx.check(self.lib.vo_semidense_world_integrate(self._h, *planes, pk, stride, int(key_on_device is not None), int(w), int(h),
-                                                             int(on_device is not None), Ka.ctypes.data, Ta.ctypes.data))
+        self.ctx.check(fn(self._h, *planes, pk, stride, int(key_on_device is not None), int(w), int(h), int(on_device is not None),
+                          Ka.ctypes.data, *(T.ctypes.data for T in Ts), *tail))
 
     def points(self, min_count=1, min_keyframes=1, capacity=None):
         """The voxels with count >= min_count and keyframes >= min_keyframes: a SemiDenseWorldPoints in ascending key order."""
@@ -1757,7 +1780,8 @@ class StereoVO:
         its "temporal": True or dict(z_max=..., max_search=...) also switches setSemiDenseTemporal on, and with it
         "propagate": True or dict(min_obs=, max_diff=, chi=, sigma_add=) setSemiDensePropagate,
         "regularize": True or dict(radius=, chi=, dist_sigma=, min_support=, fill_min=, g_min=) setSemiDenseRegularize,
-        "world": True or dict(voxel=, capacity_log2=, min_obs=, z_max=, source="raw" | "regularized") setSemiDenseWorld,
+        "world": True or dict(voxel=, capacity_log2=, min_obs=, z_max=, source="raw" | "regularized") setSemiDenseWorld; with
+        reanchor=True or reanchor=dict(min_move=0.0) in it, the maps follow the local BA (setSemiDenseWorldReanchor),
         "align": True or dict(min_obs=, huber=, max_iters=, eps=, min_pixels=) setSemiDenseAlign; with levels=, max_iters_level= or
         start="odometry" | "previous" in it, coarse to fine on a map pyramid (setSemiDenseAlignPyramid); with affine=True or
         affine=dict(gain0=, offset0=) in it, gain and offset are estimated next to the pose (setSemiDenseAlignAffine).
@@ -2024,12 +2048,51 @@ class StereoVO:
             return
         params = dict(params)
         src = params.pop("source", "raw")
+        reanchor = params.pop("reanchor", None)
         if source is not None:
             src = source
         if src not in SEMIDENSE_WORLD_SOURCE:
             raise ValueError(f"setSemiDenseWorld: source {src!r}; known: {sorted(SEMIDENSE_WORLD_SOURCE)}")
         p = _semidense_world_params(self.lib, params)
         self.ctx.check(self.lib.vo_svo_set_semidense_world(self._h, C.byref(p), SEMIDENSE_WORLD_SOURCE[src]))
+        if reanchor is not None:
+            self.setSemiDenseWorldReanchor(reanchor)
+
+    def setSemiDenseWorldReanchor(self, params):
+        """The world map follows the local BA (include/vo_hip.h, "Semi-dense world map: removal and re-anchoring"): the maps of the
+        keyframes in the BA's window are retained on the device, and at every keyframe each one whose keyframe the BA has moved is
+        taken out of the table and put back with the keyframe's current pose, so that getSemiDenseWorld() agrees with
+        getKeyframes(). params: True or dict(min_move=0.0) — the smallest motion, in voxels, worth a re-anchor; None or False: off.
+        Needs setSemiDenseWorld and local_ba. The odometry's results, the semi-dense results and the keyframe poses do not change.
+        Refused while a frame is in flight."""
+        if params is None or params is False:
+            self.ctx.check(self.lib.vo_svo_set_semidense_world_reanchor(self._h, 0, 0.0))
+            return
+        prm = {} if params is True else dict(params)
+        min_move = float(prm.pop("min_move", 0.0))
+        if prm:
+            raise ValueError(f"setSemiDenseWorldReanchor: unknown parameter {sorted(prm)[0]!r}; known: ['min_move']")
+        self.ctx.check(self.lib.vo_svo_set_semidense_world_reanchor(self._h, 1, min_move))
+
+    def getSemiDenseWorldAnchors(self):
+        """Per keyframe integrated with setSemiDenseWorldReanchor on, in integration order: dict(frame_id int32 [n], index int32 [n]
+        (the keyframe's place in getKeyframes()), T_wk float32 [n, 4, 4] (the pose its map is in the table with), in_window bool [n])."""
+        n = C.c_int()
+        rc = self.lib.vo_svo_get_semidense_world_anchors(self._h, 0, None, None, None, None, C.byref(n))
+        if rc < 0 and rc != -8:
+            self.ctx.check(rc)
+        m = max(n.value, 1)
+        fid, idx, T, inw = np.zeros(m, np.int32), np.zeros(m, np.int32), np.zeros((m, 4, 4), np.float32), np.zeros(m, np.int32)
+        self.ctx.check(self.lib.vo_svo_get_semidense_world_anchors(self._h, n.value, fid.ctypes.data, idx.ctypes.data, T.ctypes.data, inw.ctypes.data,
+                                                                   C.byref(n)))
+        k = n.value
+        return dict(frame_id=fid[:k], index=idx[:k], T_wk=T[:k], in_window=inw[:k].astype(bool))
+
+    def getSemiDenseWorldReanchorStats(self):
+        """dict(removals, refused_removals, removed, missing, reanchors, vacant) of the world map"""
+        info = _capi.SemiDenseWorldReanchorInfo()
+        self.ctx.check(self.lib.vo_svo_get_semidense_world_reanchor_stats(self._h, C.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in _capi.SemiDenseWorldReanchorInfo._fields_}
 
     def flushSemiDenseWorld(self):
         """Integrates the current keyframe's map now (the end of a sequence); the next keyframe change does not integrate it again."""

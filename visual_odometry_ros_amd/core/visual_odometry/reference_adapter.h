@@ -526,6 +526,8 @@ class StereoVO {
   // sequence, getSemiDenseWorldPoints() the voxels' mean positions seen by at least min_keyframes keyframes
   void setSemiDenseWorld(const vo_semidense_world_params *prm, int source = VO_SEMIDENSE_WORLD_RAW) { impl_.setSemiDenseWorld(prm, source); }
   void flushSemiDenseWorld() { impl_.flushSemiDenseWorld(); }
+  // the world map follows the local BA (vo::StereoVO::setSemiDenseWorldReanchor): min_move in voxels, 0 = any change of a pose
+  void setSemiDenseWorldReanchor(bool on, float min_move = 0.0f) { impl_.setSemiDenseWorldReanchor(on, min_move); }
   PointVec getSemiDenseWorldPoints(int min_count = 1, int min_keyframes = 1) {
     vo::PointVec v;
     impl_.getSemiDenseWorldPoints(v, min_count, min_keyframes);

@@ -342,6 +342,31 @@ class StereoVO {
   void setSemiDenseWorld(const vo_semidense_world_params *prm, int source = VO_SEMIDENSE_WORLD_RAW) {
     ctx_->check(vo_svo_set_semidense_world(svo_, prm, source));
   }
+  // The world map follows the local BA (vo_svo_set_semidense_world_reanchor; include/vo_hip.h, "Semi-dense world map: removal and
+  // re-anchoring"): the maps of the keyframes in the BA's window are retained, and at every keyframe each one whose keyframe has moved
+  // by min_move voxels or more is taken out of the table and put back with the keyframe's current pose. Needs setSemiDenseWorld and
+  // local_ba. Throws while a frame is in flight.
+  void setSemiDenseWorldReanchor(bool on, float min_move = 0.0f) { ctx_->check(vo_svo_set_semidense_world_reanchor(svo_, on ? 1 : 0, min_move)); }
+  vo_semidense_world_reanchor_info getSemiDenseWorldReanchorStats() {
+    vo_semidense_world_reanchor_info info;
+    ctx_->check(vo_svo_get_semidense_world_reanchor_stats(svo_, &info));
+    return info;
+  }
+  // per integrated keyframe, in integration order: its frame id, its index among the keyframes, the pose its map is in the table with
+  // (row-major 4 x 4, 16 floats each) and whether it is still in the window; returns their number
+  int getSemiDenseWorldAnchors(std::vector<int32_t> *frame_id, std::vector<int32_t> *kf_index, std::vector<float> *T_wk,
+                               std::vector<int32_t> *in_window = nullptr) {
+    int n = 0;
+    const int rc = vo_svo_get_semidense_world_anchors(svo_, 0, nullptr, nullptr, nullptr, nullptr, &n);
+    if (rc != VO_ERR_CAPACITY) ctx_->check(rc);  // (room for none: the count is what was asked for)
+    if (frame_id) frame_id->resize((size_t)n);
+    if (kf_index) kf_index->resize((size_t)n);
+    if (T_wk) T_wk->resize((size_t)n * 16);
+    if (in_window) in_window->resize((size_t)n);
+    if (n) ctx_->check(vo_svo_get_semidense_world_anchors(svo_, n, frame_id ? frame_id->data() : nullptr, kf_index ? kf_index->data() : nullptr,
+                                                          T_wk ? T_wk->data() : nullptr, in_window ? in_window->data() : nullptr, &n));
+    return n;
+  }
   // the current keyframe's map into the world map now (the end of a sequence); the next keyframe change does not integrate it again
   void flushSemiDenseWorld() { ctx_->check(vo_svo_semidense_world_flush(svo_)); }
   void clearSemiDenseWorld() { ctx_->check(vo_svo_semidense_world_clear(svo_)); }

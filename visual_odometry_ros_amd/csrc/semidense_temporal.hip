@@ -330,6 +330,9 @@ int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, in
     t.frame_id = frame_id;
     t.n_fused = 0;
     memcpy(t.T_wk, T_wc, sizeof(t.T_wk));
+    t.kf_index = -1;
+    for (const SvoKeyframe &k : s->keyframes)
+      if (k.frame_id == frame_id) t.kf_index = k.global;
   } else {
     float T_cw[16], T_ck[16];
     svo_inv_se3(T_wc, T_cw);  // T_ck = inverseSE3(T_wc) * T_wk, both in float, in svo_mul44's order
@@ -354,6 +357,10 @@ int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, in
   }
   if (s->sdr.on) {  // vo_svo_set_semidense_regularize: behind the launch that wrote the map, on the planes that are current now
     const int rc = vo_svo_semidense_regularize_enqueue(s);
+    if (rc) return rc;
+  }
+  if (is_keyframe && s->sdw.on && s->sdw.ra.on) {  // vo_svo_set_semidense_world_reanchor: the window's maps follow the local BA
+    const int rc = vo_svo_semidense_world_reanchor_pass(s);
     if (rc) return rc;
   }
   VO_CHECK_HIP(c, hipEventRecord(d.done, side));

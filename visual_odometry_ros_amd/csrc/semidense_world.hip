@@ -1,8 +1,9 @@
 // semidense_world.hip — the world-frame voxel map that fuses the keyframes' semi-dense maps (include/vo_hip.h, "Semi-dense world
 // map"): the handle (vo_semidense_world_create / _integrate / _points / _stats / _clear / _destroy) and StereoVO's hook
 // (vo_svo_set_semidense_world, vo_svo_semidense_world_flush, vo_svo_get_semidense_world_points / _stats; the launch is placed by
-// vo_svo_semidense_temporal_enqueue in front of whatever overwrites the outgoing keyframe's map). semidense_world_device.hpp has the
-// kernels.
+// vo_svo_semidense_temporal_enqueue in front of whatever overwrites the outgoing keyframe's map), and the exact removal of an
+// integration and the re-anchoring built on it (vo_semidense_world_remove / _reanchor / _reanchor_stats; "Semi-dense world map:
+// removal and re-anchoring"). semidense_world_device.hpp has the kernels.
 #include "stereo_vo.hpp"
 #include "vo_internal.hpp"
 #include "vo_kernels.hpp"
@@ -32,12 +33,16 @@ __device__ __forceinline__ unsigned long long sdw_cas64(unsigned long long *p, u
 #include "semidense_world_device.hpp"
 
 static_assert(sizeof(SdwSlot) == 64, "a slot is 64 bytes");
+static_assert(sizeof(SdwState) % 8 == 0, "the removal's 64-bit words behind SdwState are aligned");
+#define SDW_STATE_BYTES (sizeof(SdwState) + sizeof(SdwReanchorState))
 
 struct vo_semidense_world {
   vo_ctx *c = nullptr;
   vo_semidense_world_params prm = {};
   SdwSlot *slots = nullptr;
   SdwState *st = nullptr;
+  SdwReanchorState *rs = nullptr;  // the removal's words, behind *st in the same allocation
+  unsigned long long reanchors = 0;  // vo_semidense_world_reanchor calls that enqueued their pair
   unsigned seq = 0;             // the sequence number of the last call, refused ones included
   SdwSlot *scratch = nullptr;   // the extraction's records (grows with the first getter that needs more)
   size_t scratch_cap = 0;
@@ -73,13 +78,14 @@ extern "C" int vo_semidense_world_create(vo_ctx *c, const vo_semidense_world_par
   wm->prm = *prm;
   const size_t bytes = sizeof(SdwSlot) << prm->capacity_log2;
   void *base = nullptr;
-  if (vo_dev_malloc(c, &base, bytes + sizeof(SdwState)) != hipSuccess) {
+  if (vo_dev_malloc(c, &base, bytes + SDW_STATE_BYTES) != hipSuccess) {
     delete wm;
     VO_FAIL(c, VO_ERR_HIP, "semi-dense world map: no device memory for 2^%d slots of 64 bytes", prm->capacity_log2);
   }
   wm->slots = (SdwSlot *)base;
   wm->st = (SdwState *)((char *)base + bytes);
-  if (hipMemsetAsync(base, 0, bytes + sizeof(SdwState), c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
+  wm->rs = (SdwReanchorState *)((char *)base + bytes + sizeof(SdwState));
+  if (hipMemsetAsync(base, 0, bytes + SDW_STATE_BYTES, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
     (void)hipFree(base);
     delete wm;
     VO_FAIL(c, VO_ERR_HIP, "semi-dense world map: the table could not be cleared");
@@ -98,8 +104,9 @@ extern "C" void vo_semidense_world_destroy(vo_semidense_world *wm) {
 
 static int sdw_clear(vo_semidense_world *wm, hipStream_t s) {
   vo_ctx *c = wm->c;
-  VO_CHECK_HIP(c, hipMemsetAsync(wm->slots, 0, (sizeof(SdwSlot) << wm->prm.capacity_log2) + sizeof(SdwState), s));
+  VO_CHECK_HIP(c, hipMemsetAsync(wm->slots, 0, (sizeof(SdwSlot) << wm->prm.capacity_log2) + SDW_STATE_BYTES, s));
   wm->seq = 0;
+  wm->reanchors = 0;
   return VO_OK;
 }
 
@@ -114,9 +121,7 @@ extern "C" int vo_semidense_world_clear(vo_semidense_world *wm) {
 }
 
 // ---- the launch -------------------------------------------------------------------------------------------------------------------
-// On stream s, DEVICE planes throughout; d_key may be null. Every call that reaches the launch takes a sequence number.
-static int sdw_enqueue(vo_semidense_world *wm, hipStream_t s, const float *invd, const float *sigma, const uint8_t *n_obs, const uint8_t *d_key,
-                       int key_stride, int W, int H, const float K[4], const float T_wk[16]) {
+static int sdw_check_launch(vo_semidense_world *wm, const uint8_t *d_key, int key_stride, int W, int H, const float K[4], const float T_wk[16]) {
   vo_ctx *c = wm->c;
   if (W < 1 || H < 1 || W > 65535 || H > 65535 || (long long)W * H > 0x7FFFFFFFll)
     VO_FAIL(c, VO_ERR_SIZE, "semi-dense world map: the map must have 1 .. 65535 pixels a side and fewer than 2^31 in all");
@@ -125,6 +130,16 @@ static int sdw_enqueue(vo_semidense_world *wm, hipStream_t s, const float *invd,
     VO_FAIL(c, VO_ERR_INVALID, "semi-dense world map: fx, fy must be positive, K finite");
   for (int i = 0; i < 12; ++i)
     if (!isfinite(T_wk[i])) VO_FAIL(c, VO_ERR_INVALID, "semi-dense world map: T_wk is not finite");
+  return VO_OK;
+}
+
+// On stream s, DEVICE planes throughout; d_key may be null. Every call that reaches the launch takes a sequence number. remove: the
+// removal kernel instead of the integration.
+static int sdw_enqueue(vo_semidense_world *wm, hipStream_t s, const float *invd, const float *sigma, const uint8_t *n_obs, const uint8_t *d_key,
+                       int key_stride, int W, int H, const float K[4], const float T_wk[16], bool remove = false) {
+  vo_ctx *c = wm->c;
+  const int rc = sdw_check_launch(wm, d_key, key_stride, W, H, K, T_wk);
+  if (rc) return rc;
   SdwArgs a;
   memset(&a, 0, sizeof(a));
   a.invd = invd;
@@ -147,7 +162,12 @@ static int sdw_enqueue(vo_semidense_world *wm, hipStream_t s, const float *invd,
   hipStream_t keep = c->stream;
   c->stream = s;
   vo_prof_begin(c, VO_K_AUX);
-  if (c->dbg[VO_DBG_SDW_FORM] == 1)
+  if (remove) {
+    SdwRemoveArgs ra;
+    ra.a = a;
+    ra.rs = wm->rs;
+    hipLaunchKernelGGL(semidense_world_remove_kernel, dim3(nb), dim3(SDW_NT), 0, s, ra);
+  } else if (c->dbg[VO_DBG_SDW_FORM] == 1)
     hipLaunchKernelGGL(semidense_world_integrate_kernel<false>, dim3(nb), dim3(SDW_NT), 0, s, a);
   else
     hipLaunchKernelGGL(semidense_world_integrate_kernel<true>, dim3(nb), dim3(SDW_NT), 0, s, a);
@@ -157,9 +177,11 @@ static int sdw_enqueue(vo_semidense_world *wm, hipStream_t s, const float *invd,
   return VO_OK;
 }
 
-extern "C" int vo_semidense_world_integrate(vo_semidense_world *wm, const float *invd, const float *sigma, const uint8_t *n_obs,
-                                            const uint8_t *key_plane, int key_stride, int key_on_device, int width, int height, int on_device,
-                                            const float K[4], const float T_wk[16]) {
+// the operator's calls: the planes to the device where they are the host's, then one launch (T_new null), or the removal with T and the
+// integration with T_new behind it; synchronous
+static int sdw_operator(vo_semidense_world *wm, const float *invd, const float *sigma, const uint8_t *n_obs, const uint8_t *key_plane,
+                        int key_stride, int key_on_device, int width, int height, int on_device, const float K[4], const float T_wk[16],
+                        bool remove, const float *T_new) {
   if (!wm || !invd || !sigma || !n_obs || !K || !T_wk || width <= 0 || height <= 0) return VO_ERR_INVALID;
   vo_ctx *c = wm->c;
   if (width > c->cfg.max_width || height > c->cfg.max_height)
@@ -189,17 +211,79 @@ extern "C" int vo_semidense_world_integrate(vo_semidense_world *wm, const float 
     VO_CHECK_HIP(c, hipMemcpyAsync(b->n_obs, n_obs, np, hipMemcpyHostToDevice, s));
     d_invd = b->invd, d_sigma = b->sigma, d_no = b->n_obs;
   }
-  const int rc = sdw_enqueue(wm, s, d_invd, d_sigma, d_no, d_key, d_stride, W, H, K, T_wk);
+  int rc = T_new ? sdw_check_launch(wm, d_key, d_stride, W, H, K, T_new) : VO_OK;  // (both poses are checked before either launch)
+  if (!rc) rc = sdw_enqueue(wm, s, d_invd, d_sigma, d_no, d_key, d_stride, W, H, K, T_wk, remove);
+  if (!rc && T_new) {
+    rc = sdw_enqueue(wm, s, d_invd, d_sigma, d_no, d_key, d_stride, W, H, K, T_new);
+    if (!rc) ++wm->reanchors;
+  }
   VO_CHECK_HIP(c, hipStreamSynchronize(s));  // (the copies read the caller's memory)
   return rc;
 }
 
-// ---- stats and extraction: synchronous on stream s ----------------------------------------------------------------------------------
-static int sdw_stats(vo_semidense_world *wm, hipStream_t s, vo_semidense_world_info *info) {
+extern "C" int vo_semidense_world_integrate(vo_semidense_world *wm, const float *invd, const float *sigma, const uint8_t *n_obs,
+                                            const uint8_t *key_plane, int key_stride, int key_on_device, int width, int height, int on_device,
+                                            const float K[4], const float T_wk[16]) {
+  return sdw_operator(wm, invd, sigma, n_obs, key_plane, key_stride, key_on_device, width, height, on_device, K, T_wk, false, nullptr);
+}
+
+extern "C" int vo_semidense_world_remove(vo_semidense_world *wm, const float *invd, const float *sigma, const uint8_t *n_obs,
+                                         const uint8_t *key_plane, int key_stride, int key_on_device, int width, int height, int on_device,
+                                         const float K[4], const float T_wk[16]) {
+  return sdw_operator(wm, invd, sigma, n_obs, key_plane, key_stride, key_on_device, width, height, on_device, K, T_wk, true, nullptr);
+}
+
+extern "C" int vo_semidense_world_reanchor(vo_semidense_world *wm, const float *invd, const float *sigma, const uint8_t *n_obs,
+                                           const uint8_t *key_plane, int key_stride, int key_on_device, int width, int height, int on_device,
+                                           const float K[4], const float T_old[16], const float T_new[16], int *moved) {
+  if (!T_old || !T_new || !moved) return VO_ERR_INVALID;
+  *moved = 0;
+  if (memcmp(T_old, T_new, 12 * sizeof(float)) == 0) {  // the same bits: no launch, no seq
+    if (!wm || !invd || !sigma || !n_obs || !K || width <= 0 || height <= 0) return VO_ERR_INVALID;
+    return VO_OK;
+  }
+  const int rc = sdw_operator(wm, invd, sigma, n_obs, key_plane, key_stride, key_on_device, width, height, on_device, K, T_old, true, T_new);
+  if (!rc) *moved = 1;
+  return rc;
+}
+
+static int sdw_reanchor_stats(vo_semidense_world *wm, hipStream_t s, vo_semidense_world_reanchor_info *info) {
   vo_ctx *c = wm->c;
-  SdwState st;
-  VO_CHECK_HIP(c, hipMemcpyAsync(&st, wm->st, sizeof(st), hipMemcpyDeviceToHost, s));
+  const size_t n_slots = (size_t)1 << wm->prm.capacity_log2;
+  SdwReanchorState rs;
+  VO_CHECK_HIP(c, hipMemsetAsync(&wm->rs->vacant, 0, sizeof(unsigned), s));
+  hipLaunchKernelGGL(semidense_world_vacant_kernel, dim3((unsigned)(n_slots / SDW_NT)), dim3(SDW_NT), 0, s, wm->slots, n_slots, wm->rs);
+  VO_CHECK_HIP(c, hipGetLastError());
+  VO_CHECK_HIP(c, hipMemcpyAsync(&rs, wm->rs, sizeof(rs), hipMemcpyDeviceToHost, s));
   VO_CHECK_HIP(c, hipStreamSynchronize(s));
+  info->removals = rs.removals;
+  info->refused_removals = rs.refused_removals;
+  info->removed = rs.removed;
+  info->missing = rs.missing;
+  info->reanchors = wm->reanchors;
+  info->vacant = rs.vacant;
+  return VO_OK;
+}
+
+extern "C" int vo_semidense_world_reanchor_stats(vo_semidense_world *wm, vo_semidense_world_reanchor_info *info) {
+  if (!wm || !info) return VO_ERR_INVALID;
+  VO_CHECK_HIP(wm->c, hipSetDevice(wm->c->device));
+  return sdw_reanchor_stats(wm, wm->c->stream, info);
+}
+
+// ---- stats and extraction: synchronous on stream s ----------------------------------------------------------------------------------
+// (refused_removals: the removal's word, which lies behind SdwState and comes with the same copy — StereoVO's getter settles with it)
+static int sdw_stats(vo_semidense_world *wm, hipStream_t s, vo_semidense_world_info *info, unsigned long long *refused_removals = nullptr) {
+  vo_ctx *c = wm->c;
+  struct {
+    SdwState st;
+    SdwReanchorState rs;
+  } both;
+  static_assert(sizeof(both) == SDW_STATE_BYTES, "the two blocks lie back to back");
+  VO_CHECK_HIP(c, hipMemcpyAsync(&both, wm->st, sizeof(both), hipMemcpyDeviceToHost, s));
+  VO_CHECK_HIP(c, hipStreamSynchronize(s));
+  const SdwState &st = both.st;
+  if (refused_removals) *refused_removals = both.rs.refused_removals;
   info->occupied = st.occupied;
   info->capacity = 1ull << wm->prm.capacity_log2;
   info->integrations = st.integrations;
@@ -291,6 +375,81 @@ extern "C" int vo_semidense_world_points(vo_semidense_world *wm, int min_count, 
 // The current keyframe's map — the temporal option's planes, or the regularised copy — into the table, on the side stream behind the
 // launches that wrote it. Called by vo_svo_semidense_temporal_enqueue at the top of a keyframe change, in front of the propagation's
 // scatter and the key plane's copy, and by vo_svo_semidense_world_flush; `done`: the map is marked so that it is not integrated twice.
+struct SdwRing {
+  float *invd, *sigma;
+  uint8_t *n_obs, *key;
+};
+
+static SdwRing svo_sdw_ring(const vo_svo_semidense_world &w, int slot) {
+  char *base = (char *)w.ra.ring + (size_t)slot * w.ra.np_max * 10;
+  SdwRing p;
+  p.invd = (float *)base;
+  p.sigma = (float *)(base + 4 * w.ra.np_max);
+  p.n_obs = (uint8_t *)(base + 8 * w.ra.np_max);
+  p.key = p.n_obs + w.ra.np_max;
+  return p;
+}
+
+static bool svo_sdw_in_window(const vo_svo *s, int kf_index) {
+  for (const SvoKeyframe &k : s->keyframes)
+    if (k.global == kf_index) return true;
+  return false;
+}
+
+// the live anchors whose keyframe has left the window move to the frozen record, in order; their ring places are free
+static void svo_sdw_freeze(vo_svo *s) {
+  vo_svo_semidense_world &w = s->sdw;
+  size_t keep = 0;
+  for (size_t i = 0; i < w.ra.live.size(); ++i) {
+    if (svo_sdw_in_window(s, w.ra.live[i].kf_index)) {
+      if (keep != i) w.ra.live[keep] = w.ra.live[i];
+      ++keep;
+    } else {
+      w.ra.live[i].slot = -1;
+      w.ra.frozen.push_back(w.ra.live[i]);
+    }
+  }
+  w.ra.live.resize(keep);
+}
+
+// (vo_svo_set_semidense_world_reanchor) what is about to be integrated — the planes and the key plane of the current keyframe's map —
+// into a free place of the ring, device to device on the side stream, and the anchor: the keyframe and the pose it goes in with
+static int svo_sdw_retain(vo_svo *s, const float *invd, const float *sigma, const uint8_t *n_obs) {
+  vo_ctx *c = s->c;
+  vo_svo_semidense_world &w = s->sdw;
+  const vo_svo_semidense_temporal &t = s->sdt;
+  if (!w.ra.ring) return VO_OK;
+  svo_sdw_freeze(s);
+  unsigned used = 0;
+  for (const vo_svo_semidense_world::Anchor &an : w.ra.live) used |= 1u << an.slot;
+  vo_svo_semidense_world::Anchor an;
+  an.frame_id = t.frame_id;
+  an.kf_index = t.kf_index;
+  an.order = w.ra.n_anchors++;
+  an.w = t.w;
+  an.h = t.h;
+  memcpy(an.T_wk, t.T_wk, sizeof(an.T_wk));
+  an.slot = -1;
+  if (t.kf_index < 0 || !svo_sdw_in_window(s, t.kf_index)) {  // (a window of one keyframe: the outgoing one has left it already)
+    w.ra.frozen.push_back(an);
+    return VO_OK;
+  }
+  const size_t np = (size_t)t.w * (size_t)t.h;
+  if (np > w.ra.np_max) VO_FAIL(c, VO_ERR_SIZE, "world map re-anchoring: a %d x %d map exceeds vo_config.max_width x max_height", t.w, t.h);
+  for (int k = 0; k < w.ra.n_slots && an.slot < 0; ++k)
+    if (!(used & (1u << k))) an.slot = k;
+  // (cannot happen: the window holds kf_window keyframes at most, and only keyframes of the window keep a place)
+  if (an.slot < 0) VO_FAIL(c, VO_ERR_CAPACITY, "world map re-anchoring: no free place among %d for keyframe %d", w.ra.n_slots, t.kf_index);
+  const SdwRing p = svo_sdw_ring(w, an.slot);
+  hipStream_t side = c->stream2;
+  VO_CHECK_HIP(c, hipMemcpyAsync(p.invd, invd, np * sizeof(float), hipMemcpyDeviceToDevice, side));
+  VO_CHECK_HIP(c, hipMemcpyAsync(p.sigma, sigma, np * sizeof(float), hipMemcpyDeviceToDevice, side));
+  VO_CHECK_HIP(c, hipMemcpyAsync(p.n_obs, n_obs, np, hipMemcpyDeviceToDevice, side));
+  VO_CHECK_HIP(c, hipMemcpyAsync(p.key, t.buf.key, np, hipMemcpyDeviceToDevice, side));
+  w.ra.live.push_back(an);
+  return VO_OK;
+}
+
 int vo_svo_semidense_world_enqueue(vo_svo *s) {
   vo_svo_semidense_world &w = s->sdw;
   const vo_svo_semidense_temporal &t = s->sdt;
@@ -302,15 +461,65 @@ int vo_svo_semidense_world_enqueue(vo_svo *s) {
     if (!r.on || !r.have || r.frame_id != t.frame_id) return VO_OK;  // no regularised planes of this keyframe: nothing to integrate
     invd = r.buf.invd, sigma = r.buf.sigma, n_obs = r.buf.n_obs;
   }
-  const int rc = sdw_enqueue(w.wm, s->c->stream2, invd, sigma, n_obs, t.buf.key, t.w, t.w, t.h, s->prm.frame.Kl, t.T_wk);
+  int rc = w.ra.on ? svo_sdw_retain(s, invd, sigma, n_obs) : VO_OK;  // (in front of everything that overwrites the outgoing map)
+  if (rc) return rc;
+  rc = sdw_enqueue(w.wm, s->c->stream2, invd, sigma, n_obs, t.buf.key, t.w, t.w, t.h, s->prm.frame.Kl, t.T_wk);
   if (rc) return rc;
   w.done = true;
   return VO_OK;
 }
 
+// the local BA has written its poses back to kf_all: every retained map whose keyframe is still in the window moves from the pose it
+// is in the table with to the keyframe's current one, where the two differ in bits and by min_move voxels at least (decided here, in
+// double: move = max_r |dt_r| + z_max max_r sum_c |dR_rc|). On the side stream behind the frame's integration; nothing waits. The
+// device decides whether a pair is refused, so the pair is logged with the pose it replaces (svo_sdw_settle).
+int vo_svo_semidense_world_reanchor_pass(vo_svo *s) {
+  vo_svo_semidense_world &w = s->sdw;
+  if (!w.on || !w.ra.on || !w.ra.ring) return VO_OK;
+  const double bound = w.ra.min_move * (double)w.wm->prm.voxel, z_max = (double)w.wm->prm.z_max;
+  svo_sdw_freeze(s);  // (a keyframe that has left the window keeps the pose of the last pass it was in: nothing moves it any more)
+  for (vo_svo_semidense_world::Anchor &an : w.ra.live) {
+    const float *Tn = s->kf_all[an.kf_index].T_wc;
+    if (memcmp(an.T_wk, Tn, 12 * sizeof(float)) == 0) continue;
+    double dt = 0.0, dr = 0.0;
+    for (int r = 0; r < 3; ++r) {
+      double row = 0.0;
+      for (int k = 0; k < 3; ++k) row += fabs((double)Tn[4 * r + k] - (double)an.T_wk[4 * r + k]);
+      dr = std::max(dr, row);
+      dt = std::max(dt, fabs((double)Tn[4 * r + 3] - (double)an.T_wk[4 * r + 3]));
+    }
+    if (!(dt + z_max * dr >= bound)) continue;
+    const SdwRing p = svo_sdw_ring(w, an.slot);
+    int rc = sdw_check_launch(w.wm, p.key, an.w, an.w, an.h, s->prm.frame.Kl, Tn);  // (both poses are checked before either launch)
+    if (!rc) rc = sdw_enqueue(w.wm, s->c->stream2, p.invd, p.sigma, p.n_obs, p.key, an.w, an.w, an.h, s->prm.frame.Kl, an.T_wk, true);
+    if (!rc) rc = sdw_enqueue(w.wm, s->c->stream2, p.invd, p.sigma, p.n_obs, p.key, an.w, an.w, an.h, s->prm.frame.Kl, Tn);
+    if (rc) return rc;
+    ++w.wm->reanchors;
+    vo_svo_semidense_world::Pair pr;
+    pr.frame_id = an.frame_id;
+    memcpy(pr.T_prev, an.T_wk, sizeof(pr.T_prev));
+    w.ra.log.push_back(pr);
+    memcpy(an.T_wk, Tn, sizeof(an.T_wk));
+  }
+  return VO_OK;
+}
+
 void vo_svo_semidense_world_free(vo_svo *s) {
+  if (s->sdw.ra.ring) {
+    (void)hipSetDevice(s->c->device);
+    (void)hipFree(s->sdw.ra.ring);
+  }
   vo_semidense_world_destroy(s->sdw.wm);
   s->sdw = vo_svo_semidense_world();
+}
+
+// the table has been cleared: no map is in it
+static void svo_sdw_forget(vo_svo_semidense_world &w) {
+  w.ra.live.clear();
+  w.ra.frozen.clear();
+  w.ra.log.clear();
+  w.ra.n_anchors = 0;
+  w.ra.refused_seen = 0;
 }
 
 extern "C" int vo_svo_set_semidense_world(vo_svo *s, const vo_semidense_world_params *prm, int source) {
@@ -343,10 +552,31 @@ extern "C" int vo_svo_set_semidense_world(vo_svo *s, const vo_semidense_world_pa
     if (rc) return rc;
     w.wm->prm = *prm;
     w.done = false;
+    svo_sdw_forget(w);
   }
   w.source = source;
   w.on = true;
   return VO_OK;
+}
+
+// The pairs the passes have enqueued since the counters were last read: a refused pair left its map where it was, so its anchor takes
+// the replaced pose back. `occupied` never falls and the driver's maps have one size, so once a launch is refused every later one is:
+// the refused pairs are the LAST ones of the log, and a pair enqueued on top of a refused one was refused with it. refused_removals:
+// the device's word, as the getter that calls this has just fetched it with its statistics (no copy or wait of its own).
+static void svo_sdw_settle(vo_svo *s, unsigned long long refused_removals) {
+  vo_svo_semidense_world &w = s->sdw;
+  const unsigned long long grew = refused_removals - w.ra.refused_seen;
+  w.ra.refused_seen = refused_removals;
+  for (size_t k = 0; k < grew && k < w.ra.log.size(); ++k) {
+    const vo_svo_semidense_world::Pair &p = w.ra.log[w.ra.log.size() - 1 - k];
+    vo_svo_semidense_world::Anchor *an = nullptr;  // (by frame id: the anchor may have been frozen since)
+    for (auto &a : w.ra.live)
+      if (a.frame_id == p.frame_id) an = &a;
+    for (size_t q = w.ra.frozen.size(); !an && q-- > 0;)
+      if (w.ra.frozen[q].frame_id == p.frame_id) an = &w.ra.frozen[q];
+    if (an) memcpy(an->T_wk, p.T_prev, sizeof(p.T_prev));
+  }
+  w.ra.log.clear();
 }
 
 static int svo_sdw_ready(vo_svo *s, const char *who) {
@@ -378,14 +608,18 @@ extern "C" int vo_svo_semidense_world_clear(vo_svo *s) {
   rc = vo_semidense_world_clear(s->sdw.wm);
   if (rc) return rc;
   s->sdw.done = false;
+  svo_sdw_forget(s->sdw);
   return VO_OK;
 }
 
 extern "C" int vo_svo_get_semidense_world_stats(vo_svo *s, vo_semidense_world_info *info) {
   if (!s || !info) return VO_ERR_INVALID;
-  const int rc = svo_sdw_ready(s, "vo_svo_get_semidense_world_stats");
+  int rc = svo_sdw_ready(s, "vo_svo_get_semidense_world_stats");
   if (rc) return rc;
-  return sdw_stats(s->sdw.wm, s->c->stream, info);
+  unsigned long long refused_removals = 0;
+  rc = sdw_stats(s->sdw.wm, s->c->stream, info, &refused_removals);
+  if (!rc) svo_sdw_settle(s, refused_removals);
+  return rc;
 }
 
 extern "C" int vo_svo_get_semidense_world_points(vo_svo *s, int min_count, int min_keyframes, int cap, int32_t *index, float *xyz,
@@ -394,4 +628,71 @@ extern "C" int vo_svo_get_semidense_world_points(vo_svo *s, int min_count, int m
   const int rc = svo_sdw_ready(s, "vo_svo_get_semidense_world_points");
   if (rc) return rc;
   return sdw_points(s->sdw.wm, s->c->stream, min_count, min_keyframes, cap, index, xyz, weight, count, keyframes, grey, nullptr, n);
+}
+
+// ---- vo_svo_set_semidense_world_reanchor ----------------------------------------------------------------------------
+extern "C" int vo_svo_set_semidense_world_reanchor(vo_svo *s, int on, float min_move) {
+  if (!s) return VO_ERR_INVALID;
+  vo_ctx *c = s->c;
+  if (s->pending) VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world_reanchor: a frame is in flight: call vo_svo_result first");
+  if (s->mono) VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world_reanchor: a stereo driver only");
+  vo_svo_semidense_world &w = s->sdw;
+  if (!on) {
+    w.ra.on = false;
+    return VO_OK;
+  }
+  if (!w.on || !w.wm) VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world_reanchor: needs the world map: vo_svo_set_semidense_world first");
+  if (!s->prm.local_ba) VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world_reanchor: needs vo_svo_params.local_ba: nothing else moves a keyframe");
+  if (!(min_move >= 0.0f) || !isfinite(min_move)) VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world_reanchor: min_move must be >= 0 and finite");
+  if (!w.ra.ring) {  // the option's only allocation, at the first enable: a place per keyframe of the window
+    if (s->prm.kf_window < 1 || s->prm.kf_window > 32) VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world_reanchor: a window of 1 .. 32 keyframes");
+    VO_CHECK_HIP(c, hipSetDevice(c->device));
+    const size_t np_max = ((size_t)c->cfg.max_width * (size_t)c->cfg.max_height + 63) / 64 * 64;
+    if (vo_dev_malloc(c, &w.ra.ring, (size_t)s->prm.kf_window * np_max * 10) != hipSuccess) {
+      w.ra.ring = nullptr;
+      VO_FAIL(c, VO_ERR_HIP, "vo_svo_set_semidense_world_reanchor: no device memory for %d retained maps", s->prm.kf_window);
+    }
+    w.ra.n_slots = s->prm.kf_window;
+    w.ra.np_max = np_max;
+  }
+  w.ra.min_move = (double)min_move;
+  w.ra.on = true;
+  return VO_OK;
+}
+
+extern "C" int vo_svo_get_semidense_world_anchors(vo_svo *s, int cap, int32_t *frame_id, int32_t *kf_index, float *T_wk, int32_t *in_window,
+                                                  int *n) {
+  if (!s || !n || cap < 0) return VO_ERR_INVALID;
+  int rc = svo_sdw_ready(s, "vo_svo_get_semidense_world_anchors");
+  if (rc) return rc;
+  vo_svo_semidense_world &w = s->sdw;
+  if (!w.ra.log.empty()) {  // (pairs have been enqueued since the last look: the counters, as the statistics getter fetches them)
+    vo_semidense_world_info info;
+    unsigned long long refused_removals = 0;
+    rc = sdw_stats(w.wm, s->c->stream, &info, &refused_removals);
+    if (rc) return rc;
+    svo_sdw_settle(s, refused_removals);
+  }
+  // either list is in integration order: merged by `order` (an anchor integrated outside the window, which only a window of one
+  // keyframe gives, goes to the frozen record at once, while older anchors may still be live)
+  const size_t nf = w.ra.frozen.size(), nl = w.ra.live.size(), total = nf + nl;
+  *n = (int)total;
+  for (size_t i = 0, f = 0, l = 0; i < total && i < (size_t)cap; ++i) {
+    const bool take_frozen = f < nf && (l >= nl || w.ra.frozen[f].order < w.ra.live[l].order);
+    const vo_svo_semidense_world::Anchor &a = take_frozen ? w.ra.frozen[f++] : w.ra.live[l++];
+    if (frame_id) frame_id[i] = a.frame_id;
+    if (kf_index) kf_index[i] = a.kf_index;
+    if (T_wk) memcpy(T_wk + 16 * i, a.T_wk, sizeof(a.T_wk));
+    if (in_window) in_window[i] = a.kf_index >= 0 && svo_sdw_in_window(s, a.kf_index) ? 1 : 0;
+  }
+  return total > (size_t)cap ? VO_ERR_CAPACITY : VO_OK;
+}
+
+extern "C" int vo_svo_get_semidense_world_reanchor_stats(vo_svo *s, vo_semidense_world_reanchor_info *info) {
+  if (!s || !info) return VO_ERR_INVALID;
+  int rc = svo_sdw_ready(s, "vo_svo_get_semidense_world_reanchor_stats");
+  if (rc) return rc;
+  rc = sdw_reanchor_stats(s->sdw.wm, s->c->stream, info);
+  if (!rc) svo_sdw_settle(s, info->refused_removals);
+  return rc;
 }

@@ -23,6 +23,14 @@
 //   semidense_world_extract_kernel   one thread per slot; the slots that pass min_count / min_keyframes are appended to `out` (one LDS
 //                      rank per thread, one global atomicAdd per workgroup) in whatever order they come: the host sorts by key. The
 //                      count runs on past `cap`; nothing is written there.
+//   semidense_world_remove_kernel   one launch per removal (include/vo_hip.h, "Semi-dense world map: removal and re-anchoring"; DESIGN.md
+//                      §25), the integration's geometry and its pre-aggregated shape: the same refusal test on the same word, the same
+//                      list, the same points (sdw_point), combined in the same LDS hash; then every occupied LDS slot, and every point
+//                      that found none, LOOKS its voxel UP — the key words are only read, never compare-and-swapped — and adds the two's
+//                      complement of its sums. A probe that meets an empty slot ends: the points are counted as missing. `occupied` and
+//                      `claimed` are not written. The ticket's last workgroup counts the removal and zeroes the ticket; the words are a
+//                      block of their own (SdwReanchorState), so that SdwState keeps its layout.
+//   semidense_world_vacant_kernel   one thread per slot; counts the slots with a key and cnt == 0 (one global atomicAdd per workgroup).
 //
 // The includer provides __global__, __shared__, __syncthreads, the built-in indices, atomicAdd / atomicMax on 32- and 64-bit words in
 // global memory and LDS, sdw_cas64(p, compare, value) (returns the old word; global and LDS) and the agent-scope spellings SDW_DRAIN,
@@ -48,6 +56,7 @@
 #define SDW_LPROBE 8    // LDS probes before a point goes to the global table itself
 #define SDW_LDS_BYTES_SIMPLE (SDW_BLOCK * 2 + 6 * 4)
 #define SDW_LDS_BYTES_AGG (SDW_BLOCK * 2 + 6 * 4 + SDW_LH * (6 * 8 + 4))
+#define SDW_LDS_BYTES_REMOVE (SDW_BLOCK * 2 + 4 * 4 + SDW_LH * (6 * 8 + 4))
 #define SDW_FLT_MAX 3.4028235e38f
 #define SDW_RANGE 1048576.0f                 // 2^20 voxels either way per axis
 #define SDW_HASH_MUL 0x9E3779B97F4A7C15ull   // home slot = (key * this) >> (64 - capacity_log2)
@@ -254,4 +263,133 @@ __global__ __launch_bounds__(SDW_NT) void semidense_world_extract_kernel(SdwExtr
   if (tid == 0 && s_n) s_base = atomicAdd(&a.st->n_extract, s_n);
   __syncthreads();
   if (take && (size_t)s_base + r < (size_t)a.cap) a.out[s_base + r] = a.slots[i];
+}
+
+// ---- removal ------------------------------------------------------------------------------------------------------------
+// the removal's words on the device, behind SdwState
+struct SdwReanchorState {
+  unsigned ticket;  // (0 between launches)
+  unsigned removals, refused_removals;
+  unsigned vacant;  // the count launch's result: zeroed in front of it
+  sdw_u64 removed, missing;
+};
+
+struct SdwRemoveArgs {
+  SdwArgs a;  // the integration's, with the removal's own seq
+  SdwReanchorState *rs;
+};
+
+// sums of one voxel out of the global table; returns cnt where the voxel was found, 0 where the probe met an empty slot
+__device__ static inline unsigned sdw_uncommit(const SdwArgs &a, sdw_u64 key, sdw_u64 sw, sdw_u64 sx, sdw_u64 sy, sdw_u64 sz, sdw_u64 sg,
+                                               unsigned cnt) {
+  const size_t mask = ((size_t)1 << a.capacity_log2) - 1;
+  size_t h = (size_t)((key * SDW_HASH_MUL) >> (64 - a.capacity_log2));
+  for (size_t n = 0; n <= mask; ++n, h = (h + 1) & mask) {
+    SdwSlot *s = a.slots + h;
+    const sdw_u64 k = *(const volatile sdw_u64 *)&s->key;  // (no launch that writes a key runs next to this one)
+    if (k == 0ull) return 0u;
+    if (k != key) continue;
+    atomicAdd(&s->sw, 0ull - sw);
+    atomicAdd(&s->sx, 0ull - sx);
+    atomicAdd(&s->sy, 0ull - sy);
+    atomicAdd(&s->sz, 0ull - sz);
+    if (sg) atomicAdd(&s->sg, 0ull - sg);
+    atomicAdd(&s->cnt, 0u - cnt);
+    if (atomicMax(&s->last_seq, a.seq) < a.seq) atomicAdd(&s->kf_cnt, 0u - 1u);
+    return cnt;
+  }
+  return 0u;
+}
+
+__global__ __launch_bounds__(SDW_NT) void semidense_world_remove_kernel(SdwRemoveArgs ra) {
+  __shared__ uint16_t s_list[SDW_BLOCK];  // the block's raster offsets that are entries
+  __shared__ int s_n;
+  __shared__ unsigned s_cnt[2];  // removed, missing
+  __shared__ int s_last;
+  __shared__ sdw_u64 s_key[SDW_LH], s_sum[SDW_LH * 5];
+  __shared__ unsigned s_c[SDW_LH];
+  const SdwArgs &a = ra.a;
+  const int tid = (int)threadIdx.x;
+  const size_t np = (size_t)a.W * (size_t)a.H;
+  // all or nothing: the integration's own test on the same word, which no removal writes
+  if ((sdw_u64)a.st->occupied + (sdw_u64)np > (((sdw_u64)1 << a.capacity_log2) >> 1)) {
+    if (blockIdx.x == 0 && tid == 0) atomicAdd(&ra.rs->refused_removals, 1u);
+    return;
+  }
+  if (tid == 0) s_n = 0;
+  if (tid < 2) s_cnt[tid] = 0;
+  for (int k = tid; k < SDW_LH; k += SDW_NT) {
+    s_key[k] = 0ull;
+    s_c[k] = 0;
+    for (int j = 0; j < 5; ++j) s_sum[5 * k + j] = 0ull;
+  }
+  __syncthreads();
+  const size_t base = (size_t)blockIdx.x * SDW_BLOCK;
+  for (int k = tid; k < SDW_BLOCK; k += SDW_NT) {
+    const size_t i = base + (size_t)k;
+    if (i >= np) break;
+    const int no = (int)a.n_obs[i];
+    const float iv = a.invd[i], sg = a.sigma[i];
+    if (no >= 1 && sg > 0.0f && sg <= SDW_FLT_MAX && iv > 0.0f && iv <= SDW_FLT_MAX) s_list[atomicAdd(&s_n, 1)] = (uint16_t)k;
+  }
+  __syncthreads();
+  const int n_list = s_n;
+  unsigned n_rem = 0, n_miss = 0;
+  for (int k = tid; k < n_list; k += SDW_NT) {
+    SdwPoint p;
+    if (sdw_point(a, (int)(base + (size_t)s_list[k]), &p) != 1) continue;
+    const sdw_u64 wq = p.wq;
+    bool done = false;
+    unsigned h = (unsigned)((p.key * SDW_HASH_MUL) >> 40) & (SDW_LH - 1);
+    for (int t = 0; t < SDW_LPROBE && !done; ++t, h = (h + 1) & (SDW_LH - 1)) {
+      const sdw_u64 old = sdw_cas64(&s_key[h], 0ull, p.key);
+      if (old != 0ull && old != p.key) continue;
+      atomicAdd(&s_sum[5 * h], wq);
+      atomicAdd(&s_sum[5 * h + 1], wq * p.q[0]);
+      atomicAdd(&s_sum[5 * h + 2], wq * p.q[1]);
+      atomicAdd(&s_sum[5 * h + 3], wq * p.q[2]);
+      atomicAdd(&s_sum[5 * h + 4], wq * p.grey);
+      atomicAdd(&s_c[h], 1u);
+      done = true;
+    }
+    if (!done) {
+      const unsigned r = sdw_uncommit(a, p.key, wq, wq * p.q[0], wq * p.q[1], wq * p.q[2], wq * p.grey, 1u);
+      n_rem += r;
+      n_miss += 1u - r;
+    }
+  }
+  __syncthreads();
+  for (int k = tid; k < SDW_LH; k += SDW_NT)
+    if (s_key[k] != 0ull) {
+      const unsigned r = sdw_uncommit(a, s_key[k], s_sum[5 * k], s_sum[5 * k + 1], s_sum[5 * k + 2], s_sum[5 * k + 3], s_sum[5 * k + 4], s_c[k]);
+      n_rem += r;
+      n_miss += s_c[k] - r;
+    }
+  if (n_rem) atomicAdd(&s_cnt[0], n_rem);
+  if (n_miss) atomicAdd(&s_cnt[1], n_miss);
+  // ---- the ticket: the last workgroup counts the removal ----------------------------------------------------------------------------
+  SDW_DRAIN();      // every wavefront: its atomics have left ...
+  __syncthreads();  // ... before thread 0 adds the workgroup's counts and takes its ticket
+  if (tid == 0) {
+    if (s_cnt[0]) atomicAdd(&ra.rs->removed, (sdw_u64)s_cnt[0]);
+    if (s_cnt[1]) atomicAdd(&ra.rs->missing, (sdw_u64)s_cnt[1]);
+    SDW_FENCE_RELEASE();
+    s_last = (SDW_ATOMIC_ADD_AGENT(&ra.rs->ticket, 1u) == gridDim.x - 1u) ? 1 : 0;
+    if (s_last) {
+      SDW_FENCE_ACQUIRE();
+      ra.rs->removals = ra.rs->removals + 1u;
+      SDW_ST_AGENT(&ra.rs->ticket, 0u);
+    }
+  }
+}
+
+__global__ __launch_bounds__(SDW_NT) void semidense_world_vacant_kernel(const SdwSlot *slots, size_t n_slots, SdwReanchorState *rs) {
+  __shared__ unsigned s_n;
+  const int tid = (int)threadIdx.x;
+  if (tid == 0) s_n = 0;
+  __syncthreads();
+  const size_t i = (size_t)blockIdx.x * SDW_NT + (size_t)tid;
+  if (i < n_slots && slots[i].key != 0ull && slots[i].cnt == 0u) atomicAdd(&s_n, 1u);
+  __syncthreads();
+  if (tid == 0 && s_n) atomicAdd(&rs->vacant, s_n);
 }

@@ -39,6 +39,7 @@ struct vo_svo_semidense_temporal {
   vo_semidense_temporal_params prm = {};
   vo_sdt_buffers buf;
   int w = 0, h = 0, frame_id = -1, n_fused = 0;
+  int kf_index = -1;  // the keyframe's index among all keyframes of the stream (kf_all)
   float T_wk[16] = {};
 };
 
@@ -71,6 +72,33 @@ struct vo_svo_semidense_world {
   bool on = false, done = false;
   int source = 0;
   struct vo_semidense_world *wm = nullptr;
+  // vo_svo_set_semidense_world_reanchor: the planes of every map integrated while its keyframe sits in the local BA's
+  // window are kept in a ring on the device, so that the map can be taken out of the table and put back where the BA moves the
+  // keyframe. An anchor per integrated keyframe: `live` those whose keyframe is in the window (kf_window at most, each with a ring
+  // place; what the pass and the retaining walk), `frozen` the record of those that have left it (slot -1; 88 bytes per keyframe of
+  // the stream, like kf_all; only the anchors getter reads it). Each list is in integration order (`order`); the getter merges them.
+  // log: the pairs enqueued since the counters were last read, with the pose each replaced — a refused pair (the device decides) is
+  // taken back then.
+  struct Anchor {
+    int frame_id, kf_index, slot, w, h;
+    int order;       // its place among the integrations since the table was last cleared
+    float T_wk[16];  // the pose the map is in the table with ("applied")
+  };
+  struct Pair {
+    int frame_id;  // the anchor's
+    float T_prev[16];
+  };
+  struct {
+    bool on = false;
+    double min_move = 0.0;  // [voxels]
+    void *ring = nullptr;   // n_slots x (invd f32, sigma f32, n_obs u8, key u8) at max_width x max_height
+    int n_slots = 0;
+    size_t np_max = 0;
+    std::vector<Anchor> live, frozen;
+    std::vector<Pair> log;
+    unsigned long long refused_seen = 0;  // refused_removals when the log was last settled
+    int n_anchors = 0;                    // anchors recorded since the table was last cleared
+  } ra;
 };
 
 // vo_svo_set_semidense_align (semidense_align.hip): at every frame that is not a keyframe the frame's left image is aligned against
@@ -177,6 +205,9 @@ int vo_svo_semidense_regularize_enqueue(vo_svo *s);
 void vo_svo_semidense_regularize_free(vo_svo *s);
 // semidense_world.hip: the current keyframe's map into the table, on the side stream, unless it is there already
 int vo_svo_semidense_world_enqueue(vo_svo *s);
+// (vo_svo_set_semidense_world_reanchor) behind a keyframe frame's integration, on the side stream: the window's maps follow the poses
+// the local BA has just written back
+int vo_svo_semidense_world_reanchor_pass(vo_svo *s);
 void vo_svo_semidense_world_free(vo_svo *s);
 // semidense_align.hip: on the side stream (c->stream points at it) in front of a non-keyframe frame's temporal launch
 int vo_svo_semidense_align_enqueue(vo_svo *s, int slot_l, int frame_id, const float T_ck[16]);
