@@ -22,7 +22,10 @@ the odometry's pose, fused with the new static result) instead of being seeded a
 keyframes observed. --semidense-world FILE.ply: with --semidense-temporal, every keyframe's map is fused into one world-frame voxel
 map when the next keyframe replaces it (the last one at the end); FILE.ply has x y z grey count keyframes per voxel
 (--semidense-voxel V: the voxel's edge, default 0.1 m; --semidense-world-min-keyframes N: only voxels N keyframes reached;
---semidense-world-reanchor [MIN_MOVE]: the map follows the local bundle adjustment, so that it agrees with the keyframe poses).
+--semidense-world-reanchor [MIN_MOVE]: the map follows the local bundle adjustment, so that it agrees with the keyframe poses;
+--semidense-world-carve [MARGIN]: every integration is followed by a free-space carve, FILE.ply gets a `free` property behind
+`keyframes` — the number of later rays that passed through the voxel — and --semidense-world-max-free NUM DEN writes only the voxels
+with free * DEN <= count * NUM).
 --semidense-regularize: with --semidense-temporal, a regularised copy of the map is kept next to it (entries their
 neighbours contradict removed, high-gradient holes whose neighbours agree filled, values smoothed) and written as
 `semidense_regularized_<keyframe's frame id>.ply` wherever the fused file is written; its filled pixels have one observation, so N
@@ -108,6 +111,8 @@ def semidense_options(args):
             raise SystemExit("--semidense-world / --semidense-voxel / --semidense-world-min-keyframes need --semidense DIR")
         if args.semidense_world_reanchor is not None:
             raise SystemExit("--semidense-world-reanchor needs --semidense DIR")
+        if args.semidense_world_carve is not None or args.semidense_world_max_free is not None:
+            raise SystemExit("--semidense-world-carve / --semidense-world-max-free need --semidense DIR")
         return {}
     if args.semidense_world and not args.semidense_temporal:
         raise SystemExit("--semidense-world needs --semidense-temporal")
@@ -115,6 +120,10 @@ def semidense_options(args):
         raise SystemExit("--semidense-voxel / --semidense-world-min-keyframes need --semidense-world FILE.ply")
     if args.semidense_world_reanchor is not None and (not args.semidense_world or not args.semidense_world_reanchor >= 0):
         raise SystemExit("--semidense-world-reanchor [MIN_MOVE]: voxels, >= 0, with --semidense-world FILE.ply")
+    if args.semidense_world_carve is not None and (not args.semidense_world or not args.semidense_world_carve >= 1):
+        raise SystemExit("--semidense-world-carve [MARGIN]: voxels, >= 1, with --semidense-world FILE.ply")
+    if args.semidense_world_max_free is not None and (args.semidense_world_carve is None or min(args.semidense_world_max_free) < 0):
+        raise SystemExit("--semidense-world-max-free NUM DEN: both >= 0, with --semidense-world-carve")
     if args.semidense_voxel is not None and not args.semidense_voxel > 0:
         raise SystemExit("--semidense-voxel V: metres, > 0")
     if args.semidense_world_min_keyframes is not None and args.semidense_world_min_keyframes < 1:
@@ -150,6 +159,8 @@ def semidense_options(args):
         if args.semidense_world_reanchor is not None:
             sd["world"] = dict({} if sd["world"] is True else sd["world"],
                                reanchor=True if args.semidense_world_reanchor == 0 else {"min_move": args.semidense_world_reanchor})
+        if args.semidense_world_carve is not None:
+            sd["world"] = dict({} if sd["world"] is True else sd["world"], carve={"margin": args.semidense_world_carve})
     if args.semidense_align:
         sd["align"] = True
         if args.semidense_align_levels is not None or args.semidense_align_start is not None:
@@ -182,12 +193,14 @@ def write_ply(path, xyz, sigma_invd):
 
 
 def write_world_ply(path, w):
-    """one ASCII PLY of a world map (a SemiDenseWorldPoints): x y z, grey, the points and the keyframes per voxel"""
+    """one ASCII PLY of a world map (a SemiDenseWorldPoints): x y z, grey, the points and the keyframes per voxel; of a
+    SemiDenseWorldFreePoints (--semidense-world-carve) also the free count"""
+    free = getattr(w, "free", None)
     with open(path, "w") as f:
         f.write("ply\nformat ascii 1.0\n" + f"element vertex {len(w.xyz)}\n" + "property float x\nproperty float y\nproperty float z\n"
-                "property uchar grey\nproperty uint count\nproperty uint keyframes\nend_header\n")
-        for (x, y, z), g, c, k in zip(w.xyz, w.grey, w.count, w.keyframes):
-            f.write(f"{x:.6g} {y:.6g} {z:.6g} {int(g)} {int(c)} {int(k)}\n")
+                "property uchar grey\nproperty uint count\nproperty uint keyframes\n" + ("" if free is None else "property uint free\n") + "end_header\n")
+        for i, ((x, y, z), g, c, k) in enumerate(zip(w.xyz, w.grey, w.count, w.keyframes)):
+            f.write(f"{x:.6g} {y:.6g} {z:.6g} {int(g)} {int(c)} {int(k)}" + ("" if free is None else f" {int(free[i])}") + "\n")
 
 
 def parse_args(argv=None):
@@ -234,6 +247,11 @@ def parse_args(argv=None):
     ap.add_argument("--semidense-world-reanchor", type=float, nargs="?", const=0.0, default=None, metavar="MIN_MOVE",
                     help="--semidense-world: the map follows the local BA: a keyframe's map is re-anchored where the BA moves the keyframe "
                          "(by MIN_MOVE voxels or more; default: any change)")
+    ap.add_argument("--semidense-world-carve", type=float, nargs="?", const=2.0, default=None, metavar="MARGIN",
+                    help="--semidense-world: free-space carving: every integration is followed by a march of the map's rays through the "
+                         "table, to MARGIN voxels (default 2) in front of their surface; FILE.ply gets a `free` property")
+    ap.add_argument("--semidense-world-max-free", type=int, nargs=2, default=None, metavar=("NUM", "DEN"),
+                    help="--semidense-world-carve: write only the voxels with free * DEN <= count * NUM")
     ap.add_argument("--semidense-align", default=None, metavar="FILE",
                     help="--semidense-temporal: align every later frame's left image against the keyframe's map; one line per frame into FILE")
     ap.add_argument("--semidense-align-levels", type=int, default=None, metavar="N",
@@ -314,11 +332,15 @@ def main():
         write_fused()
     if args.semidense_world:
         svo.flushSemiDenseWorld()  # (the last keyframe's map: no later keyframe replaces it)
-        wm = svo.getSemiDenseWorld(min_keyframes=args.semidense_world_min_keyframes or 1)
+        max_free = None if args.semidense_world_carve is None else tuple(args.semidense_world_max_free or (0, 0))
+        wm = svo.getSemiDenseWorld(min_keyframes=args.semidense_world_min_keyframes or 1, max_free=max_free)
         write_world_ply(args.semidense_world, wm)
         st = svo.getSemiDenseWorldStats()
         print(f"world map: {len(wm.xyz)} voxels written of {st['occupied']} ({st['integrations']} keyframes integrated, {st['refused']} refused, "
               f"{st['inserted']} points) -> {args.semidense_world}")
+        if args.semidense_world_carve is not None:
+            cs = svo.getSemiDenseWorldCarveStats()
+            print(f"world map carving: {cs['carves']} carves, {cs['rays']} rays ({cs['short_rays']} short), {cs['visits']} voxel visits, {cs['hits']} hits")
     V.write_trajectory(args.trajectory, ids, np.stack(poses))
     if args.keyframes:
         kfs = svo.getKeyframes()

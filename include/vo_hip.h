@@ -442,7 +442,8 @@ int vo_stereo_frame_recoveries(const vo_ctx *ctx);
  *                         it), 2: its resolve only (on the keys an earlier call left) — what each launch costs (measurement)
  *   VO_DBG_SDW_FORM       1: the world map's integrations of this context run the simple kernel form (every point probes the global
  *                         table itself) instead of the pre-aggregated one — the same table contents, bit for bit (tests compare the
- *                         two; the A/B lever of the measurement) */
+ *                         two; the A/B lever of the measurement); the carves of this context run the form that is not their default,
+ *                         the pre-aggregated one ("Semi-dense world map: free-space carving") */
 enum { VO_DBG_FAIL_JOIN = 0, VO_DBG_CONC_GRID = 1, VO_DBG_SBA_LDS_SOLVE = 2, VO_DBG_SKIP_DETECT = 3, VO_OPT_POLL_YIELD = 4,
        VO_DBG_MVO_HOST_ADVANCE = 5, VO_DBG_STAGED_DETECT = 6, VO_DBG_CANDS_IN_FRAME = 7, VO_DBG_SBA_SPLIT = 8,
        VO_DBG_SDP_STAGE = 9, VO_DBG_SDW_FORM = 10, VO_DBG_COUNT = 11 };
@@ -1323,7 +1324,7 @@ int vo_svo_get_semidense_regularized_points(vo_svo *svo, int world, int min_obs,
  * only; vo_svo_semidense_world_clear empties the table. All: VO_ERR_INVALID while a frame is in flight or with the option off.
  *
  * Out of scope: re-anchoring voxels after the local BA moves a keyframe (since added: DESIGN §25, the block below; without that option
- * a keyframe stays integrated with the pose it had when it was replaced); free-space carving and the removal of moving objects; a TSDF, surfaces or meshes; growing or rehashing the table; a
+ * a keyframe stays integrated with the pose it had when it was replaced); free-space carving (since added: DESIGN §26, the block below that) and the removal of moving objects; a TSDF, surfaces or meshes; growing or rehashing the table; a
  * tighter refusal bound than W H; streaming the map out in tiles; MonoVO and vo_batch streams; any use of the map in the odometry.
  * With vo_svo_set_semidense_propagate on a propagated pixel re-enters every keyframe that carries it, so kf_cnt counts carried
  * surfaces too: min_keyframes then asks for less than independent confirmation. */
@@ -1424,6 +1425,76 @@ int vo_semidense_world_reanchor_stats(vo_semidense_world *wm, vo_semidense_world
 int vo_svo_set_semidense_world_reanchor(vo_svo *svo, int on, float min_move);
 int vo_svo_get_semidense_world_anchors(vo_svo *svo, int cap, int32_t *frame_id, int32_t *kf_index, float *T_wk, int32_t *in_window, int *n);
 int vo_svo_get_semidense_world_reanchor_stats(vo_svo *svo, vo_semidense_world_reanchor_info *info);
+
+/* ---- Semi-dense world map: free-space carving -----------------------------------------------------------------------
+ * The two blocks above only ever add evidence that something is there. This one adds the complement of a hit: a voxel that a
+ * keyframe's ray has passed through on its way to a surface behind counts as SEEN TO BE EMPTY, in a 32-bit count `free` per voxel —
+ * the word of the 64-byte slot that was padding. It is an integer like every other accumulator, so it is as independent of arrival
+ * order and as reproducible to the bit. Opt-in; with it off no launch, allocation, wait or result bit differs, with it on every other
+ * field of every voxel keeps its bits. float32, every operation rounded on its own (no FMA), in the order written here.
+ * tests/semidense_world_carve_restatement.py restates it.
+ *   inputs     of one carve: a map (invd, sigma, n_obs, W x H), K and T_wk exactly as vo_semidense_world_integrate takes them, without a
+ *              key plane. The table supplies voxel, min_obs and z_max.
+ *   params     vo_semidense_world_carve_params: margin [voxels] 2.0, >= 1; chi 3.0, >= 0; z_near [m] 0.5, > 0; all finite
+ *              (VO_ERR_INVALID otherwise).
+ *   ray        a pixel casts a ray where it passes the integration's entry test and is not SKIPPED (n_obs >= min_obs, z <= z_max,
+ *              z = 1.0f / invd) — whether or not its own point was out of range. sz = (sigma * z) * z, m = fmaxf(margin * voxel,
+ *              chi * sz), z_end = z - m, dz = voxel * 0.5f.
+ *   samples    the k in 1 .. 4096 with z_k = (float)k * dz, z_near <= z_k and z_k < z_end. 4096 is a constant of the definition: a
+ *              longer ray is carved over its near part only. A ray with no sample is counted as a SHORT ray.
+ *   position   sdw_point's text with z_k in the place of z: X = ((float)x - cx) / fx * z_k, Y = ((float)y - cy) / fy * z_k,
+ *              X'[r] = (T[r][0] X + (T[r][1] Y + T[r][2] z_k)) + T[r][3], per axis i = floorf(X' / voxel) with the integration's range
+ *              test and key. A sample with any axis out of range has key_k = 0.
+ *   visit      sample k is a VISIT where key_k != 0 and either k is the ray's first sample or key_k != key_{k-1}. A line meets a cube
+ *              in one interval, so suppressing consecutive duplicates is all the de-duplication a ray needs; the definition is the
+ *              consecutive rule itself, whatever rounding does.
+ *   lookup     the removal's: home slot, then linear probing; the key words are only read. A probe that meets key 0 ends with
+ *              nothing done; a match is a HIT and adds 1 to the slot's `free` (32 bits, wraps). A vacated voxel (cnt == 0, key kept)
+ *              collects `free` like any other: `free` belongs to the cell in space, not to an integration. The removal and the
+ *              re-anchoring do not touch it (the invariant of the block above holds for every field but `free`: a re-anchor does not
+ *              re-carve); clear zeroes it.
+ *   no seq     a carve takes no sequence number and is never refused; it writes no key and leaves occupied, cnt, kf_cnt and last_seq
+ *              alone.
+ *   counters   vo_semidense_world_carve_info: carves, rays, short_rays, visits, hits. The infos above keep their layouts; clear
+ *              zeroes these too.
+ *   extraction vo_semidense_world_points is unchanged. vo_semidense_world_points_free returns `free` per record as well, and with
+ *              free_den >= 1 keeps a voxel only where (u64)free * free_den <= (u64)cnt * free_num (free_num >= 0); free_den == 0: no
+ *              filter. Key order, cap and VO_ERR_CAPACITY as above.
+ * vo_semidense_world_carve is synchronous like _integrate and validates like it: a bad K, T or size touches nothing. The launch has the
+ * integration's geometry (ceil(W H / 1024) workgroups of 256); the block's (ray, k) pairs are shared out over the lanes, no lane owns
+ * a ray. In the default form every visit looks its voxel up itself (the simple form: hits are rare, the cost is the key reads);
+ * VO_DBG_SDW_FORM = 1 selects the OTHER form of the carve, which first combines a round's visits per workgroup in an LDS hash and
+ * looks every distinct voxel up once. Both leave the same bytes.
+ *
+ * StereoVO: vo_svo_set_semidense_world_carve(svo, prm) — prm NULL = off — needs vo_svo_set_semidense_world on; VO_ERR_INVALID
+ * otherwise, while a frame is in flight or on a mono driver. It allocates nothing. Wherever the driver integrates a keyframe's map (the
+ * keyframe change, the flush) it enqueues the carve of the same planes with the same pose directly behind that integration on the
+ * side stream: in front of whatever overwrites those planes and in front of the re-anchoring pass. Nothing waits. With it on the
+ * odometry, every semi-dense result, the keyframe poses and every other field of every voxel keep their bits.
+ *
+ * Out of scope: voxels for free space, an occupancy or TSDF grid; an exact 3-D DDA (the half-voxel sampling may miss a corner cut
+ * shorter than the step, by definition); re-carving on re-anchor; undoing a carve; deleting carved voxels or reclaiming their slots;
+ * carving from frames that are not keyframes; MonoVO and vo_batch; any use of `free` in the odometry. */
+typedef struct {
+  float margin; /* 2.0 [voxels] */
+  float chi;    /* 3.0 */
+  float z_near; /* 0.5 [m] */
+} vo_semidense_world_carve_params;
+typedef struct {
+  unsigned long long carves, rays, short_rays, visits, hits;
+} vo_semidense_world_carve_info;
+int vo_semidense_world_carve_default_params(vo_semidense_world_carve_params *prm);
+int vo_semidense_world_carve(vo_semidense_world *wm, const float *invd, const float *sigma, const uint8_t *n_obs, int width, int height,
+                             int on_device, const float K[4], const float T_wk[16], const vo_semidense_world_carve_params *prm);
+int vo_semidense_world_carve_stats(vo_semidense_world *wm, vo_semidense_world_carve_info *info);
+int vo_semidense_world_points_free(vo_semidense_world *wm, int min_count, int min_keyframes, int free_num, int free_den, int cap,
+                                   int32_t *index, float *xyz, uint32_t *weight, uint32_t *count, uint32_t *keyframes, uint8_t *grey,
+                                   uint64_t *sums, uint32_t *free_count, int *n);
+int vo_svo_set_semidense_world_carve(vo_svo *svo, const vo_semidense_world_carve_params *prm);
+int vo_svo_get_semidense_world_carve_stats(vo_svo *svo, vo_semidense_world_carve_info *info);
+int vo_svo_get_semidense_world_points_free(vo_svo *svo, int min_count, int min_keyframes, int free_num, int free_den, int cap,
+                                           int32_t *index, float *xyz, uint32_t *weight, uint32_t *count, uint32_t *keyframes,
+                                           uint8_t *grey, uint32_t *free_count, int *n);
 
 /* ---- undistortion / stereo rectification in front of the trackers ----------
  * core/visual_odometry/camera.cpp. A context holds the maps of two cameras

@@ -135,6 +135,14 @@ class SemiDenseWorldReanchorInfo(C.Structure):  # vo_semidense_world_reanchor_in
     _fields_ = [(k, C.c_ulonglong) for k in ("removals", "refused_removals", "removed", "missing", "reanchors", "vacant")]
 
 
+class SemiDenseWorldCarveParams(C.Structure):  # vo_semidense_world_carve_params
+    _fields_ = [("margin", C.c_float), ("chi", C.c_float), ("z_near", C.c_float)]
+
+
+class SemiDenseWorldCarveInfo(C.Structure):  # vo_semidense_world_carve_info
+    _fields_ = [(k, C.c_ulonglong) for k in ("carves", "rays", "short_rays", "visits", "hits")]
+
+
 class SemiDenseAlignParams(C.Structure):  # vo_semidense_align_params
     _fields_ = [("min_obs", C.c_int), ("huber", C.c_float), ("max_iters", C.c_int), ("eps", C.c_float), ("min_pixels", C.c_int)]
 
@@ -227,6 +235,8 @@ SYMBOLS = [
     "vo_svo_set_semidense_world_reanchor", "vo_svo_get_semidense_world_anchors", "vo_svo_get_semidense_world_reanchor_stats",
     "vo_semidense_world_stats", "vo_semidense_world_points", "vo_svo_set_semidense_world",
     "vo_svo_semidense_world_flush", "vo_svo_semidense_world_clear", "vo_svo_get_semidense_world_stats", "vo_svo_get_semidense_world_points",
+    "vo_semidense_world_carve_default_params", "vo_semidense_world_carve", "vo_semidense_world_carve_stats", "vo_semidense_world_points_free",
+    "vo_svo_set_semidense_world_carve", "vo_svo_get_semidense_world_carve_stats", "vo_svo_get_semidense_world_points_free",
 ]
 
 _lib = None
@@ -382,6 +392,13 @@ def load():
     lib.vo_svo_semidense_world_clear.argtypes = [vp]
     lib.vo_svo_get_semidense_world_stats.argtypes = [vp, vp]
     lib.vo_svo_get_semidense_world_points.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp]
+    lib.vo_semidense_world_carve_default_params.argtypes = [vp]
+    lib.vo_semidense_world_carve.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp]
+    lib.vo_semidense_world_carve_stats.argtypes = [vp, vp]
+    lib.vo_semidense_world_points_free.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.vo_svo_set_semidense_world_carve.argtypes = [vp, vp]
+    lib.vo_svo_get_semidense_world_carve_stats.argtypes = [vp, vp]
+    lib.vo_svo_get_semidense_world_points_free.argtypes = [vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.vo_five_point_create.argtypes = [vp, C.POINTER(FivePointParams), ci, C.POINTER(C.c_void_p)]
     lib.vo_five_point_destroy.argtypes = [vp]
     lib.vo_five_point_destroy.restype = None

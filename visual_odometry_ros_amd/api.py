@@ -186,6 +186,12 @@ class SemiDenseWorldPoints(collections.namedtuple("SemiDenseWorldPoints", "index
     __slots__ = ()
 
 
+class SemiDenseWorldFreePoints(collections.namedtuple("SemiDenseWorldFreePoints", "index xyz weight count keyframes grey sums free")):
+    """What a getter given max_free returns: the fields of SemiDenseWorldPoints and, behind them, free uint32 [n], the number of
+    carving rays that passed through the voxel (include/vo_hip.h, "Semi-dense world map: free-space carving")."""
+    __slots__ = ()
+
+
 def _semidense_world_params(lib, params):
     """keyword parameters -> vo_semidense_world_params: the C defaults, then the caller's fields"""
     p = _capi.SemiDenseWorldParams()
@@ -198,11 +204,29 @@ def _semidense_world_params(lib, params):
     return p
 
 
-def _semidense_world_points(check, get, capacity, with_sums):
+def _semidense_world_carve_params(lib, params):
+    """True or keyword parameters -> vo_semidense_world_carve_params: the C defaults, then the caller's fields"""
+    p = _capi.SemiDenseWorldCarveParams()
+    lib.vo_semidense_world_carve_default_params(C.byref(p))
+    known = {f[0] for f in _capi.SemiDenseWorldCarveParams._fields_}
+    for k, v in ({} if params is True else dict(params)).items():
+        if k not in known:
+            raise ValueError(f"world map carving: unknown parameter {k!r}; known: {sorted(known)}")
+        setattr(p, k, v)
+    return p
+
+
+def _max_free(max_free):
+    """max_free=(num, den): keep the voxels with free * den <= count * num; den 0: no filter"""
+    num, den = (int(v) for v in max_free)
+    return num, den
+
+
+def _semidense_world_points(check, get, capacity, with_sums, with_free=False):
     """the two-call pattern of the getters: the count, then the records"""
     n = C.c_int()
     if capacity is None:
-        rc = get(0, None, None, None, None, None, None, *((None,) if with_sums else ()), C.byref(n))
+        rc = get(0, None, None, None, None, None, None, *((None,) if with_sums else ()), *((None,) if with_free else ()), C.byref(n))
         if rc < 0 and rc != -8:  # (VO_ERR_CAPACITY: the count is what was asked for)
             check(rc)
         capacity = n.value
@@ -210,15 +234,17 @@ def _semidense_world_points(check, get, capacity, with_sums):
     m = max(cap, 1)
     idx, xyz = np.zeros((m, 3), np.int32), np.zeros((m, 3), np.float32)
     wt, cnt, kf, grey = np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m, np.uint32), np.zeros(m, np.uint8)
-    sums = np.zeros((m, 5), np.uint64)
+    sums, free = np.zeros((m, 5), np.uint64), np.zeros(m, np.uint32)
     rc = get(cap, idx.ctypes.data, xyz.ctypes.data, wt.ctypes.data, cnt.ctypes.data, kf.ctypes.data, grey.ctypes.data,
-             *((sums.ctypes.data,) if with_sums else ()), C.byref(n))
+             *((sums.ctypes.data,) if with_sums else ()), *((free.ctypes.data,) if with_free else ()), C.byref(n))
     try:
         check(rc)
     except VoError as e:
         e.n = n.value
         raise
     k = min(n.value, cap)
+    if with_free:
+        return SemiDenseWorldFreePoints(idx[:k], xyz[:k], wt[:k], cnt[:k], kf[:k], grey[:k], sums[:k] if with_sums else None, free[:k])
     return SemiDenseWorldPoints(idx[:k], xyz[:k], wt[:k], cnt[:k], kf[:k], grey[:k], sums[:k] if with_sums else None)
 
 
@@ -252,6 +278,33 @@ class SemiDenseWorld:
         self._launch(self.lib.vo_semidense_world_reanchor, map, K, (T_old, T_new), key, on_device, key_on_device, C.byref(moved))
         return bool(moved.value)
 
+    def carve(self, map, K, T_wk, on_device=None, **params):
+        """One carve (include/vo_hip.h, "Semi-dense world map: free-space carving"): every voxel of the table that a ray of the map
+        passes through on its way to the map's own surface gets 1 added to its `free` count. map, K, T_wk and on_device as
+        integrate() takes them; params: margin=, chi=, z_near=. Never refused; no other field of any voxel changes."""
+        p = _semidense_world_carve_params(self.lib, params)
+        get = (lambda k: getattr(map, k)) if isinstance(map, tuple) else (lambda k: map[k])
+        Ka = np.ascontiguousarray(K, np.float32).reshape(4)
+        T = np.ascontiguousarray(T_wk, np.float32).reshape(4, 4)
+        if on_device is not None:
+            w, h = on_device
+            planes = [C.c_void_p(get(k)) for k in ("invd", "sigma", "n_obs")]
+        else:
+            invd, sigma = np.ascontiguousarray(get("invd"), np.float32), np.ascontiguousarray(get("sigma"), np.float32)
+            n_obs = np.ascontiguousarray(get("n_obs"), np.uint8)
+            if invd.ndim != 2 or sigma.shape != invd.shape or n_obs.shape != invd.shape:
+                raise ValueError("invd, sigma and n_obs are planes of one (height, width)")
+            h, w = invd.shape
+            planes = [invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data]
+        self.ctx.check(self.lib.vo_semidense_world_carve(self._h, *planes, int(w), int(h), int(on_device is not None), Ka.ctypes.data,
+                                                         T.ctypes.data, C.byref(p)))
+
+    def carveStats(self):
+        """dict(carves, rays, short_rays, visits, hits)"""
+        info = _capi.SemiDenseWorldCarveInfo()
+        self.ctx.check(self.lib.vo_semidense_world_carve_stats(self._h, C.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in _capi.SemiDenseWorldCarveInfo._fields_}
+
     def reanchorStats(self):
         """dict(removals, refused_removals, removed, missing, reanchors, vacant); vacant is counted by a launch of its own"""
         info = _capi.SemiDenseWorldReanchorInfo()
@@ -284,8 +337,14 @@ class SemiDenseWorld:
         self.ctx.check(fn(self._h, *planes, pk, stride, int(key_on_device is not None), int(w), int(h), int(on_device is not None),
                           Ka.ctypes.data, *(T.ctypes.data for T in Ts), *tail))
 
-    def points(self, min_count=1, min_keyframes=1, capacity=None):
-        """The voxels with count >= min_count and keyframes >= min_keyframes: a SemiDenseWorldPoints in ascending key order."""
+    def points(self, min_count=1, min_keyframes=1, capacity=None, max_free=None):
+        """The voxels with count >= min_count and keyframes >= min_keyframes: a SemiDenseWorldPoints in ascending key order. With
+        max_free=(num, den) the result is a SemiDenseWorldFreePoints, with `free`, and with den >= 1 only the voxels with
+        free * den <= count * num are kept ((0, 0): all of them)."""
+        if max_free is not None:
+            num, den = _max_free(max_free)
+            get = lambda cap, *a: self.lib.vo_semidense_world_points_free(self._h, int(min_count), int(min_keyframes), num, den, cap, *a)
+            return _semidense_world_points(self.ctx.check, get, capacity, True, True)
         get = lambda *a: self.lib.vo_semidense_world_points(self._h, int(min_count), int(min_keyframes), *a)
         return _semidense_world_points(self.ctx.check, get, capacity, True)
 
@@ -1781,7 +1840,8 @@ class StereoVO:
         "propagate": True or dict(min_obs=, max_diff=, chi=, sigma_add=) setSemiDensePropagate,
         "regularize": True or dict(radius=, chi=, dist_sigma=, min_support=, fill_min=, g_min=) setSemiDenseRegularize,
         "world": True or dict(voxel=, capacity_log2=, min_obs=, z_max=, source="raw" | "regularized") setSemiDenseWorld; with
-        reanchor=True or reanchor=dict(min_move=0.0) in it, the maps follow the local BA (setSemiDenseWorldReanchor),
+        reanchor=True or reanchor=dict(min_move=0.0) in it, the maps follow the local BA (setSemiDenseWorldReanchor); with carve=True
+        or carve=dict(margin=, chi=, z_near=) in it, every integration is followed by a free-space carve (setSemiDenseWorldCarve),
         "align": True or dict(min_obs=, huber=, max_iters=, eps=, min_pixels=) setSemiDenseAlign; with levels=, max_iters_level= or
         start="odometry" | "previous" in it, coarse to fine on a map pyramid (setSemiDenseAlignPyramid); with affine=True or
         affine=dict(gain0=, offset0=) in it, gain and offset are estimated next to the pose (setSemiDenseAlignAffine).
@@ -2049,6 +2109,7 @@ class StereoVO:
         params = dict(params)
         src = params.pop("source", "raw")
         reanchor = params.pop("reanchor", None)
+        carve = params.pop("carve", None)
         if source is not None:
             src = source
         if src not in SEMIDENSE_WORLD_SOURCE:
@@ -2057,6 +2118,27 @@ class StereoVO:
         self.ctx.check(self.lib.vo_svo_set_semidense_world(self._h, C.byref(p), SEMIDENSE_WORLD_SOURCE[src]))
         if reanchor is not None:
             self.setSemiDenseWorldReanchor(reanchor)
+        if carve is not None:
+            self.setSemiDenseWorldCarve(carve)
+
+    def setSemiDenseWorldCarve(self, params):
+        """Free-space carving on the world map (include/vo_hip.h, "Semi-dense world map: free-space carving"): directly behind every
+        integration of a keyframe's map, one more launch on the side stream marches that map's rays through the table and counts, per
+        voxel, the rays that passed through it on their way to a surface behind (`free` of getSemiDenseWorld(max_free=...)). A voxel
+        left by a moving object or a flying pixel collects free counts; a surface does not. params: True or dict(margin=, chi=,
+        z_near=); None or False: off. Needs setSemiDenseWorld. The odometry's results, the semi-dense results, the keyframe poses
+        and every other field of every voxel do not change. Refused while a frame is in flight."""
+        if params is None or params is False:
+            self.ctx.check(self.lib.vo_svo_set_semidense_world_carve(self._h, None))
+            return
+        p = _semidense_world_carve_params(self.lib, params)
+        self.ctx.check(self.lib.vo_svo_set_semidense_world_carve(self._h, C.byref(p)))
+
+    def getSemiDenseWorldCarveStats(self):
+        """dict(carves, rays, short_rays, visits, hits) of the world map"""
+        info = _capi.SemiDenseWorldCarveInfo()
+        self.ctx.check(self.lib.vo_svo_get_semidense_world_carve_stats(self._h, C.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in _capi.SemiDenseWorldCarveInfo._fields_}
 
     def setSemiDenseWorldReanchor(self, params):
         """The world map follows the local BA (include/vo_hip.h, "Semi-dense world map: removal and re-anchoring"): the maps of the
@@ -2101,9 +2183,14 @@ class StereoVO:
     def clearSemiDenseWorld(self):
         self.ctx.check(self.lib.vo_svo_semidense_world_clear(self._h))
 
-    def getSemiDenseWorld(self, min_count=1, min_keyframes=1, capacity=None):
+    def getSemiDenseWorld(self, min_count=1, min_keyframes=1, capacity=None, max_free=None):
         """The world map's voxels with count >= min_count and keyframes >= min_keyframes: a SemiDenseWorldPoints in ascending key
-        order. Waits for the side stream's last launch only."""
+        order. With max_free=(num, den) the result is a SemiDenseWorldFreePoints, with `free`, and with den >= 1 only the voxels with
+        free * den <= count * num are kept ((0, 0): all of them). Waits for the side stream's last launch only."""
+        if max_free is not None:
+            num, den = _max_free(max_free)
+            get = lambda cap, *a: self.lib.vo_svo_get_semidense_world_points_free(self._h, int(min_count), int(min_keyframes), num, den, cap, *a)
+            return _semidense_world_points(self.ctx.check, get, capacity, False, True)
         get = lambda *a: self.lib.vo_svo_get_semidense_world_points(self._h, int(min_count), int(min_keyframes), *a)
         return _semidense_world_points(self.ctx.check, get, capacity, False)
 

@@ -528,6 +528,16 @@ class StereoVO {
   void flushSemiDenseWorld() { impl_.flushSemiDenseWorld(); }
   // the world map follows the local BA (vo::StereoVO::setSemiDenseWorldReanchor): min_move in voxels, 0 = any change of a pose
   void setSemiDenseWorldReanchor(bool on, float min_move = 0.0f) { impl_.setSemiDenseWorldReanchor(on, min_move); }
+  // free-space carving on the world map (vo::StereoVO::setSemiDenseWorldCarve): prm = nullptr: off; getSemiDenseWorldFree() the
+  // voxels' mean positions with their free counts, with free_den >= 1 only those with free * free_den <= count * free_num
+  void setSemiDenseWorldCarve(const vo_semidense_world_carve_params *prm) { impl_.setSemiDenseWorldCarve(prm); }
+  PointVec getSemiDenseWorldFree(std::vector<uint32_t> &free_count, int free_num = 0, int free_den = 0, int min_count = 1, int min_keyframes = 1) {
+    vo::PointVec v;
+    impl_.getSemiDenseWorldFree(v, free_count, free_num, free_den, min_count, min_keyframes);
+    PointVec o(v.size());
+    for (size_t i = 0; i < v.size(); ++i) o[i] = Point(v[i].x, v[i].y, v[i].z);
+    return o;
+  }
   PointVec getSemiDenseWorldPoints(int min_count = 1, int min_keyframes = 1) {
     vo::PointVec v;
     impl_.getSemiDenseWorldPoints(v, min_count, min_keyframes);

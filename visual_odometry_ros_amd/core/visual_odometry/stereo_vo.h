@@ -391,6 +391,41 @@ class StereoVO {
                                                          grey ? grey->data() : nullptr, &n));
     return n;
   }
+  // Free-space carving on the world map (vo_svo_set_semidense_world_carve; include/vo_hip.h, "Semi-dense world map: free-space
+  // carving"): directly behind every integration of a keyframe's map its rays are marched through the table, and every voxel a ray
+  // passes through on its way to a surface behind gets 1 added to its `free` count. Needs setSemiDenseWorld. prm = nullptr: off.
+  // Throws while a frame is in flight.
+  static vo_semidense_world_carve_params defaultSemiDenseWorldCarveParams() {
+    vo_semidense_world_carve_params p;
+    vo_semidense_world_carve_default_params(&p);
+    return p;
+  }
+  void setSemiDenseWorldCarve(const vo_semidense_world_carve_params *prm) { ctx_->check(vo_svo_set_semidense_world_carve(svo_, prm)); }
+  vo_semidense_world_carve_info getSemiDenseWorldCarveStats() {
+    vo_semidense_world_carve_info info;
+    ctx_->check(vo_svo_get_semidense_world_carve_stats(svo_, &info));
+    return info;
+  }
+  // getSemiDenseWorldPoints with the free count per voxel; with free_den >= 1 only the voxels with free * free_den <= count *
+  // free_num (free_den 0: all of them). Returns their number.
+  int getSemiDenseWorldFree(PointVec &xyz, std::vector<uint32_t> &free_count, int free_num = 0, int free_den = 0, int min_count = 1,
+                            int min_keyframes = 1, std::vector<uint32_t> *count = nullptr, std::vector<uint32_t> *keyframes = nullptr,
+                            std::vector<uint8_t> *grey = nullptr) {
+    int n = 0;
+    const int rc = vo_svo_get_semidense_world_points_free(svo_, min_count, min_keyframes, free_num, free_den, 0, nullptr, nullptr, nullptr, nullptr,
+                                                          nullptr, nullptr, nullptr, &n);
+    if (rc != VO_ERR_CAPACITY) ctx_->check(rc);  // (room for none: the count is what was asked for)
+    xyz.resize((size_t)n);
+    free_count.resize((size_t)n);
+    if (count) count->resize((size_t)n);
+    if (keyframes) keyframes->resize((size_t)n);
+    if (grey) grey->resize((size_t)n);
+    if (n) ctx_->check(vo_svo_get_semidense_world_points_free(svo_, min_count, min_keyframes, free_num, free_den, n, nullptr,
+                                                              reinterpret_cast<float *>(xyz.data()), nullptr, count ? count->data() : nullptr,
+                                                              keyframes ? keyframes->data() : nullptr, grey ? grey->data() : nullptr,
+                                                              free_count.data(), &n));
+    return n;
+  }
   // Direct image alignment on the keyframe's map (vo_svo_set_semidense_align; include/vo_hip.h, "Semi-dense alignment"): every frame
   // that is not a keyframe aligns its left image against the map from the odometry's pose, on the side stream in front of the
   // frame's temporal launch; nothing uses the aligned pose. Needs setSemiDenseTemporal. prm = nullptr: off. Throws while a frame is

@@ -3,7 +3,9 @@
 // (vo_svo_set_semidense_world, vo_svo_semidense_world_flush, vo_svo_get_semidense_world_points / _stats; the launch is placed by
 // vo_svo_semidense_temporal_enqueue in front of whatever overwrites the outgoing keyframe's map), and the exact removal of an
 // integration and the re-anchoring built on it (vo_semidense_world_remove / _reanchor / _reanchor_stats; "Semi-dense world map:
-// removal and re-anchoring"). semidense_world_device.hpp has the kernels.
+// removal and re-anchoring"), and the free-space carving (vo_semidense_world_carve / _carve_stats / _points_free,
+// vo_svo_set_semidense_world_carve; "Semi-dense world map: free-space carving"). semidense_world_device.hpp and
+// semidense_world_carve_device.hpp have the kernels.
 #include "stereo_vo.hpp"
 #include "vo_internal.hpp"
 #include "vo_kernels.hpp"
@@ -30,11 +32,13 @@
 __device__ __forceinline__ unsigned long long sdw_cas64(unsigned long long *p, unsigned long long cmp, unsigned long long v) {
   return atomicCAS(p, cmp, v);
 }
-#include "semidense_world_device.hpp"
+#include "semidense_world_carve_device.hpp"
 
 static_assert(sizeof(SdwSlot) == 64, "a slot is 64 bytes");
 static_assert(sizeof(SdwState) % 8 == 0, "the removal's 64-bit words behind SdwState are aligned");
-#define SDW_STATE_BYTES (sizeof(SdwState) + sizeof(SdwReanchorState))
+static_assert(sizeof(SdwReanchorState) % 8 == 0, "the carve's 64-bit words behind SdwReanchorState are aligned");
+static_assert(offsetof(SdwSlot, free) == 60, "free is the slot's last word");
+#define SDW_STATE_BYTES (sizeof(SdwState) + sizeof(SdwReanchorState) + sizeof(SdwCarveState))
 
 struct vo_semidense_world {
   vo_ctx *c = nullptr;
@@ -42,6 +46,7 @@ struct vo_semidense_world {
   SdwSlot *slots = nullptr;
   SdwState *st = nullptr;
   SdwReanchorState *rs = nullptr;  // the removal's words, behind *st in the same allocation
+  SdwCarveState *cs = nullptr;     // the carve's words, behind *rs
   unsigned long long reanchors = 0;  // vo_semidense_world_reanchor calls that enqueued their pair
   unsigned seq = 0;             // the sequence number of the last call, refused ones included
   SdwSlot *scratch = nullptr;   // the extraction's records (grows with the first getter that needs more)
@@ -85,6 +90,7 @@ extern "C" int vo_semidense_world_create(vo_ctx *c, const vo_semidense_world_par
   wm->slots = (SdwSlot *)base;
   wm->st = (SdwState *)((char *)base + bytes);
   wm->rs = (SdwReanchorState *)((char *)base + bytes + sizeof(SdwState));
+  wm->cs = (SdwCarveState *)((char *)base + bytes + sizeof(SdwState) + sizeof(SdwReanchorState));
   if (hipMemsetAsync(base, 0, bytes + SDW_STATE_BYTES, c->stream) != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) {
     (void)hipFree(base);
     delete wm;
@@ -279,7 +285,7 @@ static int sdw_stats(vo_semidense_world *wm, hipStream_t s, vo_semidense_world_i
     SdwState st;
     SdwReanchorState rs;
   } both;
-  static_assert(sizeof(both) == SDW_STATE_BYTES, "the two blocks lie back to back");
+  static_assert(sizeof(both) + sizeof(SdwCarveState) == SDW_STATE_BYTES, "the two blocks lie back to back, the carve's behind them");
   VO_CHECK_HIP(c, hipMemcpyAsync(&both, wm->st, sizeof(both), hipMemcpyDeviceToHost, s));
   VO_CHECK_HIP(c, hipStreamSynchronize(s));
   const SdwState &st = both.st;
@@ -300,7 +306,12 @@ extern "C" int vo_semidense_world_stats(vo_semidense_world *wm, vo_semidense_wor
   return sdw_stats(wm, wm->c->stream, info);
 }
 
-static int sdw_extract_launch(vo_semidense_world *wm, hipStream_t s, int min_count, int min_keyframes, unsigned *n) {
+// the free filter of vo_semidense_world_points_free; null: the extraction as it was, by its own kernel
+struct SdwFreeFilter {
+  unsigned num, den;
+};
+
+static int sdw_extract_launch(vo_semidense_world *wm, hipStream_t s, int min_count, int min_keyframes, const SdwFreeFilter *ff, unsigned *n) {
   vo_ctx *c = wm->c;
   SdwExtractArgs a;
   memset(&a, 0, sizeof(a));
@@ -312,7 +323,14 @@ static int sdw_extract_launch(vo_semidense_world *wm, hipStream_t s, int min_cou
   a.cap = (unsigned)wm->scratch_cap;
   a.st = wm->st;
   VO_CHECK_HIP(c, hipMemsetAsync(&wm->st->n_extract, 0, sizeof(unsigned), s));
-  hipLaunchKernelGGL(semidense_world_extract_kernel, dim3((unsigned)(a.n_slots / SDW_NT)), dim3(SDW_NT), 0, s, a);
+  if (ff) {
+    SdwExtractFreeArgs fa;
+    fa.e = a;
+    fa.free_num = ff->num;
+    fa.free_den = ff->den;
+    hipLaunchKernelGGL(semidense_world_extract_free_kernel, dim3((unsigned)(a.n_slots / SDW_NT)), dim3(SDW_NT), 0, s, fa);
+  } else
+    hipLaunchKernelGGL(semidense_world_extract_kernel, dim3((unsigned)(a.n_slots / SDW_NT)), dim3(SDW_NT), 0, s, a);
   VO_CHECK_HIP(c, hipGetLastError());
   VO_CHECK_HIP(c, hipMemcpyAsync(n, &wm->st->n_extract, sizeof(unsigned), hipMemcpyDeviceToHost, s));
   VO_CHECK_HIP(c, hipStreamSynchronize(s));
@@ -320,11 +338,12 @@ static int sdw_extract_launch(vo_semidense_world *wm, hipStream_t s, int min_cou
 }
 
 static int sdw_points(vo_semidense_world *wm, hipStream_t s, int min_count, int min_keyframes, int cap, int32_t *index, float *xyz,
-                      uint32_t *weight, uint32_t *count, uint32_t *keyframes, uint8_t *grey, uint64_t *sums, int *n) {
+                      uint32_t *weight, uint32_t *count, uint32_t *keyframes, uint8_t *grey, uint64_t *sums, int *n,
+                      const SdwFreeFilter *ff = nullptr, uint32_t *free_count = nullptr) {
   vo_ctx *c = wm->c;
   if (min_count < 1 || min_keyframes < 1) VO_FAIL(c, VO_ERR_INVALID, "semi-dense world map: min_count and min_keyframes are >= 1");
   unsigned k = 0;
-  int rc = sdw_extract_launch(wm, s, min_count, min_keyframes, &k);
+  int rc = sdw_extract_launch(wm, s, min_count, min_keyframes, ff, &k);
   if (rc) return rc;
   *n = (int)k;
   if (cap == 0 || k == 0) return k > (unsigned)cap ? VO_ERR_CAPACITY : VO_OK;
@@ -334,7 +353,7 @@ static int sdw_points(vo_semidense_world *wm, hipStream_t s, int min_count, int 
     wm->scratch_cap = 0;
     VO_CHECK_HIP(c, vo_dev_malloc(c, (void **)&wm->scratch, (size_t)k * sizeof(SdwSlot)));
     wm->scratch_cap = k;
-    rc = sdw_extract_launch(wm, s, min_count, min_keyframes, &k);
+    rc = sdw_extract_launch(wm, s, min_count, min_keyframes, ff, &k);
     if (rc) return rc;
   }
   std::vector<SdwSlot> rec(k);
@@ -358,6 +377,7 @@ static int sdw_points(vo_semidense_world *wm, hipStream_t s, int min_count, int 
     if (weight) weight[i] = r.sw > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)r.sw;
     if (count) count[i] = r.cnt;
     if (keyframes) keyframes[i] = r.kf_cnt;
+    if (free_count) free_count[i] = r.free;
     if (grey) grey[i] = (uint8_t)((r.sg + r.sw / 2) / r.sw);
     if (sums) sums[5 * i] = r.sw, sums[5 * i + 1] = r.sx, sums[5 * i + 2] = r.sy, sums[5 * i + 3] = r.sz, sums[5 * i + 4] = r.sg;
   }
@@ -369,6 +389,134 @@ extern "C" int vo_semidense_world_points(vo_semidense_world *wm, int min_count, 
   if (!wm || !n || cap < 0) return VO_ERR_INVALID;
   VO_CHECK_HIP(wm->c, hipSetDevice(wm->c->device));
   return sdw_points(wm, wm->c->stream, min_count, min_keyframes, cap, index, xyz, weight, count, keyframes, grey, sums, n);
+}
+
+// ---- free-space carving ------------------------------------------------------------------------------------------------
+extern "C" int vo_semidense_world_carve_default_params(vo_semidense_world_carve_params *p) {
+  if (!p) return VO_ERR_INVALID;
+  memset(p, 0, sizeof(*p));
+  p->margin = 2.0f;
+  p->chi = 3.0f;
+  p->z_near = 0.5f;
+  return VO_OK;
+}
+
+static int sdw_check_carve_params(vo_ctx *c, const vo_semidense_world_carve_params *p) {
+  if (!(p->margin >= 1.0f) || !isfinite(p->margin)) VO_FAIL(c, VO_ERR_INVALID, "world map carving: margin must be >= 1 voxel and finite");
+  if (!(p->chi >= 0.0f) || !isfinite(p->chi)) VO_FAIL(c, VO_ERR_INVALID, "world map carving: chi must be >= 0 and finite");
+  if (!(p->z_near > 0.0f) || !isfinite(p->z_near)) VO_FAIL(c, VO_ERR_INVALID, "world map carving: z_near must be positive and finite");
+  return VO_OK;
+}
+
+// On stream s, DEVICE planes. No seq, no refusal: the launch reads keys and adds to `free` words and to the carve's counters only.
+static int sdw_carve_enqueue(vo_semidense_world *wm, hipStream_t s, const float *invd, const float *sigma, const uint8_t *n_obs, int W, int H,
+                             const float K[4], const float T_wk[16], const vo_semidense_world_carve_params *prm) {
+  vo_ctx *c = wm->c;
+  int rc = sdw_check_carve_params(c, prm);
+  if (!rc) rc = sdw_check_launch(wm, nullptr, 0, W, H, K, T_wk);
+  if (rc) return rc;
+  SdwCarveArgs ca;
+  memset(&ca, 0, sizeof(ca));
+  SdwArgs &a = ca.a;
+  a.invd = invd;
+  a.sigma = sigma;
+  a.n_obs = n_obs;
+  a.W = W;
+  a.H = H;
+  a.min_obs = wm->prm.min_obs;
+  a.z_max = wm->prm.z_max;
+  a.voxel = wm->prm.voxel;
+  a.fx = K[0], a.fy = K[1], a.cx = K[2], a.cy = K[3];
+  memcpy(a.T, T_wk, sizeof(a.T));
+  a.capacity_log2 = wm->prm.capacity_log2;
+  a.slots = wm->slots;
+  a.st = wm->st;
+  ca.margin = prm->margin;
+  ca.chi = prm->chi;
+  ca.z_near = prm->z_near;
+  ca.dz = a.voxel * 0.5f;
+  ca.k0 = 1;  // the first sample's k is the launch's: z_k does not fall with k (host code: -ffp-contract=off)
+  while (ca.k0 <= SDWC_MAX_K && !(ca.z_near <= (float)ca.k0 * ca.dz)) ++ca.k0;
+  ca.cs = wm->cs;
+  const unsigned nb = (unsigned)(((size_t)W * (size_t)H + SDW_BLOCK - 1) / SDW_BLOCK);
+  hipStream_t keep = c->stream;
+  c->stream = s;
+  vo_prof_begin(c, VO_K_AUX);
+  // the simple form is the default: the faster of the two on a table as lightly loaded as a sequence leaves it
+  if (c->dbg[VO_DBG_SDW_FORM] == 1)
+    hipLaunchKernelGGL(semidense_world_carve_kernel<true>, dim3(nb), dim3(SDW_NT), 0, s, ca);
+  else
+    hipLaunchKernelGGL(semidense_world_carve_kernel<false>, dim3(nb), dim3(SDW_NT), 0, s, ca);
+  vo_prof_end(c);
+  c->stream = keep;
+  VO_CHECK_HIP(c, hipGetLastError());
+  return VO_OK;
+}
+
+extern "C" int vo_semidense_world_carve(vo_semidense_world *wm, const float *invd, const float *sigma, const uint8_t *n_obs, int width,
+                                        int height, int on_device, const float K[4], const float T_wk[16],
+                                        const vo_semidense_world_carve_params *prm) {
+  if (!wm || !invd || !sigma || !n_obs || !K || !T_wk || !prm || width <= 0 || height <= 0) return VO_ERR_INVALID;
+  vo_ctx *c = wm->c;
+  if (width > c->cfg.max_width || height > c->cfg.max_height)
+    VO_FAIL(c, VO_ERR_SIZE, "%d x %d planes exceed vo_config.max_width x max_height", width, height);
+  int rc = sdw_check_carve_params(c, prm);  // (before any copy: a bad call touches nothing)
+  if (!rc) rc = sdw_check_launch(wm, nullptr, 0, width, height, K, T_wk);
+  if (rc) return rc;
+  VO_CHECK_HIP(c, hipSetDevice(c->device));
+  hipStream_t s = c->stream;
+  const size_t np = (size_t)width * (size_t)height;
+  const float *d_invd = invd, *d_sigma = sigma;
+  const uint8_t *d_no = n_obs;
+  if (!on_device) {
+    vo_sdt_buffers *b = nullptr;
+    rc = vo_sdt_ctx_buffers(c, &b);
+    if (rc) return rc;
+    VO_CHECK_HIP(c, hipMemcpyAsync(b->invd, invd, np * sizeof(float), hipMemcpyHostToDevice, s));
+    VO_CHECK_HIP(c, hipMemcpyAsync(b->sigma, sigma, np * sizeof(float), hipMemcpyHostToDevice, s));
+    VO_CHECK_HIP(c, hipMemcpyAsync(b->n_obs, n_obs, np, hipMemcpyHostToDevice, s));
+    d_invd = b->invd, d_sigma = b->sigma, d_no = b->n_obs;
+  }
+  rc = sdw_carve_enqueue(wm, s, d_invd, d_sigma, d_no, width, height, K, T_wk, prm);
+  VO_CHECK_HIP(c, hipStreamSynchronize(s));  // (the copies read the caller's memory)
+  return rc;
+}
+
+static int sdw_carve_stats(vo_semidense_world *wm, hipStream_t s, vo_semidense_world_carve_info *info) {
+  vo_ctx *c = wm->c;
+  SdwCarveState cs;
+  VO_CHECK_HIP(c, hipMemcpyAsync(&cs, wm->cs, sizeof(cs), hipMemcpyDeviceToHost, s));
+  VO_CHECK_HIP(c, hipStreamSynchronize(s));
+  info->carves = cs.carves;
+  info->rays = cs.rays;
+  info->short_rays = cs.short_rays;
+  info->visits = cs.visits;
+  info->hits = cs.hits;
+  return VO_OK;
+}
+
+extern "C" int vo_semidense_world_carve_stats(vo_semidense_world *wm, vo_semidense_world_carve_info *info) {
+  if (!wm || !info) return VO_ERR_INVALID;
+  VO_CHECK_HIP(wm->c, hipSetDevice(wm->c->device));
+  return sdw_carve_stats(wm, wm->c->stream, info);
+}
+
+static int sdw_free_filter(vo_ctx *c, int free_num, int free_den, SdwFreeFilter *ff) {
+  if (free_num < 0 || free_den < 0) VO_FAIL(c, VO_ERR_INVALID, "semi-dense world map: free_num and free_den are >= 0");
+  ff->num = (unsigned)free_num;
+  ff->den = (unsigned)free_den;
+  return VO_OK;
+}
+
+extern "C" int vo_semidense_world_points_free(vo_semidense_world *wm, int min_count, int min_keyframes, int free_num, int free_den, int cap,
+                                              int32_t *index, float *xyz, uint32_t *weight, uint32_t *count, uint32_t *keyframes,
+                                              uint8_t *grey, uint64_t *sums, uint32_t *free_count, int *n) {
+  if (!wm || !n || cap < 0) return VO_ERR_INVALID;
+  SdwFreeFilter ff;
+  const int rc = sdw_free_filter(wm->c, free_num, free_den, &ff);
+  if (rc) return rc;
+  VO_CHECK_HIP(wm->c, hipSetDevice(wm->c->device));
+  return sdw_points(wm, wm->c->stream, min_count, min_keyframes, cap, index, xyz, weight, count, keyframes, grey, sums, n, &ff, free_count);
 }
 
 // ---- StereoVO's hook ------------------------------------------------------------------------------------------------------------------
@@ -465,6 +613,9 @@ int vo_svo_semidense_world_enqueue(vo_svo *s) {
   if (rc) return rc;
   rc = sdw_enqueue(w.wm, s->c->stream2, invd, sigma, n_obs, t.buf.key, t.w, t.w, t.h, s->prm.frame.Kl, t.T_wk);
   if (rc) return rc;
+  // vo_svo_set_semidense_world_carve: the same planes with the same pose, directly behind their integration
+  if (w.carve_on) rc = sdw_carve_enqueue(w.wm, s->c->stream2, invd, sigma, n_obs, t.w, t.h, s->prm.frame.Kl, t.T_wk, &w.carve);
+  if (rc) return rc;
   w.done = true;
   return VO_OK;
 }
@@ -530,6 +681,7 @@ extern "C" int vo_svo_set_semidense_world(vo_svo *s, const vo_semidense_world_pa
   vo_svo_semidense_world &w = s->sdw;
   if (!prm) {
     w.on = false;
+    w.carve_on = false;  // (the carve needs the world map)
     return VO_OK;
   }
   if (!s->sdt.on || !s->sd.on)
@@ -695,4 +847,42 @@ extern "C" int vo_svo_get_semidense_world_reanchor_stats(vo_svo *s, vo_semidense
   rc = sdw_reanchor_stats(s->sdw.wm, s->c->stream, info);
   if (!rc) svo_sdw_settle(s, info->refused_removals);
   return rc;
+}
+
+// ---- vo_svo_set_semidense_world_carve -------------------------------------------------------------------------------
+extern "C" int vo_svo_set_semidense_world_carve(vo_svo *s, const vo_semidense_world_carve_params *prm) {
+  if (!s) return VO_ERR_INVALID;
+  vo_ctx *c = s->c;
+  if (s->pending) VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world_carve: a frame is in flight: call vo_svo_result first");
+  if (s->mono) VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world_carve: a stereo driver only");
+  vo_svo_semidense_world &w = s->sdw;
+  if (!prm) {
+    w.carve_on = false;
+    return VO_OK;
+  }
+  if (!w.on || !w.wm) VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world_carve: needs the world map: vo_svo_set_semidense_world first");
+  const int rc = sdw_check_carve_params(c, prm);
+  if (rc) return rc;
+  w.carve = *prm;
+  w.carve_on = true;
+  return VO_OK;
+}
+
+extern "C" int vo_svo_get_semidense_world_carve_stats(vo_svo *s, vo_semidense_world_carve_info *info) {
+  if (!s || !info) return VO_ERR_INVALID;
+  const int rc = svo_sdw_ready(s, "vo_svo_get_semidense_world_carve_stats");
+  if (rc) return rc;
+  return sdw_carve_stats(s->sdw.wm, s->c->stream, info);
+}
+
+extern "C" int vo_svo_get_semidense_world_points_free(vo_svo *s, int min_count, int min_keyframes, int free_num, int free_den, int cap,
+                                                      int32_t *index, float *xyz, uint32_t *weight, uint32_t *count, uint32_t *keyframes,
+                                                      uint8_t *grey, uint32_t *free_count, int *n) {
+  if (!s || !n || cap < 0) return VO_ERR_INVALID;
+  int rc = svo_sdw_ready(s, "vo_svo_get_semidense_world_points_free");
+  if (rc) return rc;
+  SdwFreeFilter ff;
+  rc = sdw_free_filter(s->c, free_num, free_den, &ff);
+  if (rc) return rc;
+  return sdw_points(s->sdw.wm, s->c->stream, min_count, min_keyframes, cap, index, xyz, weight, count, keyframes, grey, nullptr, n, &ff, free_count);
 }

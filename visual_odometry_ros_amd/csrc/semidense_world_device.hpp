@@ -68,7 +68,7 @@ typedef unsigned long long sdw_u64;
 struct SdwSlot {
   sdw_u64 key;
   sdw_u64 sw, sx, sy, sz, sg;
-  unsigned cnt, kf_cnt, last_seq, pad;
+  unsigned cnt, kf_cnt, last_seq, free;  // free: the carve's count (semidense_world_carve_device.hpp); no other kernel writes it
 };
 
 // the table's words on the device

@@ -72,6 +72,9 @@ struct vo_svo_semidense_world {
   bool on = false, done = false;
   int source = 0;
   struct vo_semidense_world *wm = nullptr;
+  // vo_svo_set_semidense_world_carve: every integration of a keyframe's map is followed by the carve of the same planes
+  bool carve_on = false;
+  vo_semidense_world_carve_params carve = {};
   // vo_svo_set_semidense_world_reanchor: the planes of every map integrated while its keyframe sits in the local BA's
   // window are kept in a ring on the device, so that the map can be taken out of the table and put back where the BA moves the
   // keyframe. An anchor per integrated keyframe: `live` those whose keyframe is in the window (kf_window at most, each with a ring
