@@ -39,7 +39,10 @@ identity at the first frame after a keyframe, afterwards the previous frame's al
 odometry's. With either, the line ends with the start that was used and "status:iterations:pixels" per level, level 0 first.
 --semidense-align-affine: the alignment also estimates a gain and an offset of the keyframe's grey levels (for streams whose exposure
 changes between a keyframe and its frames; status 5: they left their range); the line then carries the two behind the rotation
-distance, in front of the start."""
+distance, in front of the start.
+--dense DIR [--dense-every frame] [--dense-disparities N] [--dense-paths 4|8]: a dense disparity (census + semi-global matching) of
+every keyframe's (or every frame's) pair, independent of --semidense; `dense_<frame id>.ply` per result in DIR, as the semi-dense
+files. N (default 128) disparities are searched, ending at a depth of 3 m."""
 import argparse
 import os
 import sys
@@ -95,6 +98,22 @@ def zncc_options(args):
     if not (win % 2 == 1 and 3 <= win <= 31) or args.zncc != args.zncc:
         raise SystemExit("--zncc: THRES is a number; --zncc-win: N is odd, 3..31")
     return {"zncc_gate": {"thres": args.zncc, "win": win, "pattern": "centered", "pairs": ("temporal", "stereo") if args.zncc_stereo else ("temporal",)}}
+
+
+def dense_options(args):
+    """--dense DIR [--dense-every frame] [--dense-disparities N] [--dense-paths 4|8] as the `dense` argument of from_yaml: a dense
+    disparity (census + semi-global matching) of every keyframe's (or every frame's) pair; bf comes from the file's camera, the range
+    from a smallest depth of 3 m"""
+    if args.dense is None:
+        if args.dense_every is not None or args.dense_disparities is not None or args.dense_paths is not None:
+            raise SystemExit("--dense-every / --dense-disparities / --dense-paths need --dense DIR")
+        return {}
+    if args.dense_disparities is not None and not 1 <= args.dense_disparities <= 256:
+        raise SystemExit("--dense-disparities N: 1..256 (rounded up to 64, 128, 192 or 256)")
+    ds = {"z_min": 3.0, "n_disp": args.dense_disparities or 128, "every": args.dense_every or "keyframe"}
+    if args.dense_paths is not None:
+        ds["paths"] = args.dense_paths
+    return {"dense": ds}
 
 
 def semidense_options(args):
@@ -261,6 +280,12 @@ def parse_args(argv=None):
     ap.add_argument("--semidense-align-affine", action="store_true",
                     help="--semidense-align: estimate a gain and an offset of the keyframe's grey levels next to the pose; two more columns")
     ap.add_argument("--semidense-min-obs", type=int, default=None, metavar="N", help="observations a fused pixel needs (default 2)")
+    ap.add_argument("--dense", default=None, metavar="DIR",
+                    help="dense stereo disparity (census + semi-global matching) of every keyframe's pair; one ASCII PLY per result in DIR")
+    ap.add_argument("--dense-every", choices=("keyframe", "frame"), default=None, help="a dense result per keyframe (default) or per frame")
+    ap.add_argument("--dense-disparities", type=int, default=None, metavar="N",
+                    help="disparities searched by --dense (default 128; rounded up to 64, 128, 192 or 256), ending at a depth of 3 m")
+    ap.add_argument("--dense-paths", type=int, choices=(4, 8), default=None, help="aggregation paths of --dense (default 8)")
     return ap.parse_args(argv)
 
 
@@ -275,9 +300,12 @@ def main():
         raise SystemExit("no image pairs found")
     svo = V.StereoVO.from_yaml(args.config, device=args.device, strict_border=args.strict_border, local_ba=not args.no_local_ba,
                                pose_covariance=bool(args.covariance), **mask_options(args), **clahe_options(args),
-                               **zncc_options(args), **semidense_options(args))
+                               **zncc_options(args), **semidense_options(args), **dense_options(args))
     if args.semidense:
         os.makedirs(args.semidense, exist_ok=True)
+    if args.dense:
+        os.makedirs(args.dense, exist_ok=True)
+    ds_last = -1
     sd_last, fused, regd = -1, None, None  # (fused, regd: the current keyframe's map and its regularised copy as points, as of the last frame)
     min_obs = args.semidense_min_obs or 2
 
@@ -314,6 +342,11 @@ def main():
             if pts is not None and pts["frame_id"] != sd_last:
                 sd_last = pts["frame_id"]
                 write_ply(os.path.join(args.semidense, f"semidense_{sd_last:06d}.ply"), pts["xyz"], pts["sigma_invd"])
+        if args.dense and (info.is_keyframe or args.dense_every == "frame"):  # (fetched here for simplicity, as the semi-dense result)
+            pts = svo.getDensePoints(world=True)
+            if pts is not None and pts["frame_id"] != ds_last:
+                ds_last = pts["frame_id"]
+                write_ply(os.path.join(args.dense, f"dense_{ds_last:06d}.ply"), pts["xyz"], pts["sigma_invd"])
         if args.semidense and args.semidense_temporal:
             # (a keyframe has replaced the map by the time its result is here, so the map is taken after every frame — after a
             # keyframe it is the freshly seeded one, which is what gets written if the next frame is a keyframe again — and

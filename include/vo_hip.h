@@ -809,6 +809,70 @@ int vo_svo_get_semidense(vo_svo *svo, float *disparity, float *score, float *sig
                          int *frame_id, float T_wc[16], int *n_accepted);
 int vo_svo_get_semidense_points(vo_svo *svo, int world, int cap, float *xyz, float *sigma_invd, uint16_t *pixel, int *n, int *frame_id);
 
+/* ---- Dense stereo: a disparity for every pixel by census + semi-global matching ----------------------------
+ * Coverage, not precision: the semi-dense operator above measures the high-gradient pixels more exactly; this one gives walls,
+ * road and weakly textured surfaces a disparity too. Inputs: the level-0 u8 planes L, R of two slots of one size W x H (both
+ * <= 65535), the left slot's ignore mask where one is bound, and vo_dense_stereo_params. Everything up to the parabola is an
+ * integer, and min and + do not depend on an order: tests/dense_stereo_restatement.py restates it.
+ *   params     d_min >= 0; n_disp 64, 128, 192 or 256: the disparities searched are d_min + d, d = 0 .. n_disp-1; paths 4 or 8;
+ *              0 <= p1 < p2 <= 8129 (S below fits 16 bits: 8 (62 + p2) <= 65535); uniqueness 0..99; lr_max >= -1 (-1: no
+ *              left-right check); eps_d >= 0 [pixel] and bf = focal length x baseline [pixel m] > 0, both finite.
+ *   census     cen(x, y): 62 bits of a 64-bit word over the 9 x 7 window without its centre. Taps in raster order, v = -3..3
+ *              (rows, outer), k = -4..4 (columns, inner), the centre skipped: the t-th tap sets bit t (t = 0..61) where
+ *              I(clamp(x+k, 0, W-1), clamp(y+v, 0, H-1)) < I(x, y).
+ *   cost       C(x, y, d) = popcount(cenL(x, y) ^ cenR(x - d_min - d, y)); 62 where x - d_min - d < 0.
+ *   paths      directions r = (dx, dy): (1,0), (-1,0), (0,1), (0,-1), and with paths = 8 also (1,1), (-1,-1), (1,-1), (-1,1).
+ *              L_r(p, d) = C(p, d) where p - r lies outside the image, else with m = min_k L_r(p-r, k):
+ *              C(p, d) + min(L_r(p-r, d), min(L_r(p-r, d-1), L_r(p-r, d+1)) + p1, m + p2) - m; a neighbour d-1 < 0 or
+ *              d+1 > n_disp-1 does not take part. p2 is constant. S = the sum of L_r over the directions (<= 65535).
+ *   decision   d_best = the d of the smallest S(x, y, d) (ties: the smallest d); S2 = the smallest S(x, y, d) over |d - d_best| > 1;
+ *              x_r = x - d_min - d_best; d_R(x_r) = the d of the smallest S(x_r + d_min + d, y, d) over the d with
+ *              x_r + d_min + d <= W-1 (ties: the smallest d): the right view's disparity from the same volume.
+ *   status     in this order of precedence: 0 masked (mask byte == 0); 4 d_best == 0 or d_best == n_disp-1; 2 S2 (100 - uniqueness) <
+ *              100 S(d_best) (64-bit integers); 3 with lr_max >= 0: x_r < 0 or |d_R(x_r) - d_best| > lr_max; 1 accepted. The mask
+ *              touches the outputs only: masked pixels take part in the aggregation.
+ *   accepted   Sm, S0, Sp = (float)S(x, y, d_best - 1), .. (d_best), .. (d_best + 1); den = (Sm + Sp) - (S0 + S0);
+ *              off = den != 0 ? (0.5f * (Sm - Sp)) / den : 0; disparity = (float)(d_min + d_best) + off; sigma_invd = eps_d / bf —
+ *              float32, each operation rounded on its own (no FMA).
+ *   outputs    four W x H planes, tightly packed: disparity f32 (0 where status != 1), cost u16 (S(d_best); 0 where masked),
+ *              sigma_invd f32 (0 where status != 1), status u8. disparity, sigma_invd and status mean what vo_semidense_stereo's
+ *              planes mean: vo_semidense_points, vo_semidense_map_seed, the regularisation and vo_semidense_world_integrate take
+ *              them unchanged.
+ * vo_dense_stereo: any output may be NULL; on_device: the outputs are device memory. Synchronous. The workspace — two census
+ * planes (8 bytes a pixel each) and S (2 n_disp bytes a pixel) — belongs to the context, is allocated at the first call and grows
+ * when a later call needs more; vo_dense_stereo_workspace reports its size for a shape. An allocation that fails is VO_ERR_HIP.
+ *
+ * StereoVO (off by default; with it off no launch, wait, allocation or result bit differs; with it on the odometry's and every
+ * semi-dense option's results are the same bits): vo_svo_set_dense_stereo(svo, prm, every) — prm NULL = off, every as in
+ * vo_svo_set_semidense — with exactly that option's rules: the option's only allocations at the first enable; the launches for a
+ * frame are enqueued by vo_svo_result on the side stream behind a fork event of the main stream and read the frame's own slots;
+ * vo_svo_result never waits; a later ingestion into a slot they read is ordered behind their event on the device.
+ * vo_svo_get_dense_stereo: the last result's planes (any may be NULL), size, frame_id (-1 and 0 x 0 before any), T_wc and the
+ * number of accepted pixels; vo_svo_get_dense_points: vo_semidense_points of it with the left camera's K. Both wait for that
+ * result's event only. All three: VO_ERR_INVALID while a frame is in flight and on a MonoVO's driver; the getters also with the
+ * option off. Independent of vo_svo_set_semidense: either, both or neither may be on.
+ * Out of scope: the driver's world map, temporal map or propagation taking this result as their source (the operators above take
+ * the planes: that is the follow-up); gradient-adaptive p2; speckle and median filters; hole filling; a right-image mask;
+ * sub-pixel costs; more than 256 disparities; MonoVO and vo_batch; any use of the disparity in the odometry. */
+typedef struct {
+  int d_min;        /* 0 */
+  int n_disp;       /* 64 */
+  int paths;        /* 8 */
+  int p1, p2;       /* 8, 64 */
+  int uniqueness;   /* 10 */
+  int lr_max;       /* 1 */
+  float eps_d;      /* 0.5 */
+  float bf;         /* 1.0: set it */
+} vo_dense_stereo_params;
+int vo_dense_stereo_default_params(vo_dense_stereo_params *prm);
+int vo_dense_stereo_workspace(int width, int height, const vo_dense_stereo_params *prm, size_t *bytes);
+int vo_dense_stereo(vo_ctx *ctx, int slot_l, int slot_r, const vo_dense_stereo_params *prm, float *disparity, uint16_t *cost,
+                    float *sigma_invd, uint8_t *status, int on_device);
+int vo_svo_set_dense_stereo(vo_svo *svo, const vo_dense_stereo_params *prm, int every);
+int vo_svo_get_dense_stereo(vo_svo *svo, float *disparity, uint16_t *cost, float *sigma_invd, uint8_t *status, int *width, int *height,
+                            int *frame_id, float T_wc[16], int *n_accepted);
+int vo_svo_get_dense_points(vo_svo *svo, int world, int cap, float *xyz, float *sigma_invd, uint16_t *pixel, int *n, int *frame_id);
+
 /* ---- Semi-dense temporal: the keyframe's pixels searched in the following left images, fused per keyframe ----
  * The second half of the reference author's semi-dense prototype, read for intent only: a pixel of the keyframe's left image is
  * searched in a later left image along the epipolar line the odometry's pose gives, and the inverse depths are fused as

@@ -12,4 +12,5 @@ from .api import (Context, FeatureTracker, MotionEstimator, FeatureExtractor,  #
                   FivePointRansac, PoseInformation, PoseCovariance, propagate_pose_covariance, pose_covariance_ros,
                   se3_adjoint, SemiDenseResult, SemiDenseMap, semidense_disparity_range, SemiDensePropagated, SemiDenseAligned, SemiDenseAlignedLevel,
                   SEMIDENSE_ALIGN_STATUS, SemiDenseAlignedAffineLevel, SEMIDENSE_ALIGN_AFFINE_STATUS,
-                  SemiDenseRegularized, SEMIDENSE_RSTATUS, SemiDenseWorld, SemiDenseWorldPoints, SemiDenseWorldFreePoints, SEMIDENSE_WORLD_SOURCE)
+                  SemiDenseRegularized, SEMIDENSE_RSTATUS, SemiDenseWorld, SemiDenseWorldPoints, SemiDenseWorldFreePoints, SEMIDENSE_WORLD_SOURCE,
+                  DenseStereoResult, DENSE_STEREO_DISPARITIES)

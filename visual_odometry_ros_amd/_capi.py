@@ -108,6 +108,11 @@ class SemiDenseParams(C.Structure):  # vo_semidense_params
                 ("bf", C.c_float)]
 
 
+class DenseStereoParams(C.Structure):  # vo_dense_stereo_params
+    _fields_ = [("d_min", C.c_int), ("n_disp", C.c_int), ("paths", C.c_int), ("p1", C.c_int), ("p2", C.c_int), ("uniqueness", C.c_int),
+                ("lr_max", C.c_int), ("eps_d", C.c_float), ("bf", C.c_float)]
+
+
 class SemiDenseTemporalParams(C.Structure):  # vo_semidense_temporal_params
     _fields_ = [("hw", C.c_int), ("hh", C.c_int), ("g_min", C.c_int), ("thres_best", C.c_float), ("thres_peak", C.c_float),
                 ("peak_px", C.c_int), ("edge_px", C.c_int), ("eps_edge", C.c_float), ("eps_epi", C.c_float), ("eps_scale", C.c_float),
@@ -220,6 +225,8 @@ SYMBOLS = [
     "vo_zncc", "vo_svo_set_zncc_gate", "vo_svo_get_zncc", "vo_mvo_set_zncc_gate", "vo_mvo_get_zncc",
     "vo_semidense_default_params", "vo_semidense_stereo", "vo_semidense_points",
     "vo_svo_set_semidense", "vo_svo_get_semidense", "vo_svo_get_semidense_points",
+    "vo_dense_stereo_default_params", "vo_dense_stereo_workspace", "vo_dense_stereo",
+    "vo_svo_set_dense_stereo", "vo_svo_get_dense_stereo", "vo_svo_get_dense_points",
     "vo_semidense_temporal_default_params", "vo_semidense_map_seed", "vo_semidense_temporal", "vo_semidense_map_points",
     "vo_svo_set_semidense_temporal", "vo_svo_get_semidense_map", "vo_svo_get_semidense_map_points",
     "vo_semidense_propagate_default_params", "vo_semidense_map_propagate", "vo_svo_set_semidense_propagate", "vo_svo_get_semidense_origin",
@@ -342,6 +349,12 @@ def load():
     lib.vo_svo_set_semidense.argtypes = [vp, vp, ci]
     lib.vo_svo_get_semidense.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.vo_svo_get_semidense_points.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp]
+    lib.vo_dense_stereo_default_params.argtypes = [vp]
+    lib.vo_dense_stereo_workspace.argtypes = [ci, ci, vp, vp]
+    lib.vo_dense_stereo.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, ci]
+    lib.vo_svo_set_dense_stereo.argtypes = [vp, vp, ci]
+    lib.vo_svo_get_dense_stereo.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.vo_svo_get_dense_points.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp]
     lib.vo_semidense_temporal_default_params.argtypes = [vp]
     lib.vo_semidense_map_seed.argtypes = [vp, vp, vp, vp, ci, ci, C.c_float, vp, vp, vp, vp, ci]
     lib.vo_semidense_temporal.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci]

@@ -114,6 +114,45 @@ def _semidense_params(lib, params):
     return p
 
 
+class DenseStereoResult(collections.namedtuple("DenseStereoResult", "disparity cost sigma_invd status frame_id T_wc n_accepted")):
+    """The planes of a dense stereo result (include/vo_hip.h, "Dense stereo"): disparity, sigma_invd float32 (height, width), cost
+    uint16, status uint8 — disparity, sigma_invd and status as a SemiDenseResult's; from a driver also the frame's id, its T_wc;
+    n_accepted: the number of accepted pixels (status 1)."""
+    __slots__ = ()
+
+    @property
+    def accepted(self):
+        return self.status == 1
+
+
+DENSE_STEREO_DISPARITIES = (64, 128, 192, 256)
+
+
+def _dense_stereo_params(lib, params):
+    """keyword parameters -> vo_dense_stereo_params: the C defaults, then the caller's fields. z_min [m] (with bf, in place of d_min)
+    gives d_max as the semi-dense option derives it; n_disp is then rounded up to the next allowed value and d_min = max(0, d_max + 1
+    - n_disp)."""
+    p = _capi.DenseStereoParams()
+    lib.vo_dense_stereo_default_params(C.byref(p))
+    params = dict(params)
+    z_min = params.pop("z_min", None)
+    known = {f[0] for f in _capi.DenseStereoParams._fields_}
+    for k, v in params.items():
+        if k not in known:
+            raise ValueError(f"dense stereo: unknown parameter {k!r}; known: {sorted(known)} and z_min")
+        setattr(p, k, v)
+    if z_min is not None:
+        if "d_min" in params or "bf" not in params:
+            raise ValueError("dense stereo: z_min needs bf and replaces d_min")
+        d_max = semidense_disparity_range(float(params["bf"]), float(z_min))[1]
+        fits = [n for n in DENSE_STEREO_DISPARITIES if n >= int(p.n_disp)]
+        if not fits:
+            raise ValueError(f"dense stereo: n_disp={p.n_disp}: at most {DENSE_STEREO_DISPARITIES[-1]}")
+        p.n_disp = fits[0]
+        p.d_min = max(0, d_max + 1 - p.n_disp)
+    return p
+
+
 class SemiDenseMap(collections.namedtuple("SemiDenseMap", "invd sigma n_obs tstatus score frame_id T_wc n_fused")):
     """A keyframe's semi-dense map (include/vo_hip.h, "Semi-dense temporal"): invd, sigma float32 (height, width) — both 0 where
     there is nothing yet —, n_obs, tstatus uint8; score float32 (the operator's diagnostic plane, None from a driver); from a driver
@@ -651,6 +690,34 @@ class Context:
         self.check(self.lib.vo_semidense_stereo(self._h, int(slot_l), int(slot_r), C.byref(p), d.ctypes.data, sc.ctypes.data, sg.ctypes.data,
                                                 st.ctypes.data, 0))
         return SemiDenseResult(d, sc, sg, st, None, None, int((st == 1).sum()))
+
+    # ---- dense stereo disparity (include/vo_hip.h, "Dense stereo") ---------------------------------------------------------------
+    def denseStereo(self, slot_l, slot_r, out=None, **params):
+        """Dense disparity (census + semi-global matching) of the rectified pair in slot_l / slot_r (level 0; the left slot's ignore
+        mask applies): a DenseStereoResult of (height, width) planes. params: the fields of vo_dense_stereo_params (d_min, n_disp,
+        paths, p1, p2, uniqueness, lr_max, eps_d, bf), or z_min [m] with bf in place of d_min. out: dict(disparity=, cost=,
+        sigma_invd=, status=) of DEVICE addresses (any may be missing) — the planes are then written there, tightly packed, and
+        None is returned. The planes go into semiDensePoints, semiDenseMapSeed and SemiDenseWorld.integrate as a SemiDenseResult's."""
+        p = _dense_stereo_params(self.lib, params)
+        if out is not None:
+            ptr = [C.c_void_p(out.get(k)) if out.get(k) else None for k in ("disparity", "cost", "sigma_invd", "status")]
+            self.check(self.lib.vo_dense_stereo(self._h, int(slot_l), int(slot_r), C.byref(p), *ptr, 1))
+            return None
+        w, h = self.slot_image_size(slot_l)
+        if w <= 0:
+            raise VoError(-1, f"slot {slot_l} holds no image")
+        d, sg = (np.zeros((h, w), np.float32) for _ in range(2))
+        co, st = np.zeros((h, w), np.uint16), np.zeros((h, w), np.uint8)
+        self.check(self.lib.vo_dense_stereo(self._h, int(slot_l), int(slot_r), C.byref(p), d.ctypes.data, co.ctypes.data, sg.ctypes.data,
+                                            st.ctypes.data, 0))
+        return DenseStereoResult(d, co, sg, st, None, None, int((st == 1).sum()))
+
+    def denseStereoWorkspace(self, width, height, **params):
+        """bytes of device memory denseStereo's workspace takes for a width x height pair (two census planes and the summed volume)"""
+        p = _dense_stereo_params(self.lib, params)
+        n = C.c_size_t()
+        self.check(self.lib.vo_dense_stereo_workspace(int(width), int(height), C.byref(p), C.byref(n)))
+        return n.value
 
     def semiDensePoints(self, disparity, sigma_invd, status, K, bf, T=None, capacity=None, on_device=None):
         """The accepted pixels of semi-dense planes in raster order: (xyz float32 [n, 3], sigma_invd float32 [n], pixel uint16
@@ -1833,7 +1900,7 @@ class StereoVO:
     def __init__(self, ctx, width, height, Kl, Kr, T_lr, n_bins_u, n_bins_v, thres_fastscore=15, window_size=21, max_level=6,
                  thres_error=80.0, thres_bidirection=0.5, thres_poseba_error=3.0, thres_alive_ratio=0.6, thres_rotation=15.0,
                  thres_trans=10.0, n_max_keyframes_in_window=9, strict_border=4, local_ba=True, rectify=False, thres_sampson=60.0,
-                 debug_image=False, pose_covariance=False, sigma_px=0.0, mask=None, zncc_gate=None, semidense=None):
+                 debug_image=False, pose_covariance=False, sigma_px=0.0, mask=None, zncc_gate=None, semidense=None, dense=None):
         """debug_image=True: every tracked frame draws the reference's img_debug_ on the device (getDebugImage).
         semidense: dict of semi-dense stereo parameters (setSemiDense; "every": "keyframe" or "frame") — depth of the keyframes' pairs;
         its "temporal": True or dict(z_max=..., max_search=...) also switches setSemiDenseTemporal on, and with it
@@ -1845,6 +1912,8 @@ class StereoVO:
         "align": True or dict(min_obs=, huber=, max_iters=, eps=, min_pixels=) setSemiDenseAlign; with levels=, max_iters_level= or
         start="odometry" | "previous" in it, coarse to fine on a map pyramid (setSemiDenseAlignPyramid); with affine=True or
         affine=dict(gain0=, offset0=) in it, gain and offset are estimated next to the pose (setSemiDenseAlignAffine).
+        dense: dict of dense stereo parameters (setDenseStereo; "every": "keyframe" or "frame"), e.g. dict(bf=, z_min=3.0,
+        n_disp=128) — a disparity for every pixel of the keyframes' pairs; independent of semidense.
         mask: the ignore mask every pair carries from the first one on (setMask).
         zncc_gate: dict(thres=, win=15, pattern="centered", pairs=("temporal",)) — the appearance gate (setZnccGate).
         pose_covariance=True: every frame chains the covariance of its pose on the device (getPoseCovariance); sigma_px > 0
@@ -1897,12 +1966,15 @@ class StereoVO:
                 self.setSemiDenseRegularize({} if regularize is True else regularize)
             if world:
                 self.setSemiDenseWorld({} if world is True else world)
+        if dense is not None:
+            ds = dict(dense)
+            self.setDenseStereo(ds, every=ds.pop("every", "keyframe"))
         self._info = SvoFrameInfo()
         self.stats_frame = []  # AlgorithmStatistics::FrameStatistics::Twc per frame (stereo_vo.cpp:979-980)
 
     @classmethod
     def from_yaml(cls, path, device=0, max_points=None, input_format="mono8", mask=None, mask_erode=0, equalize=None, zncc_gate=None,
-                  semidense=None, **overrides):
+                  semidense=None, dense=None, **overrides):
         """StereoVO(mode = "rosbag", directory_intrinsic = path) of the reference (stereo_vo.cpp:15-57, :118-280): the
         object configured by one of its config/stereo/*.yaml files. The context is created here (sized by the file) and
         closed with the object. With flagDoUndistortion the pairs go through the rectification maps and the loop runs on
@@ -1915,7 +1987,7 @@ class StereoVO:
         what cv::remap fills with 0 is not looked at), which needs flagDoUndistortion in the file.
         `equalize`: None, "clahe" (OpenCV's defaults) or dict(clip_limit=, tiles=): Context.set_equalize on the new context.
         `zncc_gate`: the constructor's (setZnccGate). `semidense`: the constructor's (setSemiDense); without "bf" the (rectified)
-        camera's focal length x baseline is filled in."""
+        camera's focal length x baseline is filled in. `dense`: the constructor's (setDenseStereo), bf filled in likewise."""
         from . import config as _config
         cfg = _config.load_stereo_config(path)
         eq = _equalize_arg(equalize)
@@ -1946,6 +2018,10 @@ class StereoVO:
                 semidense = dict(semidense)
                 semidense.setdefault("bf", float(np.asarray(Kl, np.float64).reshape(-1)[0] * np.linalg.norm(np.asarray(T_lr, np.float64).reshape(4, 4)[:3, 3])))
                 overrides = dict(overrides, semidense=semidense)
+            if dense is not None:
+                dense = dict(dense)
+                dense.setdefault("bf", float(np.asarray(Kl, np.float64).reshape(-1)[0] * np.linalg.norm(np.asarray(T_lr, np.float64).reshape(4, 4)[:3, 3])))
+                overrides = dict(overrides, dense=dense)
             obj = cls(ctx, W, H, Kl, Kr, T_lr, fe["n_bins_u"], fe["n_bins_v"], thres_fastscore=fe["thres_fastscore"],
                       window_size=ft["window_size"], max_level=ft["max_level"], thres_error=ft["thres_error"],
                       thres_sampson=ft["thres_sampson"],
@@ -2035,6 +2111,39 @@ class StereoVO:
         self.ctx.check(self.lib.vo_svo_get_semidense(self._h, d.ctypes.data, sc.ctypes.data, sg.ctypes.data, st.ctypes.data, C.byref(w), C.byref(h),
                                                      C.byref(fid), T.ctypes.data, C.byref(na)))
         return SemiDenseResult(d, sc, sg, st, fid.value, T, na.value)
+
+    def setDenseStereo(self, params, every="keyframe"):
+        """Dense stereo disparity (include/vo_hip.h, "Dense stereo") of every keyframe's — every="frame": every frame's — own
+        rectified pair, computed on the side stream behind the frame; the odometry's and the semi-dense options' results do not
+        change. params: dict of Context.denseStereo's parameters (bf is needed), None: off. Refused while a frame is in flight.
+        StereoVO only; independent of setSemiDense."""
+        if params is None:
+            self.ctx.check(self.lib.vo_svo_set_dense_stereo(self._h, None, 0))
+            return
+        if every not in self.SEMIDENSE_EVERY:
+            raise ValueError(f"every must be one of {sorted(self.SEMIDENSE_EVERY)}, not {every!r}")
+        if "bf" not in params:
+            raise ValueError("setDenseStereo: bf (focal length x baseline) is needed")
+        p = _dense_stereo_params(self.lib, params)
+        self.ctx.check(self.lib.vo_svo_set_dense_stereo(self._h, C.byref(p), self.SEMIDENSE_EVERY[every]))
+
+    def getDenseStereo(self):
+        """The last dense stereo result (a DenseStereoResult with frame_id, T_wc (4, 4) and n_accepted), None before any. Waits for
+        that result's launches only."""
+        w, h, fid, na = C.c_int(), C.c_int(), C.c_int(), C.c_int()
+        T = np.zeros((4, 4), np.float32)
+        self.ctx.check(self.lib.vo_svo_get_dense_stereo(self._h, None, None, None, None, C.byref(w), C.byref(h), C.byref(fid), None, None))
+        if w.value <= 0:
+            return None
+        d, sg = (np.zeros((h.value, w.value), np.float32) for _ in range(2))
+        co, st = np.zeros((h.value, w.value), np.uint16), np.zeros((h.value, w.value), np.uint8)
+        self.ctx.check(self.lib.vo_svo_get_dense_stereo(self._h, d.ctypes.data, co.ctypes.data, sg.ctypes.data, st.ctypes.data, C.byref(w), C.byref(h),
+                                                        C.byref(fid), T.ctypes.data, C.byref(na)))
+        return DenseStereoResult(d, co, sg, st, fid.value, T, na.value)
+
+    def getDensePoints(self, world=True, capacity=None):
+        """The accepted pixels of the last dense stereo result as points, raster order: getSemiDensePoints' dict; None before any."""
+        return self._semidense_points(lambda *a: self.lib.vo_svo_get_dense_points(self._h, int(bool(world)), *a), capacity)
 
     def setSemiDenseTemporal(self, params):
         """The temporal search and fusion (include/vo_hip.h, "Semi-dense temporal"): every keyframe's static result seeds a map that

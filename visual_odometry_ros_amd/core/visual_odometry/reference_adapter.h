@@ -479,6 +479,16 @@ class StereoVO {
     for (size_t i = 0; i < v.size(); ++i) o[i] = Point(v[i].x, v[i].y, v[i].z);
     return o;
   }
+  // NOT in the reference's StereoVO (vo::StereoVO::setDenseStereo): a dense disparity (census + semi-global matching) of every
+  // keyframe's pair; getDensePoints() is what convertPointVecToPointCloud2 of the node takes
+  void setDenseStereo(const vo_dense_stereo_params *prm, int every = VO_SEMIDENSE_KEYFRAMES) { impl_.setDenseStereo(prm, every); }
+  PointVec getDensePoints(bool world = true) {
+    vo::PointVec v;
+    impl_.getDensePoints(v, nullptr, world);
+    PointVec o(v.size());
+    for (size_t i = 0; i < v.size(); ++i) o[i] = Point(v[i].x, v[i].y, v[i].z);
+    return o;
+  }
   // the temporal half of that prototype (vo::StereoVO::setSemiDenseTemporal): the keyframe's depth fused with the following frames;
   // getSemiDenseMapPoints() is the last keyframe's map, the pixels seen at least min_obs times
   void setSemiDenseTemporal(const vo_semidense_temporal_params *prm) { impl_.setSemiDenseTemporal(prm); }

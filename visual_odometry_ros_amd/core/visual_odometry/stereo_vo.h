@@ -262,6 +262,32 @@ class StereoVO {
                                                    sigma_invd ? sigma_invd->data() : nullptr, nullptr, &n, &fid));
     return fid >= 0;
   }
+  // Dense stereo disparity (vo_svo_set_dense_stereo; include/vo_hip.h, "Dense stereo"): census + semi-global matching on every
+  // keyframe's (every = VO_SEMIDENSE_FRAMES: every frame's) own rectified pair, on the side stream behind the frame — a disparity
+  // for walls and road too, less exact than the semi-dense one; the odometry does not change. Independent of setSemiDense.
+  // prm = nullptr: off. defaultDenseStereoParams(bf) fills in the defaults for a focal length x baseline: the disparities
+  // d_min .. d_min + n_disp - 1 (n_disp 64, 128, 192 or 256) are searched. Throws while a frame is in flight.
+  static vo_dense_stereo_params defaultDenseStereoParams(float bf, int n_disp = 64, int d_min = 0) {
+    vo_dense_stereo_params p;
+    vo_dense_stereo_default_params(&p);
+    p.bf = bf;
+    p.n_disp = n_disp;
+    p.d_min = d_min;
+    return p;
+  }
+  void setDenseStereo(const vo_dense_stereo_params *prm, int every = VO_SEMIDENSE_KEYFRAMES) { ctx_->check(vo_svo_set_dense_stereo(svo_, prm, every)); }
+  // the accepted pixels of the last dense result as points, as getSemiDensePoints; waits for that result's launches only
+  bool getDensePoints(PointVec &xyz, std::vector<float> *sigma_invd = nullptr, bool world = true, int *frame_id = nullptr) {
+    int n = 0, fid = -1;
+    const int rc = vo_svo_get_dense_points(svo_, world ? 1 : 0, 0, nullptr, nullptr, nullptr, &n, &fid);
+    if (rc != VO_ERR_CAPACITY) ctx_->check(rc);  // (room for none: the count is what was asked for)
+    xyz.resize((size_t)n);
+    if (sigma_invd) sigma_invd->resize((size_t)n);
+    if (frame_id) *frame_id = fid;
+    if (n) ctx_->check(vo_svo_get_dense_points(svo_, world ? 1 : 0, n, reinterpret_cast<float *>(xyz.data()),
+                                               sigma_invd ? sigma_invd->data() : nullptr, nullptr, &n, &fid));
+    return fid >= 0;
+  }
   // The temporal half of that prototype (vo_svo_set_semidense_temporal; include/vo_hip.h, "Semi-dense temporal"): every keyframe's
   // static result seeds a map that each later frame until the next keyframe updates on the side stream (an epipolar search along
   // the odometry's pose, Gaussian fusion of the inverse depths). Needs setSemiDense. prm = nullptr: off. Throws while a frame is in flight.

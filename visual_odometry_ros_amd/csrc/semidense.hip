@@ -91,6 +91,7 @@ static int sd_points_alloc(vo_ctx *c, vo_sd_buffers *b) {
   VO_CHECK_HIP(c, vo_dev_malloc(c, (void **)&b->pts, b->npix * (4 * sizeof(float) + 2 * sizeof(uint16_t))));
   return VO_OK;
 }
+int vo_sd_points_alloc(vo_ctx *c, vo_sd_buffers *b) { return sd_points_alloc(c, b); }
 
 struct vo_semidense_state {
   vo_sd_buffers buf;

@@ -278,6 +278,7 @@ extern "C" void vo_svo_destroy(vo_svo *s) {
   vo_driver_mask_free(&s->mask);
   vo_zncc_gate_free(&s->zncc);
   vo_svo_semidense_free(s);
+  vo_svo_dense_stereo_free(s);
   vo_svo_lba_free(s);
   delete s;
 }
@@ -358,6 +359,7 @@ extern "C" int vo_svo_prefetch(vo_svo *s, const void *left, const void *right, i
   VO_CHECK_HIP(s->c, hipSetDevice(s->c->device));
   s->prefetched = false;  // (whatever was handed over before is overwritten from here on, also if this fails half-way)
   RC(vo_svo_semidense_guard(s, s->slot[S_NL], s->slot[S_NR]));
+  RC(vo_svo_dense_stereo_guard(s, s->slot[S_NL], s->slot[S_NR]));
   RC(svo_bind_mask(s));
   RC(svo_ingest(s, left, right, stride, on_device, true, true));
   if (g_trace) s->ht.acc[2] += svo_now() - t_in;
@@ -465,6 +467,7 @@ extern "C" int vo_svo_enqueue(vo_svo *s, const void *left, const void *right, in
     // the synchronous call builds its pyramids on the MAIN stream — behind that launch, then (one event; nothing in the loop)
     RC(vo_frame_candidates_abandon(c, s->tab_next));
     RC(vo_svo_semidense_guard(s, s->slot[S_NL], s->slot[S_NR]));
+    RC(vo_svo_dense_stereo_guard(s, s->slot[S_NL], s->slot[S_NR]));
     RC(svo_bind_mask(s));
     deferred = !s->first && s->c->ingest_side;
     if (deferred && !s->prm.rectify && s->n > 0 && vo_orb_cand_table(c, s->tab_next)) {
@@ -676,6 +679,7 @@ extern "C" int vo_svo_result(vo_svo *s, vo_svo_frame_info *info) {
     if (info) *info = I;
     if (s->sda.on) s->sda.have = false, s->sda.frame_id = I.frame_id;  // (vo_svo_set_semidense_align: the first frame has no result)
     if (s->sd.on && s->sd.every == VO_SEMIDENSE_FRAMES) RC(vo_svo_semidense_enqueue(s, s->slot[S_CL], s->slot[S_CR], I.frame_id, I.T_wc));
+    if (s->ds.on && s->ds.every == VO_SEMIDENSE_FRAMES) RC(vo_svo_dense_stereo_enqueue(s, s->slot[S_CL], s->slot[S_CR], I.frame_id, I.T_wc));
     return VO_OK;
   }
   // the BA launch's epilogue wrote the loop's counts (pinned block) in front of the frame's sequence word
@@ -768,6 +772,9 @@ extern "C" int vo_svo_result(vo_svo *s, vo_svo_frame_info *info) {
     RC(vo_svo_semidense_enqueue(s, s->slot[S_CL], s->slot[S_CR], I.frame_id, T_wc));
   // the keyframe's map (vo_svo_set_semidense_temporal): seeded behind a keyframe's static launch, fused with every later frame
   if (s->sd.on && s->sdt.on) RC(vo_svo_semidense_temporal_enqueue(s, s->slot[S_CL], I.is_keyframe, I.frame_id, T_wc));
+  // the dense disparity of this frame's own pair (vo_svo_set_dense_stereo), by the same rules, behind the semi-dense launches
+  if (s->ds.on && (I.is_keyframe || s->ds.every == VO_SEMIDENSE_FRAMES))
+    RC(vo_svo_dense_stereo_enqueue(s, s->slot[S_CL], s->slot[S_CR], I.frame_id, T_wc));
   if (g_trace) {
     s->ht.t_ret = svo_now();
     ++s->ht.n_all;

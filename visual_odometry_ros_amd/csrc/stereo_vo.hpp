@@ -31,6 +31,20 @@ struct vo_svo_semidense {
   float T_wc[16] = {};
 };
 
+// vo_svo_set_dense_stereo (dense_stereo.hip): the option's state, with the rules of vo_svo_semidense and events of its own. `buf`:
+// the result's planes (cost in the score plane) and the points list's scratch; `ws`: the workspace. Both made at the first enable.
+struct vo_svo_dense_stereo {
+  bool on = false, have = false;
+  unsigned busy = 0;
+  int every = 0;
+  vo_dense_stereo_params prm = {};
+  vo_ds_buffers ws;
+  vo_sd_buffers buf;
+  hipEvent_t fork = nullptr, done = nullptr;
+  int w = 0, h = 0, frame_id = -1;
+  float T_wc[16] = {};
+};
+
 // vo_svo_set_semidense_temporal (semidense_temporal.hip): the last keyframe's left plane and its map. The launches run on the side
 // stream behind the static option's, one after the other (the map needs no second copy), and share its events: `sd.done` is
 // recorded behind each, `sd.busy` takes the current left slot.
@@ -167,6 +181,7 @@ struct vo_svo {
   vo_svo_semidense_align sda;  // vo_svo_set_semidense_align: every later frame's left image aligned against that map
   vo_svo_semidense_regularize sdr;  // vo_svo_set_semidense_regularize: a regularised copy of that map behind every launch that writes it
   vo_svo_semidense_world sdw;  // vo_svo_set_semidense_world: the keyframes' maps fused into one world-frame voxel table
+  vo_svo_dense_stereo ds;  // vo_svo_set_dense_stereo: dense disparity of the keyframes' (or every frame's) own pair
   int mono = 0;  // the keyframe storage serves a MonoVO (mono_vo.hip): one observation per keyframe entry, bundled flags
   // all_stkeyframes_ (stats_keyframe): every keyframe's current pose (host) and where its related landmarks' ids are kept
   // on the device (a pool that only grows)
@@ -196,6 +211,9 @@ int vo_svo_lba_update_points(vo_svo *s, const SvoTrackSet &ts, int n);  // a lan
 int vo_svo_semidense_enqueue(vo_svo *s, int slot_l, int slot_r, int frame_id, const float T_wc[16]);  // semidense.hip
 int vo_svo_semidense_guard(vo_svo *s, int a, int b);
 void vo_svo_semidense_free(vo_svo *s);
+int vo_svo_dense_stereo_enqueue(vo_svo *s, int slot_l, int slot_r, int frame_id, const float T_wc[16]);  // dense_stereo.hip
+int vo_svo_dense_stereo_guard(vo_svo *s, int a, int b);
+void vo_svo_dense_stereo_free(vo_svo *s);
 int vo_svo_semidense_temporal_enqueue(vo_svo *s, int slot_l, int is_keyframe, int frame_id, const float T_wc[16]);  // semidense_temporal.hip
 void vo_svo_semidense_temporal_free(vo_svo *s);
 // semidense_propagate.hip, both on the side stream at a keyframe with the option on: the scatter in front of the key-plane copy

@@ -132,6 +132,7 @@ struct vo_ctx {
   struct vo_semidense_propagate_state *semidense_p;  // vo_semidense_map_propagate: its keys and, for host planes, the new map's device copies
   struct vo_semidense_align_state *semidense_a;  // vo_semidense_align: its state block and partial sums
   struct vo_semidense_regularize_state *semidense_r;  // vo_semidense_map_regularize with host planes: the mask's and the outputs' device copies
+  struct vo_dense_stereo_state *dense_stereo;  // vo_dense_stereo: its workspace and, for host outputs, the planes (dense_stereo.hip), made on first use
 };
 
 static inline hipError_t vo_dev_malloc(vo_ctx *c, void **p, size_t bytes) {
@@ -264,11 +265,25 @@ int vo_sd_enqueue(vo_ctx *c, int slot_l, int slot_r, const vo_semidense_params *
                   int *wg_accepted, int *W_out, int *H_out);
 
 int vo_sd_ctx_buffers(vo_ctx *c, vo_sd_buffers **b);  // the context's own buffers, made on first use
+int vo_sd_points_alloc(vo_ctx *c, vo_sd_buffers *b);  // the points list's device outputs, ahead of its first call
 // the points of DEVICE planes (host outputs), synchronous on c->stream; vo_sd_points_keyed: b->key is written already (the caller's rule)
 int vo_sd_points(vo_ctx *c, vo_sd_buffers *b, const float *d_disp, const float *d_sigma, const uint8_t *d_status, int W, int H,
                  const float K[4], float bf, const float *T, int cap, float *xyz, float *sigma_out, uint16_t *pixel, int *n);
 int vo_sd_points_keyed(vo_ctx *c, vo_sd_buffers *b, const float *d_disp, const float *d_sigma, int W, int H, const float K[4], float bf,
                        const float *T, int cap, float *xyz, float *sigma_out, uint16_t *pixel, int *n);
+
+// Dense stereo disparity (dense_stereo.hip; include/vo_hip.h, "Dense stereo"): the workspace (two census planes and the summed
+// volume, in one allocation that grows when a call needs more). A result's four planes live in a vo_sd_buffers (the u16 cost plane in
+// its score plane), whose scratch the points list needs anyway.
+struct vo_ds_buffers {
+  void *ws = nullptr;
+  size_t ws_bytes = 0;
+};
+void vo_ds_buffers_free(vo_ds_buffers *b);
+void vo_dense_stereo_free(vo_ctx *c);
+// the launches on c->stream, into device planes (any may be null)
+int vo_ds_enqueue(vo_ctx *c, vo_ds_buffers *b, int slot_l, int slot_r, const vo_dense_stereo_params *p, float *disp, uint16_t *cost, float *sigma,
+                  uint8_t *status, int *W_out, int *H_out);
 
 // The temporal semi-dense search (semidense_temporal.hip; include/vo_hip.h, "Semi-dense temporal"): a key plane, the four planes of a
 // map and — the context's operator — the score plane or — a driver's option — the keyframe's ignore mask: one allocation sized by
