@@ -42,7 +42,9 @@ changes between a keyframe and its frames; status 5: they left their range); the
 distance, in front of the start.
 --dense DIR [--dense-every frame] [--dense-disparities N] [--dense-paths 4|8]: a dense disparity (census + semi-global matching) of
 every keyframe's (or every frame's) pair, independent of --semidense; `dense_<frame id>.ply` per result in DIR, as the semi-dense
-files. N (default 128) disparities are searched, ending at a depth of 3 m."""
+files. N (default 128) disparities are searched, ending at a depth of 3 m.
+--dense-speckle [MAX_SIZE] [--dense-speckle-diff D]: with --dense, the speckle filter behind every dense result: connected components
+(4-neighbours, disparities at most D = 1 px apart) of at most MAX_SIZE (default 100) pixels are left out of the files."""
 import argparse
 import os
 import sys
@@ -103,16 +105,28 @@ def zncc_options(args):
 def dense_options(args):
     """--dense DIR [--dense-every frame] [--dense-disparities N] [--dense-paths 4|8] as the `dense` argument of from_yaml: a dense
     disparity (census + semi-global matching) of every keyframe's (or every frame's) pair; bf comes from the file's camera, the range
-    from a smallest depth of 3 m"""
+    from a smallest depth of 3 m. --dense-speckle [MAX_SIZE] [--dense-speckle-diff D]: its "speckle" entry"""
     if args.dense is None:
         if args.dense_every is not None or args.dense_disparities is not None or args.dense_paths is not None:
             raise SystemExit("--dense-every / --dense-disparities / --dense-paths need --dense DIR")
+        if args.dense_speckle is not None or args.dense_speckle_diff is not None:
+            raise SystemExit("--dense-speckle / --dense-speckle-diff need --dense DIR")
         return {}
+    if args.dense_speckle is None and args.dense_speckle_diff is not None:
+        raise SystemExit("--dense-speckle-diff needs --dense-speckle")
+    if args.dense_speckle is not None and args.dense_speckle < 0:
+        raise SystemExit("--dense-speckle MAX_SIZE: >= 0")
+    if args.dense_speckle_diff is not None and not 0 <= args.dense_speckle_diff < float("inf"):
+        raise SystemExit("--dense-speckle-diff D: finite and >= 0")
     if args.dense_disparities is not None and not 1 <= args.dense_disparities <= 256:
         raise SystemExit("--dense-disparities N: 1..256 (rounded up to 64, 128, 192 or 256)")
     ds = {"z_min": 3.0, "n_disp": args.dense_disparities or 128, "every": args.dense_every or "keyframe"}
     if args.dense_paths is not None:
         ds["paths"] = args.dense_paths
+    if args.dense_speckle is not None:
+        ds["speckle"] = {"max_size": args.dense_speckle}
+        if args.dense_speckle_diff is not None:
+            ds["speckle"]["max_diff"] = args.dense_speckle_diff
     return {"dense": ds}
 
 
@@ -286,6 +300,10 @@ def parse_args(argv=None):
     ap.add_argument("--dense-disparities", type=int, default=None, metavar="N",
                     help="disparities searched by --dense (default 128; rounded up to 64, 128, 192 or 256), ending at a depth of 3 m")
     ap.add_argument("--dense-paths", type=int, choices=(4, 8), default=None, help="aggregation paths of --dense (default 8)")
+    ap.add_argument("--dense-speckle", type=int, nargs="?", const=100, default=None, metavar="MAX_SIZE",
+                    help="--dense: remove connected components of at most MAX_SIZE (default 100) pixels from every dense result")
+    ap.add_argument("--dense-speckle-diff", type=float, default=None, metavar="D",
+                    help="--dense-speckle: neighbours belong to one component where their disparities differ by at most D (default 1.0) px")
     return ap.parse_args(argv)
 
 

@@ -873,6 +873,54 @@ int vo_svo_get_dense_stereo(vo_svo *svo, float *disparity, uint16_t *cost, float
                             int *frame_id, float T_wc[16], int *n_accepted);
 int vo_svo_get_dense_points(vo_svo *svo, int world, int cap, float *xyz, float *sigma_invd, uint16_t *pixel, int *n, int *frame_id);
 
+/* ---- Speckle filter: small connected components of a disparity plane removed --------------------------------
+ * Small islands of wrong disparity survive the dense operator's uniqueness and left-right checks; in a point cloud or the voxel
+ * map they are floating blobs. This operator labels the connected components of (disparity, sigma_invd, status) planes — W x H,
+ * tightly packed, with the meaning they have under "Semi-dense stereo" and "Dense stereo" — and removes the small ones, in
+ * place. 1 <= W, H <= 65535 and W H <= 2^31 - 1. tests/dense_speckle_restatement.py restates it.
+ *   valid      a pixel with status == 1.
+ *   joined     two 4-neighbours p, q (left/right, up/down) that are both valid with fabsf(disparity[p] - disparity[q]) <= max_diff:
+ *              float32, one subtraction, rounded; a NaN result fails the comparison (so a NaN or an infinite disparity under
+ *              status 1 joins nothing).
+ *   component  a connected component of the graph of joined pairs over the valid pixels; its label is the smallest raster index
+ *              y W + x among its pixels, its size the number of its pixels. Neither depends on any order of arrival.
+ *   removal    every pixel of a component with size <= max_size: status = VO_DISPARITY_SPECKLE (6), disparity = 0 and (where the
+ *              plane is given) sigma_invd = 0. Every other pixel, valid or not, keeps every bit; a cost or score plane is not
+ *              touched. max_size = 0 removes nothing (the labels, sizes and counts are still computed).
+ *   params     0 <= max_size; max_diff >= 0, finite [pixel].
+ * vo_disparity_speckle_filter: disparity and status are required; sigma_invd, label, size, n_removed and n_components may be
+ * NULL. label, size: W x H int32 planes describing the components BEFORE the removal — a pixel's label and its component's size;
+ * -1 and 0 on invalid pixels. n_components: the number of components (all of them); n_removed: the number of removed pixels (host
+ * integers also with on_device). on_device: the planes, label and size are device memory. Synchronous. The workspace — 16 bytes
+ * of counters and two int32 planes: 16 + 8 W H bytes, what vo_speckle_workspace reports — belongs to the context, is allocated at
+ * the first call and grows when a later call needs more; host planes also take a device copy of 9 W H bytes that grows likewise.
+ * An allocation that fails is VO_ERR_HIP.
+ *
+ * StereoVO (off by default; with it off no launch, wait, allocation or result bit differs): vo_svo_set_dense_speckle(svo, prm) —
+ * prm NULL = off — needs vo_svo_set_dense_stereo to be on. Its only allocation, at the first enable: the workspace for
+ * max_width x max_height. The filter's launches follow the dense decision on the side stream, in front of that result's event,
+ * in place on the driver's dense planes: vo_svo_get_dense_stereo returns the filtered planes (n_accepted counts status 1, so it
+ * falls by the pixels removed), vo_svo_get_dense_points leaves the speckles out, and the guard of the slots covers them
+ * unchanged. vo_svo_get_dense_speckle_stats: n_removed and n_components of the last result (0, 0 before any that went through
+ * the filter; either may be NULL); waits for that result's event only. Both: VO_ERR_INVALID while a frame is in flight and on a
+ * MonoVO's driver; the getter also with the option off.
+ * Out of scope: the driver's world map, temporal map or propagation taking the dense result as their source (still the
+ * follow-up, now with a filter in front of it); a median filter; hole filling; 8-connectivity; fixed-point disparities as
+ * OpenCV's filterSpeckles takes; the filter on the driver's semi-dense result (the operator takes any planes, but a map of thin
+ * edges would lose most of itself); MonoVO and vo_batch. */
+#define VO_DISPARITY_SPECKLE 6 /* status of a removed pixel (the semi-dense operator uses 0..5) */
+typedef struct {
+  int max_size;   /* 100 */
+  float max_diff; /* 1.0 */
+} vo_speckle_params;
+int vo_speckle_default_params(vo_speckle_params *prm);
+int vo_speckle_workspace(int width, int height, size_t *bytes);
+int vo_disparity_speckle_filter(vo_ctx *ctx, float *disparity, float *sigma_invd, uint8_t *status, int width, int height,
+                                const vo_speckle_params *prm, int32_t *label, int32_t *size, int *n_removed, int *n_components,
+                                int on_device);
+int vo_svo_set_dense_speckle(vo_svo *svo, const vo_speckle_params *prm);
+int vo_svo_get_dense_speckle_stats(vo_svo *svo, int *n_removed, int *n_components);
+
 /* ---- Semi-dense temporal: the keyframe's pixels searched in the following left images, fused per keyframe ----
  * The second half of the reference author's semi-dense prototype, read for intent only: a pixel of the keyframe's left image is
  * searched in a later left image along the epipolar line the odometry's pose gives, and the inverse depths are fused as

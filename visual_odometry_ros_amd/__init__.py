@@ -13,4 +13,4 @@ from .api import (Context, FeatureTracker, MotionEstimator, FeatureExtractor,  #
                   se3_adjoint, SemiDenseResult, SemiDenseMap, semidense_disparity_range, SemiDensePropagated, SemiDenseAligned, SemiDenseAlignedLevel,
                   SEMIDENSE_ALIGN_STATUS, SemiDenseAlignedAffineLevel, SEMIDENSE_ALIGN_AFFINE_STATUS,
                   SemiDenseRegularized, SEMIDENSE_RSTATUS, SemiDenseWorld, SemiDenseWorldPoints, SemiDenseWorldFreePoints, SEMIDENSE_WORLD_SOURCE,
-                  DenseStereoResult, DENSE_STEREO_DISPARITIES)
+                  DenseStereoResult, DENSE_STEREO_DISPARITIES, SpeckleResult, DISPARITY_SPECKLE)

@@ -113,6 +113,10 @@ class DenseStereoParams(C.Structure):  # vo_dense_stereo_params
                 ("lr_max", C.c_int), ("eps_d", C.c_float), ("bf", C.c_float)]
 
 
+class SpeckleParams(C.Structure):  # vo_speckle_params
+    _fields_ = [("max_size", C.c_int), ("max_diff", C.c_float)]
+
+
 class SemiDenseTemporalParams(C.Structure):  # vo_semidense_temporal_params
     _fields_ = [("hw", C.c_int), ("hh", C.c_int), ("g_min", C.c_int), ("thres_best", C.c_float), ("thres_peak", C.c_float),
                 ("peak_px", C.c_int), ("edge_px", C.c_int), ("eps_edge", C.c_float), ("eps_epi", C.c_float), ("eps_scale", C.c_float),
@@ -227,6 +231,8 @@ SYMBOLS = [
     "vo_svo_set_semidense", "vo_svo_get_semidense", "vo_svo_get_semidense_points",
     "vo_dense_stereo_default_params", "vo_dense_stereo_workspace", "vo_dense_stereo",
     "vo_svo_set_dense_stereo", "vo_svo_get_dense_stereo", "vo_svo_get_dense_points",
+    "vo_speckle_default_params", "vo_speckle_workspace", "vo_disparity_speckle_filter",
+    "vo_svo_set_dense_speckle", "vo_svo_get_dense_speckle_stats",
     "vo_semidense_temporal_default_params", "vo_semidense_map_seed", "vo_semidense_temporal", "vo_semidense_map_points",
     "vo_svo_set_semidense_temporal", "vo_svo_get_semidense_map", "vo_svo_get_semidense_map_points",
     "vo_semidense_propagate_default_params", "vo_semidense_map_propagate", "vo_svo_set_semidense_propagate", "vo_svo_get_semidense_origin",
@@ -355,6 +361,11 @@ def load():
     lib.vo_svo_set_dense_stereo.argtypes = [vp, vp, ci]
     lib.vo_svo_get_dense_stereo.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.vo_svo_get_dense_points.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp]
+    lib.vo_speckle_default_params.argtypes = [vp]
+    lib.vo_speckle_workspace.argtypes = [ci, ci, vp]
+    lib.vo_disparity_speckle_filter.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, ci]
+    lib.vo_svo_set_dense_speckle.argtypes = [vp, vp]
+    lib.vo_svo_get_dense_speckle_stats.argtypes = [vp, vp, vp]
     lib.vo_semidense_temporal_default_params.argtypes = [vp]
     lib.vo_semidense_map_seed.argtypes = [vp, vp, vp, vp, ci, ci, C.c_float, vp, vp, vp, vp, ci]
     lib.vo_semidense_temporal.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci]

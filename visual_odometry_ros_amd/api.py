@@ -153,6 +153,29 @@ def _dense_stereo_params(lib, params):
     return p
 
 
+class SpeckleResult(collections.namedtuple("SpeckleResult", "disparity sigma_invd status label size n_removed n_components")):
+    """What the speckle filter (include/vo_hip.h, "Speckle filter") returns: the filtered planes disparity, sigma_invd float32 (height,
+    width) and status uint8 — removed pixels carry status 6 (VO_DISPARITY_SPECKLE) and zeros; None for planes in device memory, which
+    are filtered in place —, with labels=True the int32 planes label and size of the components before the removal (-1 and 0 on
+    invalid pixels; else None), the number of removed pixels and the number of components."""
+    __slots__ = ()
+
+
+DISPARITY_SPECKLE = 6  # VO_DISPARITY_SPECKLE
+
+
+def _speckle_params(lib, params):
+    """True or keyword parameters -> vo_speckle_params: the C defaults, then the caller's fields (max_size, max_diff)"""
+    p = _capi.SpeckleParams()
+    lib.vo_speckle_default_params(C.byref(p))
+    known = {f[0] for f in _capi.SpeckleParams._fields_}
+    for k, v in ({} if params is True else dict(params)).items():
+        if k not in known:
+            raise ValueError(f"speckle filter: unknown parameter {k!r}; known: {sorted(known)}")
+        setattr(p, k, v)
+    return p
+
+
 class SemiDenseMap(collections.namedtuple("SemiDenseMap", "invd sigma n_obs tstatus score frame_id T_wc n_fused")):
     """A keyframe's semi-dense map (include/vo_hip.h, "Semi-dense temporal"): invd, sigma float32 (height, width) — both 0 where
     there is nothing yet —, n_obs, tstatus uint8; score float32 (the operator's diagnostic plane, None from a driver); from a driver
@@ -692,16 +715,24 @@ class Context:
         return SemiDenseResult(d, sc, sg, st, None, None, int((st == 1).sum()))
 
     # ---- dense stereo disparity (include/vo_hip.h, "Dense stereo") ---------------------------------------------------------------
-    def denseStereo(self, slot_l, slot_r, out=None, **params):
+    def denseStereo(self, slot_l, slot_r, out=None, speckle=None, **params):
         """Dense disparity (census + semi-global matching) of the rectified pair in slot_l / slot_r (level 0; the left slot's ignore
         mask applies): a DenseStereoResult of (height, width) planes. params: the fields of vo_dense_stereo_params (d_min, n_disp,
         paths, p1, p2, uniqueness, lr_max, eps_d, bf), or z_min [m] with bf in place of d_min. out: dict(disparity=, cost=,
         sigma_invd=, status=) of DEVICE addresses (any may be missing) — the planes are then written there, tightly packed, and
-        None is returned. The planes go into semiDensePoints, semiDenseMapSeed and SemiDenseWorld.integrate as a SemiDenseResult's."""
+        None is returned. The planes go into semiDensePoints, semiDenseMapSeed and SemiDenseWorld.integrate as a SemiDenseResult's.
+        speckle: True or dict(max_size=, max_diff=) — a convenience: disparitySpeckleFilter behind the decision, on the same stream
+        (with `out`, in place on its disparity and status, which are then needed, and its sigma_invd where given)."""
         p = _dense_stereo_params(self.lib, params)
+        sp = None if speckle is None or speckle is False else _speckle_params(self.lib, speckle)
         if out is not None:
+            if sp is not None and not (out.get("disparity") and out.get("status")):
+                raise ValueError("denseStereo: speckle needs the disparity and status planes in out")
             ptr = [C.c_void_p(out.get(k)) if out.get(k) else None for k in ("disparity", "cost", "sigma_invd", "status")]
             self.check(self.lib.vo_dense_stereo(self._h, int(slot_l), int(slot_r), C.byref(p), *ptr, 1))
+            if sp is not None:
+                w, h = self.slot_image_size(slot_l)
+                self.check(self.lib.vo_disparity_speckle_filter(self._h, ptr[0], ptr[2], ptr[3], w, h, C.byref(sp), None, None, None, None, 1))
             return None
         w, h = self.slot_image_size(slot_l)
         if w <= 0:
@@ -710,7 +741,43 @@ class Context:
         co, st = np.zeros((h, w), np.uint16), np.zeros((h, w), np.uint8)
         self.check(self.lib.vo_dense_stereo(self._h, int(slot_l), int(slot_r), C.byref(p), d.ctypes.data, co.ctypes.data, sg.ctypes.data,
                                             st.ctypes.data, 0))
+        if sp is not None:
+            self.check(self.lib.vo_disparity_speckle_filter(self._h, d.ctypes.data, sg.ctypes.data, st.ctypes.data, w, h, C.byref(sp), None, None,
+                                                            None, None, 0))
         return DenseStereoResult(d, co, sg, st, None, None, int((st == 1).sum()))
+
+    # ---- speckle filter for disparity planes (include/vo_hip.h, "Speckle filter") ------------------------------------------------
+    def disparitySpeckleFilter(self, disparity, sigma_invd, status, max_size=100, max_diff=1.0, labels=False, on_device=None):
+        """The connected components (4-neighbours, |Δdisparity| <= max_diff) of the accepted pixels of disparity planes — a dense or
+        semi-dense result's — labelled on the device, those of at most max_size pixels removed: a SpeckleResult. The planes are
+        arrays (sigma_invd may be None), which are not changed: the result holds the filtered copies, and with labels=True the label
+        and size planes. Or DEVICE addresses with on_device=(width, height) (sigma_invd may be None): filtered in place; labels is
+        then False or dict(label=, size=) of DEVICE addresses (either may be missing), and the result holds the two counts only."""
+        p = _speckle_params(self.lib, dict(max_size=max_size, max_diff=max_diff))
+        nr, nc = C.c_int(), C.c_int()
+        if on_device is not None:
+            w, h = on_device
+            lab = labels if isinstance(labels, dict) else {}
+            self.check(self.lib.vo_disparity_speckle_filter(self._h, C.c_void_p(disparity), C.c_void_p(sigma_invd) if sigma_invd else None,
+                                                            C.c_void_p(status), int(w), int(h), C.byref(p),
+                                                            C.c_void_p(lab["label"]) if lab.get("label") else None,
+                                                            C.c_void_p(lab["size"]) if lab.get("size") else None, C.byref(nr), C.byref(nc), 1))
+            return SpeckleResult(None, None, None, None, None, nr.value, nc.value)
+        d, st = np.array(disparity, np.float32, order="C"), np.array(status, np.uint8, order="C")
+        sg = None if sigma_invd is None else np.array(sigma_invd, np.float32, order="C")
+        if d.ndim != 2 or st.shape != d.shape or (sg is not None and sg.shape != d.shape):
+            raise ValueError("disparity, sigma_invd and status are planes of one (height, width)")
+        lab, sz = (np.zeros(d.shape, np.int32) for _ in range(2)) if labels else (None, None)
+        self.check(self.lib.vo_disparity_speckle_filter(self._h, d.ctypes.data, None if sg is None else sg.ctypes.data, st.ctypes.data, d.shape[1],
+                                                        d.shape[0], C.byref(p), None if lab is None else lab.ctypes.data,
+                                                        None if sz is None else sz.ctypes.data, C.byref(nr), C.byref(nc), 0))
+        return SpeckleResult(d, sg, st, lab, sz, nr.value, nc.value)
+
+    def disparitySpeckleWorkspace(self, width, height):
+        """bytes of device memory disparitySpeckleFilter's workspace takes for width x height planes (counters, labels, sizes)"""
+        n = C.c_size_t()
+        self.check(self.lib.vo_speckle_workspace(int(width), int(height), C.byref(n)))
+        return n.value
 
     def denseStereoWorkspace(self, width, height, **params):
         """bytes of device memory denseStereo's workspace takes for a width x height pair (two census planes and the summed volume)"""
@@ -1913,7 +1980,8 @@ class StereoVO:
         start="odometry" | "previous" in it, coarse to fine on a map pyramid (setSemiDenseAlignPyramid); with affine=True or
         affine=dict(gain0=, offset0=) in it, gain and offset are estimated next to the pose (setSemiDenseAlignAffine).
         dense: dict of dense stereo parameters (setDenseStereo; "every": "keyframe" or "frame"), e.g. dict(bf=, z_min=3.0,
-        n_disp=128) — a disparity for every pixel of the keyframes' pairs; independent of semidense.
+        n_disp=128) — a disparity for every pixel of the keyframes' pairs; independent of semidense. Its "speckle": True or
+        dict(max_size=, max_diff=) switches setDenseSpeckle on: the small islands of each result removed.
         mask: the ignore mask every pair carries from the first one on (setMask).
         zncc_gate: dict(thres=, win=15, pattern="centered", pairs=("temporal",)) — the appearance gate (setZnccGate).
         pose_covariance=True: every frame chains the covariance of its pose on the device (getPoseCovariance); sigma_px > 0
@@ -1968,7 +2036,10 @@ class StereoVO:
                 self.setSemiDenseWorld({} if world is True else world)
         if dense is not None:
             ds = dict(dense)
+            speckle = ds.pop("speckle", None)
             self.setDenseStereo(ds, every=ds.pop("every", "keyframe"))
+            if speckle is not None and speckle is not False:
+                self.setDenseSpeckle(speckle)
         self._info = SvoFrameInfo()
         self.stats_frame = []  # AlgorithmStatistics::FrameStatistics::Twc per frame (stereo_vo.cpp:979-980)
 
@@ -2140,6 +2211,22 @@ class StereoVO:
         self.ctx.check(self.lib.vo_svo_get_dense_stereo(self._h, d.ctypes.data, co.ctypes.data, sg.ctypes.data, st.ctypes.data, C.byref(w), C.byref(h),
                                                         C.byref(fid), T.ctypes.data, C.byref(na)))
         return DenseStereoResult(d, co, sg, st, fid.value, T, na.value)
+
+    def setDenseSpeckle(self, params=True):
+        """The speckle filter (include/vo_hip.h, "Speckle filter") behind every dense result, on the side stream, in place:
+        getDenseStereo and getDensePoints then leave the small components out (status 6). params: True (the defaults: max_size 100,
+        max_diff 1.0) or dict(max_size=, max_diff=); None or False: off. Needs setDenseStereo. Refused while a frame is in flight."""
+        if params is None or params is False:
+            self.ctx.check(self.lib.vo_svo_set_dense_speckle(self._h, None))
+            return
+        p = _speckle_params(self.lib, params)
+        self.ctx.check(self.lib.vo_svo_set_dense_speckle(self._h, C.byref(p)))
+
+    def getDenseSpeckleStats(self):
+        """(n_removed, n_components) of the last dense result's filter; (0, 0) before any. Waits for that result's launches only."""
+        nr, nc = C.c_int(), C.c_int()
+        self.ctx.check(self.lib.vo_svo_get_dense_speckle_stats(self._h, C.byref(nr), C.byref(nc)))
+        return nr.value, nc.value
 
     def getDensePoints(self, world=True, capacity=None):
         """The accepted pixels of the last dense stereo result as points, raster order: getSemiDensePoints' dict; None before any."""

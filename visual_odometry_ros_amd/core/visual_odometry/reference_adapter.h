@@ -482,6 +482,8 @@ class StereoVO {
   // NOT in the reference's StereoVO (vo::StereoVO::setDenseStereo): a dense disparity (census + semi-global matching) of every
   // keyframe's pair; getDensePoints() is what convertPointVecToPointCloud2 of the node takes
   void setDenseStereo(const vo_dense_stereo_params *prm, int every = VO_SEMIDENSE_KEYFRAMES) { impl_.setDenseStereo(prm, every); }
+  // the speckle filter behind it (vo::StereoVO::setDenseSpeckle): getDensePoints() then leaves the small islands out
+  void setDenseSpeckle(const vo_speckle_params *prm) { impl_.setDenseSpeckle(prm); }
   PointVec getDensePoints(bool world = true) {
     vo::PointVec v;
     impl_.getDensePoints(v, nullptr, world);

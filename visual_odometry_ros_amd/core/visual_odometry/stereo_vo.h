@@ -276,6 +276,17 @@ class StereoVO {
     return p;
   }
   void setDenseStereo(const vo_dense_stereo_params *prm, int every = VO_SEMIDENSE_KEYFRAMES) { ctx_->check(vo_svo_set_dense_stereo(svo_, prm, every)); }
+  // The speckle filter behind every dense result (vo_svo_set_dense_speckle; include/vo_hip.h, "Speckle filter"): the connected
+  // components of at most max_size pixels (4-neighbours, |disparity difference| <= max_diff) are removed on the side stream, in
+  // place, so that getDensePoints leaves them out. Needs setDenseStereo. prm = nullptr: off. Throws while a frame is in flight.
+  static vo_speckle_params defaultSpeckleParams() {
+    vo_speckle_params p;
+    vo_speckle_default_params(&p);
+    return p;
+  }
+  void setDenseSpeckle(const vo_speckle_params *prm) { ctx_->check(vo_svo_set_dense_speckle(svo_, prm)); }
+  // the last result's number of removed pixels and of components (0, 0 before any); waits for that result's launches only
+  void getDenseSpeckleStats(int *n_removed, int *n_components) { ctx_->check(vo_svo_get_dense_speckle_stats(svo_, n_removed, n_components)); }
   // the accepted pixels of the last dense result as points, as getSemiDensePoints; waits for that result's launches only
   bool getDensePoints(PointVec &xyz, std::vector<float> *sigma_invd = nullptr, bool world = true, int *frame_id = nullptr) {
     int n = 0, fid = -1;

@@ -225,11 +225,14 @@ int vo_svo_dense_stereo_enqueue(vo_svo *s, int slot_l, int slot_r, int frame_id,
   VO_CHECK_HIP(c, hipStreamWaitEvent(c->stream2, d.fork, 0));
   hipStream_t keep = c->stream;
   c->stream = c->stream2;
-  const int rc = vo_ds_enqueue(c, &d.ws, slot_l, slot_r, &d.prm, d.buf.disp, (uint16_t *)d.buf.score, d.buf.sigma, d.buf.status, &d.w, &d.h);
+  int rc = vo_ds_enqueue(c, &d.ws, slot_l, slot_r, &d.prm, d.buf.disp, (uint16_t *)d.buf.score, d.buf.sigma, d.buf.status, &d.w, &d.h);
+  // vo_svo_set_dense_speckle: the filter's launches behind the decision, in place on the result's planes, in front of `done`
+  if (!rc && d.spk_on) rc = vo_spk_enqueue(c, &d.spk, d.buf.disp, d.buf.sigma, d.buf.status, d.w, d.h, &d.spk_prm);
   c->stream = keep;
   if (rc) return rc;
   VO_CHECK_HIP(c, hipEventRecord(d.done, c->stream2));
   d.have = true;
+  d.spk_have = d.spk_on;
   d.busy |= (1u << slot_l) | (1u << slot_r);  // (launches follow each other on the side stream: `done` covers every earlier one)
   d.frame_id = frame_id;
   memcpy(d.T_wc, T_wc, sizeof(d.T_wc));
@@ -252,6 +255,7 @@ void vo_svo_dense_stereo_free(vo_svo *s) {
   vo_svo_dense_stereo &d = s->ds;
   if (d.have) (void)hipEventSynchronize(d.done);
   vo_ds_buffers_free(&d.ws);
+  vo_spk_buffers_free(&d.spk);
   vo_sd_buffers_free(&d.buf);
   if (d.fork) (void)hipEventDestroy(d.fork);
   if (d.done) (void)hipEventDestroy(d.done);

@@ -43,6 +43,11 @@ struct vo_svo_dense_stereo {
   hipEvent_t fork = nullptr, done = nullptr;
   int w = 0, h = 0, frame_id = -1;
   float T_wc[16] = {};
+  // vo_svo_set_dense_speckle (dense_speckle.hip): the filter behind the decision, in place on `buf`; `spk`: its label and size planes
+  // and counters, made at the first enable; spk_have: the last result went through it
+  bool spk_on = false, spk_have = false;
+  vo_speckle_params spk_prm = {};
+  vo_spk_buffers spk;
 };
 
 // vo_svo_set_semidense_temporal (semidense_temporal.hip): the last keyframe's left plane and its map. The launches run on the side

@@ -133,6 +133,7 @@ struct vo_ctx {
   struct vo_semidense_align_state *semidense_a;  // vo_semidense_align: its state block and partial sums
   struct vo_semidense_regularize_state *semidense_r;  // vo_semidense_map_regularize with host planes: the mask's and the outputs' device copies
   struct vo_dense_stereo_state *dense_stereo;  // vo_dense_stereo: its workspace and, for host outputs, the planes (dense_stereo.hip), made on first use
+  struct vo_speckle_state *speckle;  // vo_disparity_speckle_filter: its workspace and, for host planes, their device copies (dense_speckle.hip), made on first use
 };
 
 static inline hipError_t vo_dev_malloc(vo_ctx *c, void **p, size_t bytes) {
@@ -284,6 +285,22 @@ void vo_dense_stereo_free(vo_ctx *c);
 // the launches on c->stream, into device planes (any may be null)
 int vo_ds_enqueue(vo_ctx *c, vo_ds_buffers *b, int slot_l, int slot_r, const vo_dense_stereo_params *p, float *disp, uint16_t *cost, float *sigma,
                   uint8_t *status, int *W_out, int *H_out);
+
+// The speckle filter for disparity planes (dense_speckle.hip; include/vo_hip.h, "Speckle filter"): the workspace — the counters, the
+// label plane and the size plane in one allocation that grows when a call needs more.
+struct vo_spk_buffers {
+  void *ws = nullptr;
+  size_t ws_bytes = 0;
+};
+int vo_spk_reserve(vo_ctx *c, vo_spk_buffers *b, int W, int H);
+void vo_spk_buffers_free(vo_spk_buffers *b);
+void vo_speckle_free(vo_ctx *c);
+int vo_spk_check_params(vo_ctx *c, const vo_speckle_params *p);
+int32_t *vo_spk_label(const vo_spk_buffers *b);
+int32_t *vo_spk_size(const vo_spk_buffers *b, int W, int H);
+int *vo_spk_counters(const vo_spk_buffers *b);  // [0] n_removed, [1] n_components
+// the four launches on c->stream, in place on DEVICE planes (sigma may be null); b holds the shape (vo_spk_reserve)
+int vo_spk_enqueue(vo_ctx *c, vo_spk_buffers *b, float *disp, float *sigma, uint8_t *status, int W, int H, const vo_speckle_params *p);
 
 // The temporal semi-dense search (semidense_temporal.hip; include/vo_hip.h, "Semi-dense temporal"): a key plane, the four planes of a
 // map and — the context's operator — the score plane or — a driver's option — the keyframe's ignore mask: one allocation sized by
