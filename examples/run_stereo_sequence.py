@@ -25,7 +25,9 @@ map when the next keyframe replaces it (the last one at the end); FILE.ply has x
 --semidense-world-reanchor [MIN_MOVE]: the map follows the local bundle adjustment, so that it agrees with the keyframe poses;
 --semidense-world-carve [MARGIN]: every integration is followed by a free-space carve, FILE.ply gets a `free` property behind
 `keyframes` — the number of later rays that passed through the voxel — and --semidense-world-max-free NUM DEN writes only the voxels
-with free * DEN <= count * NUM).
+with free * DEN <= count * NUM; --semidense-world-source raw|regularized|dense|merged: what is integrated — with --dense DIR, `dense` is
+every keyframe's dense result and `merged` the keyframe's map merged per pixel with it, so that the world map holds walls as well as
+edges; --semidense-world-merge-chi C and --semidense-world-keep-obs N set that merge's gate and its rule for a disagreement).
 --semidense-regularize: with --semidense-temporal, a regularised copy of the map is kept next to it (entries their
 neighbours contradict removed, high-gradient holes whose neighbours agree filled, values smoothed) and written as
 `semidense_regularized_<keyframe's frame id>.ply` wherever the fused file is written; its filled pixels have one observation, so N
@@ -146,7 +148,22 @@ def semidense_options(args):
             raise SystemExit("--semidense-world-reanchor needs --semidense DIR")
         if args.semidense_world_carve is not None or args.semidense_world_max_free is not None:
             raise SystemExit("--semidense-world-carve / --semidense-world-max-free need --semidense DIR")
+        if args.semidense_world_source is not None or args.semidense_world_merge_chi is not None or args.semidense_world_keep_obs is not None:
+            raise SystemExit("--semidense-world-source / --semidense-world-merge-chi / --semidense-world-keep-obs need --semidense DIR")
         return {}
+    src = args.semidense_world_source
+    if src is not None and not args.semidense_world:
+        raise SystemExit("--semidense-world-source needs --semidense-world FILE.ply")
+    if src in ("dense", "merged") and args.dense is None:
+        raise SystemExit(f"--semidense-world-source {src} needs --dense DIR: the world map then reads every keyframe's dense result")
+    if src == "regularized" and not args.semidense_regularize:
+        raise SystemExit("--semidense-world-source regularized needs --semidense-regularize")
+    if (args.semidense_world_merge_chi is not None or args.semidense_world_keep_obs is not None) and src not in ("dense", "merged"):
+        raise SystemExit("--semidense-world-merge-chi / --semidense-world-keep-obs need --semidense-world-source dense | merged")
+    if args.semidense_world_merge_chi is not None and not (0 < args.semidense_world_merge_chi < float("inf")):
+        raise SystemExit("--semidense-world-merge-chi C: finite, > 0")
+    if args.semidense_world_keep_obs is not None and not 0 <= args.semidense_world_keep_obs <= 256:
+        raise SystemExit("--semidense-world-keep-obs N: 0..256")
     if args.semidense_world and not args.semidense_temporal:
         raise SystemExit("--semidense-world needs --semidense-temporal")
     if (args.semidense_voxel is not None or args.semidense_world_min_keyframes is not None) and not args.semidense_world:
@@ -194,6 +211,11 @@ def semidense_options(args):
                                reanchor=True if args.semidense_world_reanchor == 0 else {"min_move": args.semidense_world_reanchor})
         if args.semidense_world_carve is not None:
             sd["world"] = dict({} if sd["world"] is True else sd["world"], carve={"margin": args.semidense_world_carve})
+        if src is not None:
+            sd["world"] = dict({} if sd["world"] is True else sd["world"], source=src)
+            mg = {k: v for k, v in (("chi", args.semidense_world_merge_chi), ("keep_obs", args.semidense_world_keep_obs)) if v is not None}
+            if mg:
+                sd["world"]["merge"] = mg
     if args.semidense_align:
         sd["align"] = True
         if args.semidense_align_levels is not None or args.semidense_align_start is not None:
@@ -283,6 +305,13 @@ def parse_args(argv=None):
     ap.add_argument("--semidense-world-carve", type=float, nargs="?", const=2.0, default=None, metavar="MARGIN",
                     help="--semidense-world: free-space carving: every integration is followed by a march of the map's rays through the "
                          "table, to MARGIN voxels (default 2) in front of their surface; FILE.ply gets a `free` property")
+    ap.add_argument("--semidense-world-source", choices=("raw", "regularized", "dense", "merged"), default=None,
+                    help="--semidense-world: what is integrated: the keyframe's map (raw, the default), its regularised copy, the keyframe's "
+                         "dense result (dense) or the map merged per pixel with that result (merged); dense and merged need --dense DIR")
+    ap.add_argument("--semidense-world-merge-chi", type=float, default=None, metavar="C",
+                    help="--semidense-world-source dense | merged: the map and the dense value agree within C sigma (default 3)")
+    ap.add_argument("--semidense-world-keep-obs", type=int, default=None, metavar="N",
+                    help="--semidense-world-source merged: where they disagree, a map entry with N observations or more is kept (default 2)")
     ap.add_argument("--semidense-world-max-free", type=int, nargs=2, default=None, metavar=("NUM", "DEN"),
                     help="--semidense-world-carve: write only the voxels with free * DEN <= count * NUM")
     ap.add_argument("--semidense-align", default=None, metavar="FILE",

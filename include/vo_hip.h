@@ -852,7 +852,7 @@ int vo_svo_get_semidense_points(vo_svo *svo, int world, int cap, float *xyz, flo
  * result's event only. All three: VO_ERR_INVALID while a frame is in flight and on a MonoVO's driver; the getters also with the
  * option off. Independent of vo_svo_set_semidense: either, both or neither may be on.
  * Out of scope: the driver's world map, temporal map or propagation taking this result as their source (the operators above take
- * the planes: that is the follow-up); gradient-adaptive p2; speckle and median filters; hole filling; a right-image mask;
+ * the planes; the world map's driver option since added: "Semi-dense map merge"); gradient-adaptive p2; speckle and median filters; hole filling; a right-image mask;
  * sub-pixel costs; more than 256 disparities; MonoVO and vo_batch; any use of the disparity in the odometry. */
 typedef struct {
   int d_min;        /* 0 */
@@ -904,8 +904,8 @@ int vo_svo_get_dense_points(vo_svo *svo, int world, int cap, float *xyz, float *
  * unchanged. vo_svo_get_dense_speckle_stats: n_removed and n_components of the last result (0, 0 before any that went through
  * the filter; either may be NULL); waits for that result's event only. Both: VO_ERR_INVALID while a frame is in flight and on a
  * MonoVO's driver; the getter also with the option off.
- * Out of scope: the driver's world map, temporal map or propagation taking the dense result as their source (still the
- * follow-up, now with a filter in front of it); a median filter; hole filling; 8-connectivity; fixed-point disparities as
+ * Out of scope: the driver's world map taking the dense result as its source (since added: "Semi-dense map merge" below);
+ * its temporal map or propagation doing so; a median filter; hole filling; 8-connectivity; fixed-point disparities as
  * OpenCV's filterSpeckles takes; the filter on the driver's semi-dense result (the operator takes any planes, but a map of thin
  * edges would lose most of itself); MonoVO and vo_batch. */
 #define VO_DISPARITY_SPECKLE 6 /* status of a removed pixel (the semi-dense operator uses 0..5) */
@@ -920,6 +920,69 @@ int vo_disparity_speckle_filter(vo_ctx *ctx, float *disparity, float *sigma_invd
                                 int on_device);
 int vo_svo_set_dense_speckle(vo_svo *svo, const vo_speckle_params *prm);
 int vo_svo_get_dense_speckle_stats(vo_svo *svo, int *n_removed, int *n_components);
+
+/* ---- Semi-dense map merge: a keyframe's map and a disparity result of the same keyframe, per pixel --------------
+ * The semi-dense chain measures edges well and covers little; the dense operator covers nearly everything and measures an edge worse.
+ * The merge takes, per pixel, the better of what the two have: the fusion where they agree, the map where several frames outvote one
+ * dense decision, the dense value where it is the only one. float32, every operation rounded on its own (no FMA), in the order
+ * written; the counts are integers. tests/semidense_map_merge_restatement.py restates it.
+ *   inputs     a map: invd, sigma f32, n_obs u8 (all three NULL: no map); a disparity result — a dense or a semi-dense one, filtered or
+ *              not —: disparity, sigma_invd f32, status u8, with bf > 0; all W x H, tightly packed, W, H >= 1, W H <= 2^31 - 1.
+ *   params     chi > 0, finite (default 3, the propagation's); keep_obs in 0..256 (default 2). chi2 = chi chi.
+ *   m          the map has an entry at pixel j: a map is given and n_obs[j] >= 1.
+ *   s          the result has one: rho_d, sig_d and the count n_d are what vo_semidense_map_seed writes for the pixel (rho_d =
+ *              disparity[j] / bf, sig_d = sigma_invd[j], n_d = 1 where status[j] == 1; else 0, 0, 0 — the same device function), and
+ *              s is n_d >= 1. Status 6 (VO_DISPARITY_SPECKLE) and every other status but 1 therefore give no entry, whatever bits
+ *              their disparity and sigma_invd hold; a disparity of 0 under status 1 is an entry like any other (the seed makes one).
+ *   neither    invd = sigma = 0, n_obs = 0, origin 0.
+ *   m only     the map's three values, every bit, origin 1.
+ *   s only     rho_d, sig_d, n_d, origin 2.
+ *   both       the test and the fusion of the propagation's resolve (the same device function), the map in the warped source's
+ *              role and the result in the static one's: dd = invd - rho_d, s2 = sigma sigma, m2 = sig_d sig_d, sum = s2 + m2.
+ *              agree iff sum > 0 and dd dd <= chi2 sum (a NaN anywhere fails): invd = (invd m2 + rho_d s2) / sum,
+ *              sigma = sqrtf((s2 m2) / sum), n_obs = min(255, n_obs + 1), origin 3.
+ *              Otherwise, where the map's n_obs >= keep_obs: the map's three values, every bit, origin 4 (several frames outvote
+ *              one decision); else invd = sigma = 0, n_obs = 0, origin 5 (one of two single measurements is grossly wrong and
+ *              nothing says which). keep_obs = 0 always keeps the map, 256 never.
+ *   counts     counts[k], k = 0..5: the number of pixels with origin k; they sum to W H.
+ * vo_semidense_map_merge: the outputs invd, sigma, n_obs are required, origin and counts may be NULL; host planes, or all device
+ * planes with on_device (counts is a host array of 6 either way). An output plane may be the input plane of the same kind (invd on
+ * the map's invd, sigma on its sigma, n_obs on its n_obs): the operator is per pixel and the lane that writes a pixel is the only one
+ * that reads it. A device pointer may have any alignment: planes that are not all 16-byte (f32) and 4-byte (u8) aligned take a path
+ * that moves single elements, with the same bits. One launch; synchronous. VO_ERR_INVALID: chi not finite or <= 0, keep_obs outside
+ * 0..256, bf not positive, a missing plane, a partial map trio. The context keeps 64 bytes of counts and, for host planes, a device copy
+ * of 28 bytes a pixel that grows when a call needs more.
+ *
+ * StereoVO: vo_svo_set_semidense_world(svo, prm, source) also takes source = VO_SEMIDENSE_WORLD_DENSE (the merge without a map: the
+ * dense result seeded) and VO_SEMIDENSE_WORLD_MERGED (the keyframe's fused map merged with the dense result of the keyframe's own
+ * pair). Both need vo_svo_set_dense_stereo on next to the temporal option — VO_ERR_INVALID otherwise — and make one allocation at the
+ * first enable of such a source: 64 bytes of counts, the keyframe's dense planes (9 bytes a pixel) and the merged planes with origin
+ * (10 bytes a pixel) for max_width x max_height. One rule for either `every` of the dense option: behind the dense launches of a
+ * keyframe (and the speckle filter's, whose planes the merge then sees) the result is copied device to device on the side stream
+ * into the option's planes. When the keyframe is replaced (or at the flush) ONE merge launch on the side stream writes the merged
+ * planes, and the re-anchoring's ring, the integration and the carve take those exactly as they take the regularised ones. A keyframe
+ * without a dense result of its own pair (the source or the dense option switched on after it, the dense option off, another size)
+ * is not integrated, and a later flush does not integrate it either. vo_svo_set_semidense_world_merge(svo, prm) sets chi and
+ * keep_obs for the merges enqueued from then on (prm NULL: the defaults). vo_svo_get_semidense_world_source: the planes, origin and
+ * counts (any may be NULL) of the last merge the driver enqueued, its size (0 x 0 where there is none) and keyframe; waits for the
+ * side stream's last launch only. Both: VO_ERR_INVALID while a frame is in flight; the getter also with the world option off. With
+ * these sources on, the odometry's results, the semi-dense and dense results and the keyframes' poses are the same bits.
+ * Out of scope: the world option without the temporal option; the temporal search, the propagation or the alignment reading the merged
+ * map; the dense value as a prior of the temporal search; trimming dense pixels at depth discontinuities, a median filter, hole
+ * filling; decimating the dense input; a tighter refusal bound or a growing table; re-merging when the map changes after its
+ * integration; MonoVO and vo_batch. */
+typedef struct {
+  float chi;     /* 3.0 */
+  int keep_obs;  /* 2 */
+} vo_semidense_map_merge_params;
+int vo_semidense_map_merge_default_params(vo_semidense_map_merge_params *prm);
+int vo_semidense_map_merge(vo_ctx *ctx, const float *map_invd, const float *map_sigma, const uint8_t *map_n_obs, const float *disparity,
+                           const float *sigma_invd, const uint8_t *status, int width, int height, float bf,
+                           const vo_semidense_map_merge_params *prm, float *invd, float *sigma, uint8_t *n_obs, uint8_t *origin,
+                           uint64_t *counts, int on_device);
+int vo_svo_set_semidense_world_merge(vo_svo *svo, const vo_semidense_map_merge_params *prm);
+int vo_svo_get_semidense_world_source(vo_svo *svo, float *invd, float *sigma, uint8_t *n_obs, uint8_t *origin, int *width, int *height,
+                                      int *frame_id, uint64_t *counts);
 
 /* ---- Semi-dense temporal: the keyframe's pixels searched in the following left images, fused per keyframe ----
  * The second half of the reference author's semi-dense prototype, read for intent only: a pixel of the keyframe's left image is
@@ -1449,7 +1512,7 @@ typedef struct {
 typedef struct {
   unsigned long long occupied, capacity, integrations, refused, inserted, skipped, out_of_range;
 } vo_semidense_world_info;
-enum { VO_SEMIDENSE_WORLD_RAW = 0, VO_SEMIDENSE_WORLD_REGULARIZED = 1 };
+enum { VO_SEMIDENSE_WORLD_RAW = 0, VO_SEMIDENSE_WORLD_REGULARIZED = 1, VO_SEMIDENSE_WORLD_DENSE = 2, VO_SEMIDENSE_WORLD_MERGED = 3 };  /* 2, 3: "Semi-dense map merge" */
 typedef struct vo_semidense_world vo_semidense_world;
 int vo_semidense_world_default_params(vo_semidense_world_params *prm);
 int vo_semidense_world_create(vo_ctx *ctx, const vo_semidense_world_params *prm, vo_semidense_world **wm);

@@ -13,4 +13,5 @@ from .api import (Context, FeatureTracker, MotionEstimator, FeatureExtractor,  #
                   se3_adjoint, SemiDenseResult, SemiDenseMap, semidense_disparity_range, SemiDensePropagated, SemiDenseAligned, SemiDenseAlignedLevel,
                   SEMIDENSE_ALIGN_STATUS, SemiDenseAlignedAffineLevel, SEMIDENSE_ALIGN_AFFINE_STATUS,
                   SemiDenseRegularized, SEMIDENSE_RSTATUS, SemiDenseWorld, SemiDenseWorldPoints, SemiDenseWorldFreePoints, SEMIDENSE_WORLD_SOURCE,
-                  DenseStereoResult, DENSE_STEREO_DISPARITIES, SpeckleResult, DISPARITY_SPECKLE)
+                  DenseStereoResult, DENSE_STEREO_DISPARITIES, SpeckleResult, DISPARITY_SPECKLE,
+                  SemiDenseMerged, SEMIDENSE_MERGE_ORIGIN)

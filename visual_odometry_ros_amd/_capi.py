@@ -117,6 +117,10 @@ class SpeckleParams(C.Structure):  # vo_speckle_params
     _fields_ = [("max_size", C.c_int), ("max_diff", C.c_float)]
 
 
+class SemiDenseMapMergeParams(C.Structure):  # vo_semidense_map_merge_params
+    _fields_ = [("chi", C.c_float), ("keep_obs", C.c_int)]
+
+
 class SemiDenseTemporalParams(C.Structure):  # vo_semidense_temporal_params
     _fields_ = [("hw", C.c_int), ("hh", C.c_int), ("g_min", C.c_int), ("thres_best", C.c_float), ("thres_peak", C.c_float),
                 ("peak_px", C.c_int), ("edge_px", C.c_int), ("eps_edge", C.c_float), ("eps_epi", C.c_float), ("eps_scale", C.c_float),
@@ -233,6 +237,8 @@ SYMBOLS = [
     "vo_svo_set_dense_stereo", "vo_svo_get_dense_stereo", "vo_svo_get_dense_points",
     "vo_speckle_default_params", "vo_speckle_workspace", "vo_disparity_speckle_filter",
     "vo_svo_set_dense_speckle", "vo_svo_get_dense_speckle_stats",
+    "vo_semidense_map_merge_default_params", "vo_semidense_map_merge", "vo_svo_set_semidense_world_merge",
+    "vo_svo_get_semidense_world_source",
     "vo_semidense_temporal_default_params", "vo_semidense_map_seed", "vo_semidense_temporal", "vo_semidense_map_points",
     "vo_svo_set_semidense_temporal", "vo_svo_get_semidense_map", "vo_svo_get_semidense_map_points",
     "vo_semidense_propagate_default_params", "vo_semidense_map_propagate", "vo_svo_set_semidense_propagate", "vo_svo_get_semidense_origin",
@@ -366,6 +372,10 @@ def load():
     lib.vo_disparity_speckle_filter.argtypes = [vp, vp, vp, vp, ci, ci, vp, vp, vp, vp, vp, ci]
     lib.vo_svo_set_dense_speckle.argtypes = [vp, vp]
     lib.vo_svo_get_dense_speckle_stats.argtypes = [vp, vp, vp]
+    lib.vo_semidense_map_merge_default_params.argtypes = [vp]
+    lib.vo_semidense_map_merge.argtypes = [vp, vp, vp, vp, vp, vp, vp, ci, ci, C.c_float, vp, vp, vp, vp, vp, vp, ci]
+    lib.vo_svo_set_semidense_world_merge.argtypes = [vp, vp]
+    lib.vo_svo_get_semidense_world_source.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.vo_semidense_temporal_default_params.argtypes = [vp]
     lib.vo_semidense_map_seed.argtypes = [vp, vp, vp, vp, ci, ci, C.c_float, vp, vp, vp, vp, ci]
     lib.vo_semidense_temporal.argtypes = [vp, vp, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp, ci]

@@ -238,7 +238,28 @@ def _semidense_regularize_params(lib, params):
     return p
 
 
-SEMIDENSE_WORLD_SOURCE = {"raw": 0, "regularized": 1}
+SEMIDENSE_WORLD_SOURCE = {"raw": 0, "regularized": 1, "dense": 2, "merged": 3}
+SEMIDENSE_MERGE_ORIGIN = {0: "nothing", 1: "the map's", 2: "the result's", 3: "fused", 4: "inconsistent: the map kept", 5: "inconsistent: dropped"}
+
+
+class SemiDenseMerged(collections.namedtuple("SemiDenseMerged", "invd sigma n_obs origin counts frame_id", defaults=(None,))):
+    """A map merged with a disparity result (include/vo_hip.h, "Semi-dense map merge"): invd, sigma float32 (height, width), n_obs uint8
+    — a map like a SemiDenseMap: semiDenseAlign, semiDenseMapRegularize, SemiDenseWorld.integrate and semiDenseMapPoints take it —,
+    origin uint8 (the keys of SEMIDENSE_MERGE_ORIGIN) and counts uint64 [6], the number of pixels per origin; from a driver also the
+    keyframe's frame id. None for planes in device memory."""
+    __slots__ = ()
+
+
+def _semidense_merge_params(lib, params):
+    """keyword parameters -> vo_semidense_map_merge_params: the C defaults, then the caller's fields (chi, keep_obs)"""
+    p = _capi.SemiDenseMapMergeParams()
+    lib.vo_semidense_map_merge_default_params(C.byref(p))
+    known = {f[0] for f in _capi.SemiDenseMapMergeParams._fields_}
+    for k, v in ({} if params is True else dict(params)).items():
+        if k not in known:
+            raise ValueError(f"semi-dense map merge: unknown parameter {k!r}; known: {sorted(known)}")
+        setattr(p, k, v)
+    return p
 
 
 class SemiDenseWorldPoints(collections.namedtuple("SemiDenseWorldPoints", "index xyz weight count keyframes grey sums", defaults=(None,))):
@@ -834,6 +855,49 @@ class Context:
         self.check(self.lib.vo_semidense_map_seed(self._h, d.ctypes.data, sg.ctypes.data, st.ctypes.data, d.shape[1], d.shape[0], float(bf),
                                                   invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data, ts.ctypes.data, 0))
         return SemiDenseMap(invd, sigma, n_obs, ts, None, None, None, None)
+
+    def semiDenseMapMerge(self, map, dense, bf, chi=3.0, keep_obs=2, out=None, on_device=None):
+        """A map merged per pixel with a disparity result of the same keyframe (include/vo_hip.h, "Semi-dense map merge"): the fusion
+        where both have the pixel and agree within chi, the map where they disagree and it has keep_obs observations at least, the
+        result's value where it is the only one. map: a SemiDenseMap / SemiDenseRegularized / dict(invd=, sigma=, n_obs=) of arrays, or
+        None (the result seeded); dense: a DenseStereoResult / SemiDenseResult / dict(disparity=, sigma_invd=, status=) / the three
+        planes as a tuple. Returns a SemiDenseMerged; the arguments stay. With on_device=(width, height) every plane is a DEVICE address
+        (any alignment) and out=dict(invd=, sigma=, n_obs=[, origin=]) names the outputs — each may be the map's plane of the same kind —;
+        the result then holds the counts only."""
+        p = _semidense_merge_params(self.lib, dict(chi=chi, keep_obs=keep_obs))
+        getm = None if map is None else ((lambda k: getattr(map, k)) if isinstance(map, tuple) and hasattr(map, "_fields") else (lambda k: map[k]))
+        if hasattr(dense, "_fields"):
+            dp = [getattr(dense, k) for k in ("disparity", "sigma_invd", "status")]
+        elif isinstance(dense, dict):
+            dp = [dense[k] for k in ("disparity", "sigma_invd", "status")]
+        else:
+            dp = list(dense)
+            if len(dp) != 3:
+                raise ValueError("semiDenseMapMerge: dense is a result or its planes disparity, sigma_invd, status")
+        counts = np.zeros(6, np.uint64)
+        if on_device is not None:
+            w, h = on_device
+            mp = [None] * 3 if map is None else [C.c_void_p(getm(k)) for k in ("invd", "sigma", "n_obs")]
+            self.check(self.lib.vo_semidense_map_merge(self._h, *mp, *(C.c_void_p(x) for x in dp), int(w), int(h), float(bf), C.byref(p),
+                                                       *(C.c_void_p(out[k]) for k in ("invd", "sigma", "n_obs")),
+                                                       C.c_void_p(out["origin"]) if out.get("origin") else None, counts.ctypes.data, 1))
+            return SemiDenseMerged(None, None, None, None, counts)
+        d, sg, st = np.ascontiguousarray(dp[0], np.float32), np.ascontiguousarray(dp[1], np.float32), np.ascontiguousarray(dp[2], np.uint8)
+        if d.ndim != 2 or sg.shape != d.shape or st.shape != d.shape:
+            raise ValueError("disparity, sigma_invd and status are planes of one (height, width)")
+        mp = [None] * 3
+        if map is not None:
+            keep = [np.ascontiguousarray(getm("invd"), np.float32), np.ascontiguousarray(getm("sigma"), np.float32),
+                    np.ascontiguousarray(getm("n_obs"), np.uint8)]
+            if any(x.shape != d.shape for x in keep):
+                raise ValueError("the map's planes and the result's are of one (height, width)")
+            mp = [x.ctypes.data for x in keep]
+        invd, sigma = np.zeros(d.shape, np.float32), np.zeros(d.shape, np.float32)
+        n_obs, origin = np.zeros(d.shape, np.uint8), np.zeros(d.shape, np.uint8)
+        self.check(self.lib.vo_semidense_map_merge(self._h, *mp, d.ctypes.data, sg.ctypes.data, st.ctypes.data, d.shape[1], d.shape[0], float(bf),
+                                                   C.byref(p), invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data, origin.ctypes.data,
+                                                   counts.ctypes.data, 0))
+        return SemiDenseMerged(invd, sigma, n_obs, origin, counts)
 
     def semiDenseTemporal(self, key, slot_cur, K, T_ck, map, key_on_device=None, map_on_device=False, **params):
         """One temporal launch: the key plane's pixels searched in slot_cur's level-0 plane along the epipolar lines of T_ck (4 x 4,
@@ -2032,14 +2096,21 @@ class StereoVO:
                 self.setSemiDenseAlign({} if align is True else align)
             if regularize:
                 self.setSemiDenseRegularize({} if regularize is True else regularize)
-            if world:
+            world_late = bool(world) and world is not True and dict(world).get("source") in ("dense", "merged")
+            if world_late and dense is None:
+                raise ValueError('semidense: world source "dense" / "merged" needs dense=')
+            if world and not world_late:
                 self.setSemiDenseWorld({} if world is True else world)
+        else:
+            world, world_late = None, False
         if dense is not None:
             ds = dict(dense)
             speckle = ds.pop("speckle", None)
             self.setDenseStereo(ds, every=ds.pop("every", "keyframe"))
             if speckle is not None and speckle is not False:
                 self.setDenseSpeckle(speckle)
+        if world_late:  # (the sources that read the dense result need that option on first)
+            self.setSemiDenseWorld(world)
         self._info = SvoFrameInfo()
         self.stats_frame = []  # AlgorithmStatistics::FrameStatistics::Twc per frame (stereo_vo.cpp:979-980)
 
@@ -2297,8 +2368,9 @@ class StereoVO:
         replaced, one launch on the side stream integrates its map, with its T_wc and key plane, into a hash table of voxels;
         flushSemiDenseWorld() integrates the current keyframe's at the end of a sequence, getSemiDenseWorld() reads the voxels. The
         odometry's results, the semi-dense results and the map do not change. params: dict(voxel=, capacity_log2=, min_obs=, z_max=,
-        source="raw" | "regularized") ({}: the defaults), None: off. Needs setSemiDenseTemporal; source="regularized" also
-        setSemiDenseRegularize. Refused while a frame is in flight."""
+        source="raw" | "regularized" | "dense" | "merged", merge=dict(chi=, keep_obs=)) ({}: the defaults), None: off. Needs
+        setSemiDenseTemporal; source="regularized" also setSemiDenseRegularize; "dense" (the keyframe's dense result seeded) and "merged"
+        (the keyframe's map merged with it: "Semi-dense map merge") also setDenseStereo. Refused while a frame is in flight."""
         if params is None:
             self.ctx.check(self.lib.vo_svo_set_semidense_world(self._h, None, 0))
             return
@@ -2306,6 +2378,7 @@ class StereoVO:
         src = params.pop("source", "raw")
         reanchor = params.pop("reanchor", None)
         carve = params.pop("carve", None)
+        merge = params.pop("merge", None)
         if source is not None:
             src = source
         if src not in SEMIDENSE_WORLD_SOURCE:
@@ -2316,6 +2389,31 @@ class StereoVO:
             self.setSemiDenseWorldReanchor(reanchor)
         if carve is not None:
             self.setSemiDenseWorldCarve(carve)
+        if merge is not None:
+            self.setSemiDenseWorldMerge(merge)
+
+    def setSemiDenseWorldMerge(self, params=None):
+        """chi and keep_obs of the merges the world map's sources "dense" and "merged" enqueue from now on: dict(chi=, keep_obs=);
+        None or True: the defaults (3, 2). Refused while a frame is in flight."""
+        if params is None or params is True:
+            self.ctx.check(self.lib.vo_svo_set_semidense_world_merge(self._h, None))
+            return
+        p = _semidense_merge_params(self.lib, params)
+        self.ctx.check(self.lib.vo_svo_set_semidense_world_merge(self._h, C.byref(p)))
+
+    def getSemiDenseWorldSource(self):
+        """What the world map's source "dense" or "merged" last integrated: a SemiDenseMerged with the keyframe's frame id — the planes,
+        origin and counts of the last merge the driver enqueued —, or None where there is none yet. Waits for the side stream only."""
+        w, h, fid = C.c_int(), C.c_int(), C.c_int()
+        self.ctx.check(self.lib.vo_svo_get_semidense_world_source(self._h, None, None, None, None, C.byref(w), C.byref(h), C.byref(fid), None))
+        if w.value == 0:
+            return None
+        shape = (h.value, w.value)
+        invd, sigma = np.zeros(shape, np.float32), np.zeros(shape, np.float32)
+        n_obs, origin, counts = np.zeros(shape, np.uint8), np.zeros(shape, np.uint8), np.zeros(6, np.uint64)
+        self.ctx.check(self.lib.vo_svo_get_semidense_world_source(self._h, invd.ctypes.data, sigma.ctypes.data, n_obs.ctypes.data, origin.ctypes.data,
+                                                                  C.byref(w), C.byref(h), C.byref(fid), counts.ctypes.data))
+        return SemiDenseMerged(invd, sigma, n_obs, origin, counts, fid.value)
 
     def setSemiDenseWorldCarve(self, params):
         """Free-space carving on the world map (include/vo_hip.h, "Semi-dense world map: free-space carving"): directly behind every

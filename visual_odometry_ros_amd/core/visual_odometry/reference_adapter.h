@@ -543,6 +543,13 @@ class StereoVO {
   // free-space carving on the world map (vo::StereoVO::setSemiDenseWorldCarve): prm = nullptr: off; getSemiDenseWorldFree() the
   // voxels' mean positions with their free counts, with free_den >= 1 only those with free * free_den <= count * free_num
   void setSemiDenseWorldCarve(const vo_semidense_world_carve_params *prm) { impl_.setSemiDenseWorldCarve(prm); }
+  // the world map fed from the dense result (vo::StereoVO::setSemiDenseWorldMerge; the sources VO_SEMIDENSE_WORLD_DENSE and _MERGED of
+  // setSemiDenseWorld need setDenseStereo): chi and keep_obs of the merge, and what the last merge wrote
+  void setSemiDenseWorldMerge(const vo_semidense_map_merge_params *prm) { impl_.setSemiDenseWorldMerge(prm); }
+  int getSemiDenseWorldSource(std::vector<float> *invd, std::vector<float> *sigma, std::vector<uint8_t> *n_obs, std::vector<uint8_t> *origin,
+                              int *width, int *height, uint64_t counts[6] = nullptr) {
+    return impl_.getSemiDenseWorldSource(invd, sigma, n_obs, origin, width, height, counts);
+  }
   PointVec getSemiDenseWorldFree(std::vector<uint32_t> &free_count, int free_num = 0, int free_den = 0, int min_count = 1, int min_keyframes = 1) {
     vo::PointVec v;
     impl_.getSemiDenseWorldFree(v, free_count, free_num, free_den, min_count, min_keyframes);

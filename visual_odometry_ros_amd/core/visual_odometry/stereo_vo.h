@@ -438,6 +438,31 @@ class StereoVO {
     return p;
   }
   void setSemiDenseWorldCarve(const vo_semidense_world_carve_params *prm) { ctx_->check(vo_svo_set_semidense_world_carve(svo_, prm)); }
+  // The world map fed from the dense result (include/vo_hip.h, "Semi-dense map merge"): setSemiDenseWorld(prm, VO_SEMIDENSE_WORLD_DENSE
+  // or _MERGED) needs setDenseStereo; setSemiDenseWorldMerge sets chi and keep_obs of the merges enqueued from then on (nullptr: the
+  // defaults 3, 2); getSemiDenseWorldSource returns what the last merge wrote — the planes sized width x height, origin and the six
+  // counts; any vector may be null — and its keyframe's frame id, -1 and 0 x 0 where there is none. Both throw while a frame is in flight.
+  static vo_semidense_map_merge_params defaultSemiDenseWorldMergeParams() {
+    vo_semidense_map_merge_params p;
+    vo_semidense_map_merge_default_params(&p);
+    return p;
+  }
+  void setSemiDenseWorldMerge(const vo_semidense_map_merge_params *prm) { ctx_->check(vo_svo_set_semidense_world_merge(svo_, prm)); }
+  int getSemiDenseWorldSource(std::vector<float> *invd, std::vector<float> *sigma, std::vector<uint8_t> *n_obs, std::vector<uint8_t> *origin,
+                              int *width, int *height, uint64_t counts[6] = nullptr) {
+    int w = 0, h = 0, frame_id = -1;
+    ctx_->check(vo_svo_get_semidense_world_source(svo_, nullptr, nullptr, nullptr, nullptr, &w, &h, &frame_id, nullptr));
+    const size_t n = (size_t)w * (size_t)h;
+    if (invd) invd->assign(n, 0.0f);
+    if (sigma) sigma->assign(n, 0.0f);
+    if (n_obs) n_obs->assign(n, 0);
+    if (origin) origin->assign(n, 0);
+    ctx_->check(vo_svo_get_semidense_world_source(svo_, invd ? invd->data() : nullptr, sigma ? sigma->data() : nullptr,
+                                                  n_obs ? n_obs->data() : nullptr, origin ? origin->data() : nullptr, &w, &h, &frame_id, counts));
+    if (width) *width = w;
+    if (height) *height = h;
+    return frame_id;
+  }
   vo_semidense_world_carve_info getSemiDenseWorldCarveStats() {
     vo_semidense_world_carve_info info;
     ctx_->check(vo_svo_get_semidense_world_carve_stats(svo_, &info));

@@ -230,6 +230,11 @@ int vo_svo_dense_stereo_enqueue(vo_svo *s, int slot_l, int slot_r, int frame_id,
   if (!rc && d.spk_on) rc = vo_spk_enqueue(c, &d.spk, d.buf.disp, d.buf.sigma, d.buf.status, d.w, d.h, &d.spk_prm);
   c->stream = keep;
   if (rc) return rc;
+  // vo_svo_set_semidense_world with a source that reads this result: a keyframe's planes are kept for the merge at its end
+  if (s->sdw.on && s->sdw.source >= VO_SEMIDENSE_WORLD_DENSE) {
+    rc = vo_svo_sdm_keep_dense(s, frame_id);
+    if (rc) return rc;
+  }
   VO_CHECK_HIP(c, hipEventRecord(d.done, c->stream2));
   d.have = true;
   d.spk_have = d.spk_on;

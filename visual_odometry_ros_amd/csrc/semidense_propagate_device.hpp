@@ -21,6 +21,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "semidense_map_fuse.hpp"  // sdm_fuse: the consistency test and the fusion, shared with the map merge
+
 #if defined(__HIP_DEVICE_COMPILE__)
 #define SDP_MUL(a, b) __fmul_rn((a), (b))
 #define SDP_ADD(a, b) __fadd_rn((a), (b))
@@ -131,12 +133,8 @@ __global__ __launch_bounds__(SDP_NT) void semidense_propagate_resolve_kernel(Sdp
   float o_invd = 0.0f, o_sig = 0.0f;
   int o_no = 0, org = 0;
   if (st && has) {
-    const float dd = SDP_SUB(invd_b, rho_s);
-    const float s2 = SDP_MUL(sigma_b, sigma_b), m2 = SDP_MUL(sig_s, sig_s), sum = SDP_ADD(s2, m2);
-    if (sum > 0.0f && SDP_MUL(dd, dd) <= SDP_MUL(a.chi2, sum)) {
+    if (sdm_fuse(invd_b, sigma_b, rho_s, sig_s, a.chi2, &o_invd, &o_sig)) {
       org = 3;
-      o_invd = SDP_ADD(SDP_MUL(invd_b, m2), SDP_MUL(rho_s, s2)) / sum;
-      o_sig = sqrtf(SDP_MUL(s2, m2) / sum);
       o_no = no < 255 ? no + 1 : 255;
     } else {
       org = 4, o_invd = rho_s, o_sig = sig_s, o_no = 1;

@@ -25,7 +25,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "semidense_sample.hpp"  // SDT_MUL / SDT_ADD / SDT_SUB, sdt_q, sdt_in, sdt_sample
+#include "semidense_map_fuse.hpp"  // sdm_seed_entry: a static result's map entry, shared with the map merge
+#include "semidense_sample.hpp"    // SDT_MUL / SDT_ADD / SDT_SUB, sdt_q, sdt_in, sdt_sample
 
 #define SDT_SEG 64           // columns per workgroup: one lane of wavefront 0 each
 #define SDT_NT 256
@@ -337,10 +338,12 @@ __global__ void semidense_map_seed_kernel(const float *disp, const float *sigma_
                                           uint8_t *n_obs, uint8_t *tstatus, int n) {
   const int i = (int)blockIdx.x * (int)blockDim.x + (int)threadIdx.x;
   if (i >= n) return;
-  const bool ok = status[i] == 1;
-  invd[i] = ok ? disp[i] / bf : 0.0f;
-  sigma[i] = ok ? sigma_invd[i] : 0.0f;
-  n_obs[i] = ok ? 1 : 0;
+  float r, sg;
+  int no;
+  sdm_seed_entry(status[i], disp[i], sigma_invd[i], bf, &r, &sg, &no);
+  invd[i] = r;
+  sigma[i] = sg;
+  n_obs[i] = (uint8_t)no;
   tstatus[i] = 0;
 }
 __global__ void semidense_map_key_kernel(const uint8_t *n_obs, uint8_t *key, int min_obs, int n) {

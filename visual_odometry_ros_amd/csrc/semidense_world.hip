@@ -609,6 +609,14 @@ int vo_svo_semidense_world_enqueue(vo_svo *s) {
     if (!r.on || !r.have || r.frame_id != t.frame_id) return VO_OK;  // no regularised planes of this keyframe: nothing to integrate
     invd = r.buf.invd, sigma = r.buf.sigma, n_obs = r.buf.n_obs;
   }
+  if (w.source == VO_SEMIDENSE_WORLD_DENSE || w.source == VO_SEMIDENSE_WORLD_MERGED) {
+    // one merge launch into planes the option owns; what follows takes them as it takes the regularised ones. No dense result of
+    // this keyframe's own pair: nothing to integrate
+    bool ok = false;
+    const int rcm = vo_svo_sdm_merge(s, &invd, &sigma, &n_obs, &ok);
+    if (rcm) return rcm;
+    if (!ok) return VO_OK;
+  }
   int rc = w.ra.on ? svo_sdw_retain(s, invd, sigma, n_obs) : VO_OK;  // (in front of everything that overwrites the outgoing map)
   if (rc) return rc;
   rc = sdw_enqueue(w.wm, s->c->stream2, invd, sigma, n_obs, t.buf.key, t.w, t.w, t.h, s->prm.frame.Kl, t.T_wk);
@@ -660,6 +668,7 @@ void vo_svo_semidense_world_free(vo_svo *s) {
     (void)hipSetDevice(s->c->device);
     (void)hipFree(s->sdw.ra.ring);
   }
+  vo_svo_sdm_free(s);
   vo_semidense_world_destroy(s->sdw.wm);
   s->sdw = vo_svo_semidense_world();
 }
@@ -686,8 +695,12 @@ extern "C" int vo_svo_set_semidense_world(vo_svo *s, const vo_semidense_world_pa
   }
   if (!s->sdt.on || !s->sd.on)
     VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world: needs the temporal option: vo_svo_set_semidense_temporal first");
-  if (source != VO_SEMIDENSE_WORLD_RAW && source != VO_SEMIDENSE_WORLD_REGULARIZED)
-    VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world: source=%d: expected VO_SEMIDENSE_WORLD_RAW or _REGULARIZED", source);
+  if (source != VO_SEMIDENSE_WORLD_RAW && source != VO_SEMIDENSE_WORLD_REGULARIZED && source != VO_SEMIDENSE_WORLD_DENSE &&
+      source != VO_SEMIDENSE_WORLD_MERGED)
+    VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world: source=%d: expected VO_SEMIDENSE_WORLD_RAW, _REGULARIZED, _DENSE or _MERGED", source);
+  const bool from_dense = source == VO_SEMIDENSE_WORLD_DENSE || source == VO_SEMIDENSE_WORLD_MERGED;
+  if (from_dense && !s->ds.on)
+    VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world: the dense and merged sources need vo_svo_set_dense_stereo first");
   if (source == VO_SEMIDENSE_WORLD_REGULARIZED && !s->sdr.on)
     VO_FAIL(c, VO_ERR_INVALID, "vo_svo_set_semidense_world: the regularised source needs vo_svo_set_semidense_regularize first");
   int rc = sdw_check_params(c, prm);
@@ -705,6 +718,10 @@ extern "C" int vo_svo_set_semidense_world(vo_svo *s, const vo_semidense_world_pa
     w.wm->prm = *prm;
     w.done = false;
     svo_sdw_forget(w);
+  }
+  if (from_dense) {  // the merged planes and the keyframe's dense copy: once, at the first enable of such a source
+    rc = vo_svo_sdm_alloc(s);
+    if (rc) return rc;
   }
   w.source = source;
   w.on = true;

@@ -121,6 +121,18 @@ struct vo_svo_semidense_world {
     unsigned long long refused_seen = 0;  // refused_removals when the log was last settled
     int n_anchors = 0;                    // anchors recorded since the table was last cleared
   } ra;
+  // the sources VO_SEMIDENSE_WORLD_DENSE and _MERGED (semidense_map_merge.hip): `buf` — the counts, the keyframe's own
+  // dense planes (copied behind its dense launches: ds_*) and the merged planes with origin, at max_width x max_height — is made at the
+  // first enable of such a source; have: a merge has been enqueued, of keyframe frame_id
+  struct {
+    vo_semidense_map_merge_params prm = {3.0f, 2};
+    void *buf = nullptr;
+    size_t np_max = 0;
+    bool ds_have = false, have = false;
+    int ds_w = 0, ds_h = 0, ds_frame_id = -1;
+    float ds_bf = 0.0f;
+    int w = 0, h = 0, frame_id = -1;
+  } mg;
 };
 
 // vo_svo_set_semidense_align (semidense_align.hip): at every frame that is not a keyframe the frame's left image is aligned against
@@ -235,6 +247,13 @@ int vo_svo_semidense_world_enqueue(vo_svo *s);
 // the local BA has just written back
 int vo_svo_semidense_world_reanchor_pass(vo_svo *s);
 void vo_svo_semidense_world_free(vo_svo *s);
+// semidense_map_merge.hip, for the world option's sources that read the dense result: the planes' one allocation; a keyframe's dense
+// planes kept (called behind the dense launches); the merge launch in front of the integration (*ok false: no dense result of the
+// outgoing keyframe, nothing launched)
+int vo_svo_sdm_alloc(vo_svo *s);
+void vo_svo_sdm_free(vo_svo *s);
+int vo_svo_sdm_keep_dense(vo_svo *s, int frame_id);
+int vo_svo_sdm_merge(vo_svo *s, const float **invd, const float **sigma, const uint8_t **n_obs, bool *ok);
 // semidense_align.hip: on the side stream (c->stream points at it) in front of a non-keyframe frame's temporal launch
 int vo_svo_semidense_align_enqueue(vo_svo *s, int slot_l, int frame_id, const float T_ck[16]);
 // (vo_svo_set_semidense_align_pyr) at a keyframe, behind the key plane's copy: the slot's coarser levels next to it

@@ -151,6 +151,7 @@ extern "C" void vo_destroy(vo_ctx *c) {
   vo_semidense_free(c);
   vo_dense_stereo_free(c);
   vo_speckle_free(c);
+  vo_semidense_merge_free(c);
   vo_sba_free(c);
   vo_orb_describe_free(c);
   vo_orb_free(c);

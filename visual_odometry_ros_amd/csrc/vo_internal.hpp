@@ -134,6 +134,7 @@ struct vo_ctx {
   struct vo_semidense_regularize_state *semidense_r;  // vo_semidense_map_regularize with host planes: the mask's and the outputs' device copies
   struct vo_dense_stereo_state *dense_stereo;  // vo_dense_stereo: its workspace and, for host outputs, the planes (dense_stereo.hip), made on first use
   struct vo_speckle_state *speckle;  // vo_disparity_speckle_filter: its workspace and, for host planes, their device copies (dense_speckle.hip), made on first use
+  struct vo_semidense_merge_state *semidense_m;  // vo_semidense_map_merge: its counts and, for host planes, their device copies (semidense_map_merge.hip), made on first use
 };
 
 static inline hipError_t vo_dev_malloc(vo_ctx *c, void **p, size_t bytes) {
@@ -301,6 +302,14 @@ int32_t *vo_spk_size(const vo_spk_buffers *b, int W, int H);
 int *vo_spk_counters(const vo_spk_buffers *b);  // [0] n_removed, [1] n_components
 // the four launches on c->stream, in place on DEVICE planes (sigma may be null); b holds the shape (vo_spk_reserve)
 int vo_spk_enqueue(vo_ctx *c, vo_spk_buffers *b, float *disp, float *sigma, uint8_t *status, int W, int H, const vo_speckle_params *p);
+
+// The map merge (semidense_map_merge.hip; include/vo_hip.h, "Semi-dense map merge"): the launch on `s` over DEVICE planes (the map's
+// three null together: no map; origin and counts may be null; counts — 6 device words — is zeroed on `s` in front of the launch)
+void vo_semidense_merge_free(vo_ctx *c);
+int vo_sdm_check_params(vo_ctx *c, const vo_semidense_map_merge_params *p);
+int vo_sdm_enqueue(vo_ctx *c, hipStream_t s, const float *m_invd, const float *m_sigma, const uint8_t *m_n_obs, const float *disp,
+                   const float *sigma_invd, const uint8_t *status, int W, int H, float bf, const vo_semidense_map_merge_params *p, float *invd,
+                   float *sigma, uint8_t *n_obs, uint8_t *origin, unsigned long long *counts);
 
 // The temporal semi-dense search (semidense_temporal.hip; include/vo_hip.h, "Semi-dense temporal"): a key plane, the four planes of a
 // map and — the context's operator — the score plane or — a driver's option — the keyframe's ignore mask: one allocation sized by
