@@ -35,7 +35,9 @@ def _reflect(p, n):
 
 
 @pytest.mark.parametrize("w,h,top,nimg", [(333, 251, 4, 2), (64, 48, 6, 1), (47, 33, 6, 1), (1241, 376, 4, 1), (160, 120, 3, 1),
-                                          (200, 150, 5, 1), (90, 70, 1, 1), (65, 65, 0, 1), (130, 40, 2, 1)])
+                                          (200, 150, 5, 1), (90, 70, 1, 1), (65, 65, 0, 1), (130, 40, 2, 1),
+                                          # narrower than the 16-byte loads and lower than the border (tests/dense_stereo_edge_cases.py)
+                                          (1, 1, 0, 1), (5, 3, 0, 1), (2, 64, 0, 1), (13, 7, 0, 2)])
 def test_pyramid_tile_kernel_every_padded_byte(oracle, emu_pyr, tmp_path, w, h, top, nimg):
     """pyr_build_kernel: every byte of every padded level plane — the level itself and its REFLECT_101 border, 40 pixels wide,
     also where a level is narrower than the border (several reflections) and where the pyramid needs a second launch (more
